@@ -4,10 +4,17 @@
 One "step" = one pass of the hot path over one batch of synthetic, HBM-resident inputs on every rank:
     3 x (unproject + ego warp + z-buffered splat)  ->  on-the-fly disk-hop emulation  ->  FC-HarDNet-70
     -> bilinear upsample + argmax   (task ``bg_forecast`` of panoptic-forecasting_amd)
-Ranks are independent (sequences shard by batch); the only collective is the end-of-run all-gather of
-the PQ accumulators.  Prints ONE JSON line on rank 0.
+Ranks are independent (sequences shard by batch); the only collectives are the end-of-run gathers of the
+per-rank step times and (--full) of the PQ accumulators.  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--replays R] [--no-graph] [--no-cpu-baseline] [--no-legs]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--replays R] [--no-graph] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-legs]]
+
+A plain run sets up, warms up, times K steps and prints the line (`value`, `ms_per_step` = milliseconds of one timed step); the
+range status of the timed region is read once afterwards.  ``--dump-outputs DIR`` then writes what the timed path computed in its
+last step (rank 0's outputs, ``dump_outputs``).  Everything else the line can carry - the per-kernel roofline pass, the PQ
+all-gather check and, at N = 1, the CPU baseline, the oracle parity and the legs listed below - runs only with ``--full``
+(``--no-cpu-baseline`` / ``--no-legs`` trim it); without it those keys are null.
 
 A step visits the rank's resident synthetic batch R times (``--replays``, default 2: 2 x 128 = 256 forecast frames per GPU per
 step, one hipGraph), so that the driver's 20 steps time about two seconds instead of a quarter of one; ``config`` states it.
@@ -21,7 +28,7 @@ convolutions of another (+3 % over starting them together: profiles/r03_experime
 RCCL; started by an external launcher it reads RANK/LOCAL_RANK/WORLD_SIZE from the environment.  It refuses to run
 when the ranks that joined differ from ``--gpus`` or the node has fewer GPUs than ranks.
 
-At N=1 the same line also carries (driver-timed, same process):
+At N=1 and with --full the same line also carries (driver-timed, same process):
     by_batch   frames/s of ONE stream at B = 1, 2, 4 frames per step (SURVEY.md 8d Config 2; the reference loop batches 2): latency
     by_batch_pipelined  the reference-shaped loop with batches in flight (export_bg.py --pipeline_depth N): B = 1, 2 per batch, N = 2
                and 3 model replicas on as many streams, eager, fresh host-inverse camera tensors every batch
@@ -70,6 +77,8 @@ SUB_BATCH = 32                  # frames per concurrent sub-batch of the headlin
 # RCCL, which refuses two ranks per device) so that the N > 1 line - per-rank times, gather, backend - is exercised on a 1-GPU box.
 # Never a measurement: the line says so (config.backend = gloo, identical `devices`)
 SHARE_GPU = os.environ.get('PF_BENCH_SHARE_GPU') == '1'
+DUMP_BYTES = 60_000_000         # --dump-outputs: array data written in all (headers aside), below the 64 MB the option allows
+DUMP_SEED = 0                   # --dump-outputs: seed of the element sample of arrays larger than their share of DUMP_BYTES
 
 
 def build_model(params):
@@ -106,12 +115,36 @@ TERM = {'short': dict(gap_len=3, predicted=False), 'mid': dict(gap_len=9, predic
 
 
 def make_batch(b, seed0, device, term='short'):
-    parts = [synth.make_inputs(b=1, t=T, h=H, w=W, seed=seed0 + i, **TERM[term]) for i in range(b)]
+    # frames are generated on host threads (the torch ops release the GIL); each comes from its own seeded generator, so the
+    # batch is the same whatever the thread count
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, min(b, torch.get_num_threads()))) as ex:
+        parts = list(ex.map(lambda i: synth.make_inputs(b=1, t=T, h=H, w=W, seed=seed0 + i, **TERM[term]), range(b)))
     inp = {k: torch.cat([p[k] for p in parts], 0) for k in parts[0]}
     # the batch dict is exactly the reference's (no pre-computed camera inverses): the model inverts K and E on the host
     # (LAPACK, like the reference) once per distinct camera tensor and afterwards hits its cache without touching the
     # stream (pc_transform_model.InverseCache) - the warm-up steps pay it, the timed region and the captured graph do not
     return {k: v.to(device) for k, v in inp.items()}
+
+
+def dump_outputs(out, dirname):
+    """--dump-outputs: every array of ``out`` (name -> tensor) as ``dirname/<name>.npy``, float64 for 32/64-bit integers and
+    float64 sources, float32 otherwise (exact for every value the path produces).  Each array gets an equal share of
+    DUMP_BYTES; a larger one is written as a fixed sample of its flattened elements: sorted indices drawn with replacement from
+    a CPU generator seeded with DUMP_SEED, so they depend only on the element count - two runs, or two builds, with the same
+    arguments write the same positions (and arrays of one shape, e.g. warped_seg / warped_depth, the same pixels)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(out))
+    for name in sorted(out):
+        t = out[name].detach()
+        wide = t.dtype in (torch.float64, torch.int32, torch.int64)
+        cap = share // (8 if wide else 4)
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(dirname, name + '.npy'), t.to(torch.float64 if wide else torch.float32).cpu().numpy())
 
 
 def source_sha():
@@ -278,7 +311,7 @@ class Workload:
         self.side = [torch.cuda.Stream() for _ in range(S - 1)]
         self.out = self.step()          # builds the plans, sizes the workspaces
         torch.cuda.synchronize()
-        self.run = self.step
+        self.run = self.step_keep
         if self.free_run_ms is not None:
             self.graphs = []
             streams = [torch.cuda.current_stream()] + self.side
@@ -356,6 +389,10 @@ class Workload:
             for i in range(1, self.S):
                 cur.wait_stream(self.side[i - 1])
         return outs
+
+    def step_keep(self):
+        """eager step: self.out holds the outputs of the latest one (a replayed graph refills its captured outputs)"""
+        self.out = self.step()
 
     def timed_free_run(self, steps, warmup, dev, barrier):
         cur = torch.cuda.current_stream()
@@ -718,10 +755,16 @@ def parse_args(argv=None):
     ap.add_argument('--replays', type=int, default=2, help='passes over the resident batch per step (one hipGraph): a step is '
                     '--replays x --batch forecast frames per GPU (20 steps then time about a second)')
     ap.add_argument('--no-graph', action='store_true', help='launch eagerly instead of replaying a hipGraph')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-legs', action='store_true', help='skip the by_batch / fp32_only legs (N=1 only)')
+    ap.add_argument('--full', action='store_true', help='besides the headline: the per-kernel roofline pass, the PQ all-gather '
+                    'check and, at N=1, the CPU baseline, oracle parity and the by_batch / pipelined / fresh-camera / '
+                    'other-resolution / fp32_only / train_step legs (off: those keys are null)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="after the timed steps, write the outputs of the last "
+                    "one (rank 0's frames) as DIR/<name>.npy, float32 / float64, at most 64 MB in all: arrays larger than "
+                    "their share as a fixed seeded sample of their elements")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline and the parity it feeds')
+    ap.add_argument('--no-legs', action='store_true', help='--full without the by_batch / fp32_only legs (N=1 only)')
     ap.add_argument('--cpu-frames', type=int, default=12)
-    ap.add_argument('--profile-steps', type=int, default=3)
+    ap.add_argument('--profile-steps', type=int, default=3, help='sub-batch forwards of the --full per-kernel pass')
     ap.add_argument('--fp32-mfma-only', action='store_true', help='headline itself without the split kernels '
                     "(model param split_f16=0): every convolution on v_mfma_f32_16x16x4_f32 / the fp32 VALU")
     ap.add_argument('--streams', type=int, default=0, help='sub-batches run concurrently on this many HIP streams '
@@ -819,19 +862,24 @@ def main():
     per_rank = pfdist.gather_objects({'rank': rank, 'ms_per_step': 1e3 * wl.local_s / args.steps, 'device': ident})
     if len({r['device'] for r in per_rank}) != len(per_rank) and not SHARE_GPU:
         raise SystemExit('bench.py: %d ranks share devices: %s' % (len(per_rank), [r['device'] for r in per_rank]))
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the models: the outputs of the last timed step as the caller receives them
+        dump_outputs(wl.outputs(), args.dump_outputs)
 
     # ---- sharded metric exchange: PQ accumulators of this rank's forecasts vs a synthetic ground truth
-    out = wl.outputs()   # the sub-batch outputs are concatenated outside the timed region
-    gt = torch.from_numpy(synth.ID2TRAINID).to(dev)[wl.batch['seg'][:, T - 1].long()].long()
-    acc = pfpq.pq_accumulate(out['seg'].long(), gt, 11)
-    allacc = pfdist.gather_accumulators(acc)
-    if int(allacc.shape[0]) != args.gpus:
-        raise SystemExit('bench.py: the PQ all-gather returned %d rank(s), --gpus %d' % (int(allacc.shape[0]), args.gpus))
-    pq_synth = pfpq.pq_from_acc(allacc.sum(0))['pq']
+    pq_gather = None
+    if args.full:
+        out = wl.outputs()   # the sub-batch outputs are concatenated outside the timed region
+        gt = torch.from_numpy(synth.ID2TRAINID).to(dev)[wl.batch['seg'][:, T - 1].long()].long()
+        acc = pfpq.pq_accumulate(out['seg'].long(), gt, 11)
+        allacc = pfdist.gather_accumulators(acc)
+        if int(allacc.shape[0]) != args.gpus:
+            raise SystemExit('bench.py: the PQ all-gather returned %d rank(s), --gpus %d' % (int(allacc.shape[0]), args.gpus))
+        pq_gather = {'pq_vs_last_input_labels': pfpq.pq_from_acc(allacc.sum(0))['pq'], 'ranks_gathered': int(allacc.shape[0])}
 
     # ---- per-kernel timing pass (eager, hipEvents on the launch stream) -> roofline of the dominant kernel + whole step
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # one sub-batch alone on the launch stream: kernels of concurrent streams share the chip, which would inflate
         # the per-launch durations the roofline fraction is computed from
         recs = profile_records(lambda: wl.models[0].predict(wl.subs[0], None), args.profile_steps)
@@ -844,7 +892,7 @@ def main():
                     r['flops'] / max(r['ms'], 1e-9) / 1e9, r['bytes'] / max(r['ms'], 1e-9) / 1e6), file=sys.stderr)
 
     cpu = parity = by_batch = by_batch_pipelined = fp32_only = fresh_cameras = train_step = other_resolution = None
-    single = rank == 0 and world == 1
+    single = rank == 0 and world == 1 and args.full
     ref = None
     n_done = 0
     if single and not args.no_cpu_baseline:
@@ -998,7 +1046,7 @@ def main():
                 'devices': [r['device'] for r in per_rank],
                 'roofline': roofline, 'cpu_baseline': cpu, 'parity': parity, 'by_batch': by_batch, 'by_batch_pipelined': by_batch_pipelined,
                 'fresh_cameras': fresh_cameras, 'other_resolution': other_resolution, 'fp32_only': fp32_only, 'train_step': train_step,
-                'pq_gather_check': {'pq_vs_last_input_labels': pq_synth, 'ranks_gathered': int(allacc.shape[0])}}
+                'pq_gather_check': pq_gather, 'full': bool(args.full)}
         print(json.dumps(line))
     if pfdist.is_dist():
         torch.distributed.barrier()

@@ -107,6 +107,42 @@ def test_bench_refuses_more_ranks_than_gpus():
     assert 'GPU(s)' in r.stderr
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """A plain run measures the headline only; the roofline pass, the PQ gather check, the CPU baseline, parity and the legs
+    need --full (tests/test_gpu_pipeline.py runs both forms on the GPU)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(['--steps', '7', '--warmup', '2'])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(['--full', '--no-legs', '--dump-outputs', 'd'])
+    assert a.full is True and a.no_legs is True and a.dump_outputs == 'd'
+
+
+def test_bench_dump_outputs_fixed_sample_under_64_mb(tmp_path):
+    """--dump-outputs: small arrays whole and exact, large ones as the same seeded sample of their elements on every call,
+    float32 / float64 only, at most 64 MB in all."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(5)
+    out = {'seg': torch.randint(0, 11, (2, 2000, 2600), generator=g, dtype=torch.uint8),
+           'warped_depth': torch.rand(1, 3, 1800, 1700, generator=g),
+           'ids': torch.arange(12, dtype=torch.int64).view(3, 4) + (1 << 40)}
+    for d in ('a', 'b'):
+        bench.dump_outputs(out, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['ids.npy', 'seg.npy', 'warped_depth.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64e6
+    a = {f[:-4]: np.load(tmp_path / 'a' / f) for f in files}
+    b = {f[:-4]: np.load(tmp_path / 'b' / f) for f in files}
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert a['ids'].dtype == np.float64 and np.array_equal(a['ids'], out['ids'].numpy().astype(np.float64))
+    assert a['seg'].dtype == np.float32 and a['warped_depth'].dtype == np.float32
+    assert 0 < a['seg'].size < out['seg'].numel() and 0 < a['warped_depth'].size < out['warped_depth'].numel()
+    assert np.isin(a['warped_depth'], out['warped_depth'].numpy()).all()
+    assert set(np.unique(a['seg'])) <= set(range(11))
+
+
 def test_export_driver_two_ranks_shard_then_barrier_then_fill(tmp_path):
     """`export_bg.py --synthetic 5 --dry_run` under two gloo ranks (torch.distributed.run, as scripts/bg/run_export_bg_val.sh would
     be started on a node): the samples are sharded round-robin, every rank writes its own frames, ALL ranks take the barrier

@@ -87,7 +87,7 @@ def test_bench_two_ranks_on_one_gpu_prints_the_multi_rank_line():
         e.pop(k, None)
     e['PF_BENCH_SHARE_GPU'] = '1'
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '16',
-                        '--profile-steps', '1'], capture_output=True, text=True, timeout=900, env=e)
+                        '--profile-steps', '1', '--full'], capture_output=True, text=True, timeout=900, env=e)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -97,3 +97,49 @@ def test_bench_two_ranks_on_one_gpu_prints_the_multi_rank_line():
     assert 'gloo' in d['config']['backend'] and d['config']['world'] == 2
     assert d['cpu_baseline'] is None and d['by_batch'] is None          # rank 0 at N = 1 only
     assert d['range_overflow'] is False
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain `bench.py` run is the headline alone (no roofline pass, gather check, baseline, parity or legs: those need --full)
+    and --dump-outputs writes what its timed graph computed: the sampled elements equal those of an eager predict of the same
+    synthetic batch through a fresh model (same batch size, so the same per-layer kernels)."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    sys.path.insert(0, ROOT)
+    import bench
+    e = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
+        e.pop(k, None)
+    dump = str(tmp_path / 'dump')
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--batch', '4',
+                        '--streams', '1', '--replays', '1', '--dump-outputs', dump], capture_output=True, text=True, timeout=600, env=e)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['ms_per_step'] > 0 and d['value'] > 0 and d['full'] is False
+    assert abs(d['value'] - 4 * 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+    for k in ('roofline', 'cpu_baseline', 'parity', 'by_batch', 'by_batch_pipelined', 'fresh_cameras', 'other_resolution',
+              'fp32_only', 'train_step', 'pq_gather_check'):
+        assert d[k] is None, k
+    assert d['range_overflow'] is False
+    files = sorted(os.listdir(dump))
+    assert files == ['seg.npy', 'warped_depth.npy', 'warped_seg.npy']
+    assert sum(os.path.getsize(os.path.join(dump, f)) for f in files) <= 64e6
+    got = {f[:-4]: np.load(os.path.join(dump, f)) for f in files}
+
+    m = bench.build_model(bench.model_params())
+    m.load_state_dict(bench.calibrated_state_dict())
+    m.eval()
+    res = m.predict(bench.make_batch(4, seed0=0, device='cuda'), None)
+    torch.cuda.synchronize()
+    ref = {}
+    for k in got:
+        t = res[k]
+        cap = bench.DUMP_BYTES // len(got) // (8 if t.dtype in (torch.float64, torch.int32, torch.int64) else 4)
+        assert t.numel() > cap, k          # every array of this size is sampled
+        idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(bench.DUMP_SEED)).sort().values
+        ref[k] = t.reshape(-1)[idx.cuda()].double().cpu().numpy()
+    assert np.array_equal(got['warped_seg'], ref['warped_seg']) and np.array_equal(got['warped_depth'], ref['warped_depth'])
+    assert (got['seg'] == ref['seg']).mean() >= 0.9999

@@ -10,7 +10,7 @@ for b in 32 4 1; do
 done
 for i in $(seq 1 $RUNS); do
   for o in 0 2; do
-    PF_OPTS=fuse_pairs=$o python bench.py --steps 20 --warmup 5 --no-legs --no-cpu-baseline --verbose --profile-steps 2 2>/dev/null | python -c "
+    PF_OPTS=fuse_pairs=$o python bench.py --full --steps 20 --warmup 5 --no-legs --no-cpu-baseline --verbose --profile-steps 2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('headline fuse_pairs=$o', round(d['value'],1), 'fps  convs', round(d['roofline']['step']['stages']['convs']['ms'],3), 'kernel sum', round(d['roofline']['kernel_ms_per_step'],3), 'overflow', d.get('range_overflow'))"
   done

@@ -2,8 +2,8 @@
 """Timeline of the replayed hipGraph from a rocprofv3 kernel trace (csv): how much of a step the chip is busy, how much of
 that with two kernels at once, where the idle gaps are and which kernels stretch when they share the chip.
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tl -o t -- python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-legs
-    python tools/graph_timeline.py gpurun_out/tl/*/t_kernel_trace.csv [steps_to_analyse [sub_batches_per_step [skip_last_sub_batches]]]
+    rocprofv3 --kernel-trace --output-format csv -d <out>/tl -o t -- python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-legs
+    python tools/graph_timeline.py <out>/tl/*/t_kernel_trace.csv [steps_to_analyse [sub_batches_per_step [skip_last_sub_batches]]]
 The trace ends with the eager per-kernel timing pass of bench.py (--profile-steps sub-batch forwards): skip those.
 """
 import csv

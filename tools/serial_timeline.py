@@ -4,7 +4,7 @@ gap between the previous kernel's end and its start, averaged over the replayed 
 dependent chain of ~85 launches, so step time = sum(durations) + sum(gaps).
 
     rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tlb1 -o t -- \
-        python bench.py --batch 1 --streams 1 --steps 40 --warmup 5 --no-cpu-baseline --no-legs --profile-steps 1
+        python bench.py --full --batch 1 --streams 1 --steps 40 --warmup 5 --no-cpu-baseline --no-legs --profile-steps 1
     python tools/serial_timeline.py gpurun_out/tlb1/*/t_kernel_trace.csv [steps]
 """
 import csv

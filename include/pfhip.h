@@ -228,6 +228,34 @@ int pf_seg_loss_workspace(int B, int out_h, int out_w, size_t *bytes);
 int pf_seg_loss(const float *logits, int B, int C, int Hin, int Win, const void *labels, int labels_i64, int out_h,
                 int out_w, int ignore_index, double *out3, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * fg forecaster network - replaces FGModel.forward (models/fg/fg_model.py:216-339) of the shipped fg config
+ * (pretrained_models/fg/config.yaml: rnn_type gru, 2 ConvLSTM layers, 2 trajectory output layers, depth + odometry
+ * inputs); its pieces: ConvLSTMCell (convlstm.py:44-70), nn.GRU, MaskRCNNConvUpsampleHead.forward
+ * (mask_rcnn_conv_upsample_head.py:60-65), _compute_traj_inst_feats (:206-214), _normalize_traj (:179-188) and
+ * expand_traj_mask (model_utils.py:11-27).  csrc/fg_net.hip.
+ *   flags      must be 0 (other values: PF_EUNSUPPORTED; reserved for the configuration switches)
+ *   pf_fg_weights_size: raw = the 52 state_dict tensors of the reference, flattened and concatenated in its state_dict
+ *              order (fp32); packed = the device buffer pf_fg_pack fills (raw copy + ConvLSTM / mask head weights re-tiled,
+ *              the i, f, o, g rows of 16 hidden channels side by side).  Both in floats.
+ *   pf_fg_pack(raw, packed): device buffers; enqueued on stream.  Re-run after the parameters change.
+ *   pf_fg_forward: N instances, T_in input steps, T_out = num_output_steps, odom_T >= T_in + T_out steps of odometry:
+ *     trajs [N,T_in,8] f32   traj_mask, vel_mask [N,T_in] f32 (0/1)   feats [N,T_in,256,14,14] f32
+ *     output_inds [N] i64 (clamped into [0,T_out))   odom [N,odom_T,5] f32   depths [N,T_in,2] f32
+ *     depth_mask [N,T_in] f32 (0/1)   classes [N] i64 (clamped into [0,8))
+ *   -> traj_norm, traj_unnorm [N,1+T_out,10]   mask_feats [N,1+T_out,256,14,14]   output_feats [N,256,14,14]
+ *      masks [N,28,28] (the logits of each instance's class row only, :335-336)
+ *   N = 0 enqueues nothing.  Dimensions are checked before any device work.  Workspace: pf_fg_workspace.
+ */
+int pf_fg_weights_size(int flags, size_t *raw_floats, size_t *packed_floats);
+int pf_fg_pack(const float *raw, float *packed, int flags, void *stream);
+int pf_fg_workspace(int N, int T_in, int T_out, int flags, size_t *bytes);
+int pf_fg_forward(const float *packed, int flags, int N, int T_in, int T_out, int odom_T, const float *trajs,
+                  const float *traj_mask, const float *vel_mask, const float *feats, const int64_t *output_inds,
+                  const float *odom, const float *depths, const float *depth_mask, const int64_t *classes,
+                  float *traj_norm, float *traj_unnorm, float *mask_feats, float *output_feats, float *masks,
+                  void *ws, size_t ws_bytes, void *stream);
+
 /* Process-wide execution options (not thread-safe; set before launching work):
  *   "fuse_pool"     (default 1) a 1x1 conv followed by AvgPool2d(2,2) (hardnet.py:296) pools in the conv epilogue;
  *   "fuse_upsample" (default 1) TransitionUp + 1x1 conv over cat([up(x), skip]) (hardnet.py:248-258,365-368) is

@@ -58,6 +58,11 @@ SIGNATURES = {
                                   _c.POINTER(_i)]),
     'pf_sgd_workspace': (_i, [_c.POINTER(_sz)]),
     'pf_sgd_step': (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _sz, _vp]),
+    'pf_fg_weights_size': (_i, [_i, _c.POINTER(_sz), _c.POINTER(_sz)]),
+    'pf_fg_pack': (_i, [_vp, _vp, _i, _vp]),
+    'pf_fg_workspace': (_i, [_i, _i, _i, _i, _c.POINTER(_sz)]),
+    'pf_fg_forward': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _vp, _sz, _vp]),
     'pf_set_option': (_i, [_c.c_char_p, _i]),
     'pf_hardnet_plan_set_option': (_i, [_vp, _c.c_char_p, _i]),
     'pf_debug_force_conv': (_i, [_i, _i, _i, _i]),

@@ -3,7 +3,7 @@
 Call contract of the reference's ``panoptic_forecasting.models.build_model`` (``models/__init__.py:16-41``), so its
 experiment scripts run with one import changed: the task comes from ``params['task']``; the model is
 moved to the GPU unless ``params['no_gpu']``; ``load_best_model`` restores ``<working_dir>/best_model``, otherwise
-``load_model`` names a checkpoint.  Tasks outside the hot path (``fg``, ``odom``) are refused with a pointer to the
+``load_model`` names a checkpoint.  The task outside the hot path (``odom``) is refused with a pointer to the
 reference — this package has no fallback implementations.
 """
 import importlib
@@ -16,8 +16,9 @@ _TASKS = {
     'bg': ('bg_model', 'BGModel'),
     'pc_transform': ('pc_transform_model', 'PCTransformModel'),
     'bg_forecast': ('bg_forecast_model', 'BGForecastModel'),       # the two stages fused on the device (new)
+    'fg': ('fg_model', 'FGModel'),                                  # shipped fg config only (fg_model.check_config)
 }
-_OUT_OF_SCOPE = ('fg', 'odom')
+_OUT_OF_SCOPE = ('odom',)
 
 
 def _checkpoint_path(params):

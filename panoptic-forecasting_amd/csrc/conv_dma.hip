@@ -448,20 +448,15 @@ static int launch_dma_epi(const ConvArgs &a0, int B, hipStream_t s) {
 
 template <int KS, int STRIDE, int WM, int WK, int NT>
 static int launch_dma_cfg(const ConvArgs &a, int B, hipStream_t s) {
-    if (a.pool || a.res || a.no_bias) {
-        if (KS == 1 && STRIDE == 1) return launch_dma_epi<KS, STRIDE, WM, WK, NT, (KS == 1 && STRIDE == 1) ? 1 : 0>(a, B, s);
-        return fail(PF_EUNSUPPORTED, "conv_dma: fused epilogue stages are built for 1x1 convs only");
-    }
+    // (conv_dma_supported has let through only what is built: fused stages on 1x1 convs, the remainder on the shapes below)
+    if (a.pool || a.res || a.no_bias) return launch_dma_epi<KS, STRIDE, WM, WK, NT, (KS == 1 && STRIDE == 1) ? 1 : 0>(a, B, s);
     if (a.rem > 0) {   // the last a.rem couts on the vector ALU (a.ntiles = tiles that go through the matrix pipe)
-        if (KS == 3 && STRIDE == 1 && WM == 4 && WK == 1 && NT <= 3) {
-            constexpr bool ok = KS == 3 && STRIDE == 1 && WM == 4 && WK == 1 && NT <= 3;
-            if (a.rem <= 2) return launch_dma_epi<KS, STRIDE, WM, WK, NT, 0, ok ? 2 : 0>(a, B, s);
-            if (a.rem <= 4) return launch_dma_epi<KS, STRIDE, WM, WK, NT, 0, ok ? 4 : 0>(a, B, s);
-            if (a.rem <= 8) return launch_dma_epi<KS, STRIDE, WM, WK, NT, 0, ok ? 8 : 0>(a, B, s);
-            if (a.rem <= 12) return launch_dma_epi<KS, STRIDE, WM, WK, NT, 0, ok ? 12 : 0>(a, B, s);
-            if (a.rem <= 16) return launch_dma_epi<KS, STRIDE, WM, WK, NT, 0, ok ? 16 : 0>(a, B, s);
-        }
-        return fail(PF_EUNSUPPORTED, "conv_dma: the vector-ALU cout path is built for 3x3/s1, WM=4, NT<=3, <=16 channels");
+        constexpr bool ok = KS == 3 && STRIDE == 1 && WM == 4 && WK == 1 && NT <= 3;
+        if (a.rem <= 2) return launch_dma_epi<KS, STRIDE, WM, WK, NT, 0, ok ? 2 : 0>(a, B, s);
+        if (a.rem <= 4) return launch_dma_epi<KS, STRIDE, WM, WK, NT, 0, ok ? 4 : 0>(a, B, s);
+        if (a.rem <= 8) return launch_dma_epi<KS, STRIDE, WM, WK, NT, 0, ok ? 8 : 0>(a, B, s);
+        if (a.rem <= 12) return launch_dma_epi<KS, STRIDE, WM, WK, NT, 0, ok ? 12 : 0>(a, B, s);
+        return launch_dma_epi<KS, STRIDE, WM, WK, NT, 0, ok ? 16 : 0>(a, B, s);
     }
     return launch_dma_epi<KS, STRIDE, WM, WK, NT, 0>(a, B, s);
 }
@@ -510,17 +505,30 @@ static void pick_shape(const ConvArgs &a, int ks, int stride, int B, int &wm, in
     }
 }
 
-int launch_conv_dma(const ConvArgs &a, int ks, int stride, int B, hipStream_t s, int force_wm, int force_nt, int model_B) {
+// the shape: the cost model's (a fully forced one does not look at it), or the forced one; then what the dispatch below and
+// launch_dma_cfg build
+bool conv_dma_supported(const ConvArgs &a, int ks, int stride, int B, int force_wm, int force_nt, int model_B, int *wm_out, int *nt_out) {
     int wm = 4, wk = 1, nt = 1;
-    pick_shape(a, ks, stride, model_B > 0 ? model_B : B, wm, wk, nt);   // the K split (WK) changes the summation order
+    if (force_wm <= 0 || force_nt <= 0) pick_shape(a, ks, stride, model_B > 0 ? model_B : B, wm, wk, nt);   // the K split (WK) changes the summation order
     if (force_wm > 0) {
         const int model_nt = wm == force_wm ? nt : 2;
         wm = force_wm;
-        wk = 4 / wm;
         nt = force_nt > 0 ? force_nt : model_nt;
         nt = nt < a.ntiles ? nt : a.ntiles;
         if (wm == 1 && nt > 2) nt = 2;
     }
+    *wm_out = wm, *nt_out = nt;
+    if (!((ks == 3 && (stride == 1 || stride == 2)) || (ks == 1 && stride == 1)) || nt < 1 || nt > (wm == 1 ? 2 : 4) || (wm != 1 && wm != 2 && wm != 4))
+        return false;
+    if (a.pool || a.res || a.no_bias) return ks == 1 && stride == 1;
+    return a.rem == 0 || (ks == 3 && stride == 1 && wm == 4 && nt <= 3 && a.rem <= 16);
+}
+
+int launch_conv_dma(const ConvArgs &a, int ks, int stride, int B, hipStream_t s, int force_wm, int force_nt, int model_B) {
+    int wm, nt;
+    if (!conv_dma_supported(a, ks, stride, B, force_wm, force_nt, model_B, &wm, &nt))
+        return fail(PF_EUNSUPPORTED, "conv_dma: no kernel for ks=%d stride=%d wm=%d nt=%d rem=%d%s", ks, stride, wm, nt, a.rem,
+                    (a.pool || a.res || a.no_bias) ? " with fused epilogue stages" : "");
 #define PF_CASE(KS_, ST_, WM_, WK_, NT_) \
     if (ks == KS_ && stride == ST_ && wm == WM_ && nt == NT_) return launch_dma_cfg<KS_, ST_, WM_, WK_, NT_>(a, B, s);
     PF_CASE(3, 1, 4, 1, 1) PF_CASE(3, 1, 4, 1, 2) PF_CASE(3, 1, 4, 1, 3) PF_CASE(3, 1, 4, 1, 4)

@@ -238,6 +238,8 @@ void pack_conv_weights_tiled(const float *w_oihw, int cin, int cout, int ks, int
 // force_wm/force_nt > 0 override the cost model (tuning runs); model_B > 0: the cost model sees this batch size
 // instead of B (batch-invariant shape choice, plan option "table_batch")
 int launch_conv_dma(const ConvArgs &a, int ks, int stride, int B, hipStream_t stream, int force_wm = 0, int force_nt = 0, int model_B = 0);
+// the shape (*wm, *nt) launch_conv_dma picks for these arguments; whether it has a kernel for it (residual window: at launch only)
+bool conv_dma_supported(const ConvArgs &a, int ks, int stride, int B, int force_wm, int force_nt, int model_B, int *wm, int *nt);
 
 // Wave-autonomous path (conv_wave.hip; stride 1, Win % 4 == 0): a.wpk must point at pack_conv_weights_wave()
 // output and a.nchunks = ceil(Cin / wave_kc(ks)).  Tile = mh rows x 16 pixels, nt cout tiles, wk-way K split.
@@ -248,6 +250,14 @@ int wave_chunks(const int *src_ch, int n_src, int ks);
 void pack_conv_weights_wave(const float *w_oihw, int cin, int cout, int ks, const int *src_ch, int n_src, float *out);
 size_t wave_packed_floats(const int *src_ch, int n_src, int cout, int ks);
 int launch_conv_wave(const ConvArgs &a, int ks, int mh, int nt, int wk, int B, hipStream_t stream);
+bool conv_wave_supported(const ConvArgs &a, int ks, int mh, int nt, int wk);   // launch_conv_wave has a kernel for this launch
+// LDS bytes of a conv_wave workgroup (WaveCfg in conv_wave.hip asserts the match)
+constexpr size_t wave_lds_bytes(int ks, int mh, int nt, int wk) {
+    const int kc = wave_kc_ct(ks), ih = mh + ks - 1, iw = 16 + (ks == 3 ? 8 : 0);
+    const int raw = ih * iw, plane = (raw + 15) / 32 * 32 + 16, nit = (kc * (plane / 4) + 63) / 64;
+    const size_t ring = (size_t)wk * 2 * nit * 256, red = (size_t)wk * mh * nt * 256;
+    return 4 * (ring > red ? ring : red);
+}
 
 // split path (conv_split.hip; 3x3/s1, Wout % 4 == 0, no fused epilogue; two fp16 terms per operand, see split_terms2
 // above): a.wpk must point at pack_conv_weights_split() output, chunks of 8 channels; the packers take the weights
@@ -256,11 +266,13 @@ int split_chunks(const int *src_ch, int n_src);
 size_t split_packed_floats(const int *src_ch, int n_src, int cout);
 void pack_conv_weights_split(const float *w_oihw, int cin, int cout, const int *src_ch, int n_src, float *out);
 int launch_conv_split(const ConvArgs &a, int nt, int wide, int B, hipStream_t stream);
+bool conv_split_supported(const ConvArgs &a);   // launch_conv_split has a kernel for this launch
 // 1x1/s1 on the same scheme (chunks of 32 channels; pack_conv_weights_split1()); supports the fused epilogue stages
 int split1_chunks(const int *src_ch, int n_src);
 size_t split1_packed_floats(const int *src_ch, int n_src, int cout);
 void pack_conv_weights_split1(const float *w_oihw, int cin, int cout, const int *src_ch, int n_src, float *out);
 int launch_conv_split1(const ConvArgs &a, int nt, int B, hipStream_t stream);
+bool conv_split1_supported(const ConvArgs &a, int nt);   // ... and launch_conv_split1 (a residual window must fit LDS)
 
 // S4 path (conv_s4.hip; stride 1, W % 4 == 0): every source in the packed-pair layout, tiles arrive by LDS-DMA, no split
 // phase.  K order = the group entries of the ranges in order, two entries (8 channels) per 3x3 round, eight (32 channels)

@@ -25,13 +25,6 @@ const Tuned kTunedS4[] = {
 #include "conv_s4_tuned.inc"
 };
 
-// LDS bytes of a conv_wave workgroup (mirrors WaveCfg in conv_wave.hip)
-size_t wave_lds_bytes(int ks, int mh, int nt, int wk) {
-    const int kc = wave_kc(ks), ih = mh + ks - 1, iw = 16 + (ks == 3 ? 8 : 0);
-    const int raw = ih * iw, plane = (raw + 15) / 32 * 32 + 16, nit = (kc * (plane / 4) + 63) / 64;
-    const size_t ring = (size_t)wk * 2 * nit * 256, red = (size_t)wk * mh * nt * 256;
-    return 4 * (ring > red ? ring : red);
-}
 }  // namespace
 
 // A layer of the architecture at an image size the tables were not measured at.  Both tables are keyed on the exact shapes of the
@@ -126,8 +119,8 @@ ConvChoice choose_conv(int ks, int stride, int cin, int cout, int hout, int wout
             return t.c;
     // Untuned shape.  Large stride-1 3x3 layers go to the split kernel: on every measured shape with >= 64x128
     // pixels x 4 images it beat the fp32-MFMA kernels by 1.3-2.2x (profiles/README.md); cout tiles per workgroup by
-    // channel count, 8x64 tiles where the image is wide enough to still fill the chip.  (The executor falls back to
-    // conv_dma when the layer needs a fused epilogue or split_f16 is off.)
+    // channel count, 8x64 tiles where the image is wide enough to still fill the chip.  (The schedule gives the layer to
+    // conv_dma when it needs a fused epilogue or split_f16 is off, hardnet_plan.hip.)
     if (ks == 3 && (need == 0) && (wout & 3) == 0 && (long)B * hout * wout >= 32768) {
         const int nt = cout <= 16 ? 1 : (cout <= 32 ? 2 : 3);
         const long tiles_wide = (long)B * ((hout + 7) / 8) * ((wout + 63) / 64) * (((cout + 15) / 16 + nt - 1) / nt);

@@ -277,9 +277,12 @@ static int launch_split_cfg(const ConvArgs &a0, int B, hipStream_t s) {
 
 // a.wpk = pack_conv_weights_split() output; chunks of 8 channels (a.src_chunk0 / chunk_begin / chunk_end set for 8).
 // nt = cout tiles per workgroup (1..3), wide = 8x64-pixel workgroup tiles instead of 8x32.
+bool conv_split_supported(const ConvArgs &a) {
+    return !a.pool && !a.res && !a.no_bias && (a.Wout & 3) == 0 && a.Hin == a.Hout && a.Win == a.Wout;
+}
+
 int launch_conv_split(const ConvArgs &a, int nt, int wide, int B, hipStream_t s) {
-    if (a.pool || a.res || a.no_bias) return fail(PF_EUNSUPPORTED, "conv_split: no fused epilogue stages");
-    if ((a.Wout & 3) != 0 || a.Hin != a.Hout || a.Win != a.Wout) return fail(PF_EUNSUPPORTED, "conv_split: 3x3/s1, width % 4 == 0 only");
+    if (!conv_split_supported(a)) return fail(PF_EUNSUPPORTED, "conv_split: 3x3/s1, width %% 4 == 0, no fused epilogue stages only");
     nt = nt < 1 ? 1 : (nt > a.ntiles ? a.ntiles : nt);
     if (wide) {
         if (nt == 1) return launch_split_cfg<1, 64>(a, B, s);
@@ -510,6 +513,13 @@ __global__ __launch_bounds__(256) void conv_split1_kernel(ConvArgs a) {
 #endif
 }
 
+bool conv_split1_supported(const ConvArgs &a, int nt) {
+    nt = nt < 1 ? 1 : (nt > a.ntiles ? a.ntiles : nt);
+    nt = nt > 4 ? 4 : nt;
+    return (a.Wout & 3) == 0 && a.Hin == a.Hout && a.Win == a.Wout &&
+           (!a.res || (size_t)nt * 16 * res_chan_stride(res_extent(8, a.res_sh), res_extent(32, a.res_sw)) * sizeof(float) <= 64 * 1024);
+}
+
 template <int NT, int EPI>
 static int launch_split1_cfg(const ConvArgs &a0, int B, hipStream_t s) {
     using C = Split1Cfg<NT>;
@@ -519,8 +529,7 @@ static int launch_split1_cfg(const ConvArgs &a0, int B, hipStream_t s) {
     size_t lds = C::MAIN;
     a.res_lds_off = -1;
     if (a.res) {
-        const size_t need = (size_t)NT * 16 * res_chan_stride(res_extent(C::TH, a.res_sh), res_extent(C::TW, a.res_sw)) * sizeof(float);
-        if (need > 64 * 1024) return fail(PF_EUNSUPPORTED, "conv_split1: residual window of %zu B does not fit LDS", need);
+        const size_t need = (size_t)NT * 16 * res_chan_stride(res_extent(C::TH, a.res_sh), res_extent(C::TW, a.res_sw)) * sizeof(float);   // <= 64 KiB
         a.res_lds_off = 0;
         if (need > lds) lds = need;
     }
@@ -544,7 +553,7 @@ static int launch_split1_cfg(const ConvArgs &a0, int B, hipStream_t s) {
 
 // 1x1/s1: a.wpk = pack_conv_weights_split1() output; chunks of 32 channels.  nt = cout tiles per workgroup (1..4).
 int launch_conv_split1(const ConvArgs &a, int nt, int B, hipStream_t s) {
-    if ((a.Wout & 3) != 0 || a.Hin != a.Hout || a.Win != a.Wout) return fail(PF_EUNSUPPORTED, "conv_split1: 1x1/s1, width % 4 == 0 only");
+    if (!conv_split1_supported(a, nt)) return fail(PF_EUNSUPPORTED, "conv_split1: 1x1/s1, width %% 4 == 0, a residual window that fits LDS only");
     nt = nt < 1 ? 1 : (nt > a.ntiles ? a.ntiles : nt);
     nt = nt > 4 ? 4 : nt;
     const bool fused = a.pool || a.res || a.no_bias;

@@ -309,15 +309,14 @@ __global__ __launch_bounds__(64 * WK) void conv_wave_kernel(ConvArgs a) {
 template <int KS, int MH, int NT, int WK, int EPI>
 static int launch_wave_epi(const ConvArgs &a0, int B, hipStream_t s) {
     using C = WaveCfg<KS, MH, NT, WK>;
+    static_assert(wave_lds_bytes(KS, MH, NT, WK) == C::LDS_FLOATS * sizeof(float), "wave_lds_bytes (conv_mfma.h) mirrors WaveCfg");
     ConvArgs a = a0;
     a.tilesX = (a.Wout + 15) / 16;
     a.tilesY = (a.Hout + MH - 1) / MH;
-    size_t lds = (size_t)C::LDS_FLOATS * sizeof(float);
-    if (lds > 64 * 1024) return fail(PF_EUNSUPPORTED, "conv_wave<%d,%d,%d,%d>: %zu B of LDS", KS, MH, NT, WK, lds);
+    size_t lds = (size_t)C::LDS_FLOATS * sizeof(float);   // (<= 64 KiB, the residual window included: conv_wave_supported)
     a.res_lds_off = -1;
     if (a.res) {   // staged residual window lives behind the K-split partial sums
         const size_t need = (size_t)C::RED + (size_t)NT * 16 * res_chan_stride(res_extent(MH, a.res_sh), res_extent(16, a.res_sw));
-        if (need * sizeof(float) > 64 * 1024) return fail(PF_EUNSUPPORTED, "residual window of %zu B does not fit LDS", need * sizeof(float));
         a.res_lds_off = C::RED;
         if (need * sizeof(float) > lds) lds = need * sizeof(float);
     }
@@ -343,14 +342,20 @@ static int launch_wave_epi(const ConvArgs &a0, int B, hipStream_t s) {
 
 template <int KS, int MH, int NT, int WK>
 static int launch_wave_cfg(const ConvArgs &a, int B, hipStream_t s) {
-    if (a.pool || a.res || a.no_bias) {
-        if (KS == 1) return launch_wave_epi<KS, MH, NT, WK, KS == 1 ? 1 : 0>(a, B, s);
-        return fail(PF_EUNSUPPORTED, "conv_wave: fused epilogue stages are built for 1x1 convs only");
-    }
+    if (a.pool || a.res || a.no_bias) return launch_wave_epi<KS, MH, NT, WK, KS == 1 ? 1 : 0>(a, B, s);   // (1x1 only: conv_wave_supported)
     return launch_wave_epi<KS, MH, NT, WK, 0>(a, B, s);
 }
 
+bool conv_wave_supported(const ConvArgs &a, int ks, int mh, int nt, int wk) {
+    const bool built = (ks == 1 || ks == 3) && (mh == 1 || mh == 2 || mh == 4) && (nt == 1 || nt == 2) && (wk == 2 || wk == 4 || wk == 8 || wk == 16);
+    if (!built || wave_lds_bytes(ks, mh, nt, wk) > 64 * 1024) return false;
+    if (!a.pool && !a.res && !a.no_bias) return true;
+    const size_t res = (size_t)nt * 16 * res_chan_stride(res_extent(mh, a.res_sh), res_extent(16, a.res_sw));
+    return ks == 1 && (!a.res || ((size_t)wk * mh * nt * 256 + res) * sizeof(float) <= 64 * 1024);
+}
+
 int launch_conv_wave(const ConvArgs &a, int ks, int mh, int nt, int wk, int B, hipStream_t s) {
+    if (!conv_wave_supported(a, ks, mh, nt, wk)) return fail(PF_EUNSUPPORTED, "conv_wave: no kernel for ks=%d mh=%d nt=%d wk=%d%s", ks, mh, nt, wk, (a.pool || a.res || a.no_bias) ? " with fused epilogue stages" : "");
 #define PF_CASE(KS_, MH_, NT_, WK_) \
     if (ks == KS_ && mh == MH_ && nt == NT_ && wk == WK_) return launch_wave_cfg<KS_, MH_, NT_, WK_>(a, B, s);
 #define PF_CASES_WK(KS_, MH_, NT_) PF_CASE(KS_, MH_, NT_, 2) PF_CASE(KS_, MH_, NT_, 4) PF_CASE(KS_, MH_, NT_, 8) PF_CASE(KS_, MH_, NT_, 16)
@@ -358,7 +363,7 @@ int launch_conv_wave(const ConvArgs &a, int ks, int mh, int nt, int wk, int B, h
     PF_CASES_WK(1, 1, 1) PF_CASES_WK(1, 1, 2) PF_CASES_WK(1, 2, 1) PF_CASES_WK(1, 2, 2) PF_CASES_WK(1, 4, 1) PF_CASES_WK(1, 4, 2)
 #undef PF_CASES_WK
 #undef PF_CASE
-    return fail(PF_EUNSUPPORTED, "conv_wave: no kernel for ks=%d mh=%d nt=%d wk=%d", ks, mh, nt, wk);
+    return PF_EUNSUPPORTED;   // (unreachable: conv_wave_supported)
 }
 
 int wave_chunks(const int *src_ch, int n_src, int ks) {

@@ -1,4 +1,5 @@
-// Plan = parsed op table + device-resident, MFMA-tiled weights; forward = walk the table and enqueue.
+// Plan = parsed op table + device-resident, MFMA-tiled weights; forward = build_schedule (the table -> a flat list of launches,
+// every fusion and kernel choice made on the host) + an enqueue loop over it.
 //
 // Replaces the module walk of reference hardnet.py:353-387 (hardnet.forward) and the glue of
 // bg_model.py:61-71,91-102.  The op table comes from the blob (packing.py / hardnet_arch.py); nothing
@@ -214,23 +215,51 @@ int layout(const pf_plan *p, int B, const std::vector<Dims> &d, std::vector<size
     return PF_OK;
 }
 
-int run_net(const pf_plan *p, const StemArgs *stem, const float *dense_x, int B, int H, int W, int out_h, int out_w,
-            void *out_seg, int out_seg_is_i64, float *out_logits, float *out_orig, void *ws, size_t ws_bytes,
-            hipStream_t s) {
+// ---- A forward = build_schedule (host code only: every launch with all its arguments, each naming exactly one kernel) + the
+//      enqueue loop of run_net.  S_CONV: inside build_schedule only, a convolution whose kernel is picked once the formats are known
+enum StepKind : uint8_t {
+    S_RANGE_CHECK, S_STEM, S_STEM_FRONT, S_PAIR, S_CONV, S_CONV_S4, S_CONV_GENERIC, S_CONV_SPLIT, S_CONV_SPLIT1, S_CONV_WAVE, S_CONV_DMA,
+    S_POOL, S_UPSAMPLE, S_HEAD };
+struct PlainArgs { const float *src; float *dst; int planes, hin, win, hout, wout; size_t n; unsigned *status, *slot; };   // pool, upsample, range check
+struct Step {
+    StepKind kind;
+    int op;          // first op of the table the step executes
+    char tag[96];    // pf_profile_* label of its launches (empty unless the plan tags ops)
+    // convolutions (and the front end's output) in the format decision: ranges [sb, se) read, destination, whether the kernel can
+    // read / write the S4 layout (can_write: whatever it reads; can_write_s4: only when it reads S4 itself)
+    int ci, need, sb, se;   // op whose weights it runs; need: bit 1 = even tile rows (pooling epilogue), bit 2 = fused stage
+    uint32_t src_t[kConvMaxSrc], dst_t;
+    bool can_read, can_write, can_write_s4;
+    ConvChoice ch;   // fp32-source kernel (table or pf_debug_force_conv); once picked, the launched kernel's shape
+    int nt, wide;    // conv_s4 shape if it reads S4
+    union {
+        ConvArgs c; PairArgs pair; PlainArgs x;
+        struct { StemArgs stem; FrontArgs front; char front_tag[96]; } sf;
+        struct { HeadArgs h; float *orig; size_t orig_bytes; } head;
+    } u;
+};
+inline bool is_conv_step(StepKind k) { return k >= S_CONV_S4 && k <= S_CONV_DMA; }
+
+int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x, int B, int H, int W, int out_h, int out_w,
+                   void *out_seg, int out_seg_is_i64, float *out_logits, float *out_orig, void *ws, size_t ws_bytes,
+                   std::vector<Step> &steps, std::vector<uint8_t> &fmt) {
+    // ---- 1. dims and workspace layout
     std::vector<Dims> d;
     int rc = propagate_dims(p, H, W, d);
     if (rc) return rc;
     std::vector<size_t> off;
-    size_t need = 0;
-    layout(p, B, d, off, need);
-    if (ws_bytes < need) return fail(PF_EWORKSPACE, "workspace %zu B < required %zu B", ws_bytes, need);
+    size_t ws_need = 0;
+    layout(p, B, d, off, ws_need);
+    if (ws_bytes < ws_need) return fail(PF_EWORKSPACE, "workspace %zu B < required %zu B", ws_bytes, ws_need);
     const uint32_t input = p->ops[0].src[0].tensor;
     auto tptr = [&](uint32_t t) -> float * {
         return t == input ? const_cast<float *>(dense_x) : reinterpret_cast<float *>((char *)ws + off[t]);
     };
 
-    const bool tag_ops = p->opt_tag_ops != 0 || g_opt_tag_ops != 0;   // option "profile_tag_ops" (per plan, or process-wide for tools that switch it on late): per-op labels in pf_profile_* records
+    // option "profile_tag_ops" (per plan, or process-wide for tools that switch it on late): per-op labels in pf_profile_* records
+    const bool tags = (p->opt_tag_ops != 0 || g_opt_tag_ops != 0) && prof_enabled();
     const bool fuse = p->opt_fuse_pool != 0;      // option "fuse_pool"
+    const int Bt = p->opt_table_batch > 0 ? p->opt_table_batch : B;   // the batch every kernel choice is made for (option "table_batch")
     // range guard of the two-term operand split (conv_mfma.h): producers of tensors a split kernel may read raise
     // PF_STATUS_RANGE in the live status word and report their max |v| to their op's slot; the forward ends with range_finalize
     // (PF_STATUS_RANGE_LOW, published status word, sticky word, everything live cleared for the next forward).  fp32-only plans
@@ -243,194 +272,109 @@ int run_net(const pf_plan *p, const StemArgs *stem, const float *dense_x, int B,
         return (status_all && p->feeds_conv[dst_t]) ? st_words + kSlot0 + op_i : nullptr;
     };
 
-    // ---- tensor formats.  The op loop below runs twice: a dry pass records every launch (which tensors it reads and
-    // writes, whether its kernel can read / write the S4 layout of conv_s4.hip), the formats are then decided - a tensor is
-    // S4 iff every launch that reads it reads all its inputs as S4 and every launch that writes it can write S4 - and
-    // the second pass enqueues.
-    struct ConvRec {
-        uint32_t src_t[kConvMaxSrc], dst_t;
-        int sb, se;            // ranges it accumulates
-        bool can_read, can_write;   // can_write: whatever it reads; can_write_s4: only when it reads S4 itself
-        bool can_write_s4;
-        int dst_limit;         // S4 stores: first buffer channel this launch must NOT write (conv_mfma.h)
-        int nt, wide;          // conv_s4 shape if it reads S4
-    };
+    // Tensor formats: a tensor is S4 iff every step that reads it reads all its inputs as S4 and every step that writes it can
+    // write S4.  cand = still possible; written = channels of each tensor some earlier step stores (half-group bookkeeping)
     const size_t nT = p->tensors.size();
-    std::vector<ConvRec> recs;
-    std::vector<uint8_t> fmt(nT, 0), cand(nT, 1);
+    fmt.assign(nT, 0);
+    std::vector<uint8_t> cand(nT, 1);
     std::vector<std::vector<uint8_t>> written(nT);
     for (size_t t = 0; t < nT; ++t) written[t].assign(p->tensors[t].channels + 8, 0);
     const bool s4_allowed = p->opt_packed_acts && p->opt_split && (g_conv_force.kind == 0 || g_conv_force.kind == 5);
-    bool dry = true;
-    size_t rec_i = 0;
-    struct ConvMeta {
-        uint32_t src_t[kConvMaxSrc], dst_t;
+    // a step stores channels [lo, hi) of tensor t: returns its S4 dst_limit (zero-fill the tail of the last group unless its owner
+    // wrote it already)
+    auto claim = [&](uint32_t t, int lo, int hi) -> int {
+        std::vector<uint8_t> &wr = written[t];
+        if ((lo & 3) == 2 && !wr[lo - 2]) cand[t] = 0;   // would expose an unwritten half group to readers of this range
+        const int limit = ((hi & 3) != 0 && !wr[hi]) ? (hi + 3) / 4 * 4 : hi;
+        for (int c = lo; c < hi; ++c) wr[c] = 1;
+        return limit;
+    };
+    // ops executed by kernels that only know fp32 NCHW pin their tensors to it
+    auto pin_fp32 = [&](const BlobOp &op) {
+        for (uint32_t j = 0; j < op.n_src; ++j) cand[op.src[j].tensor] = 0;
+        cand[op.dst] = 0;
     };
 
-    auto fill_conv_args = [&](const BlobOp &o, size_t i, const Dims &in, const Dims &out, ConvArgs &a, ConvMeta &mt) {
-        memset(&a, 0, sizeof(a));
+    steps.clear();
+    steps.reserve(2 * p->ops.size());   // at most two steps per op: no reallocation while a Step & is held
+    auto push = [&](StepKind kind, size_t i) -> Step & {
+        Step &st = steps.emplace_back();
+        memset(&st, 0, sizeof(st));
+        st.kind = kind; st.op = (int)i;
+        const BlobOp &o = p->ops[i];
+        const Dims out = o.kind == OP_HEAD ? d[o.src[0].tensor] : d[o.dst];
+        if (tags) snprintf(st.tag, sizeof(st.tag), "%02zu %s %u->%u %dx%d", i, p->tensors[o.dst].name, o.cin, o.cout, out.h, out.w);
+        return st;
+    };
+    // a step of op i running convolution ci
+    auto conv_step = [&](size_t i, size_t ci, const Dims &in, const Dims &out) -> Step & {
+        Step &st = push(S_CONV, i);
+        const BlobOp &o = p->ops[ci];
+        ConvArgs &a = st.u.c;
+        st.ci = (int)ci; st.dst_t = o.dst;
         a.n_src = (int)o.n_src;
         int c0 = 0;
         for (int j = 0; j < a.n_src; ++j) {
-            a.src[j] = tptr(o.src[j].tensor);
-            mt.src_t[j] = o.src[j].tensor;
+            a.src[j] = tptr((st.src_t[j] = o.src[j].tensor));
             a.src_ctotal[j] = (int)p->tensors[o.src[j].tensor].channels;
             a.src_choff[j] = (int)o.src[j].choff;
             a.src_cstart[j] = c0;
             c0 += (int)o.src[j].ch;
         }
         for (int j = a.n_src; j <= kConvMaxSrc; ++j) a.src_cstart[j] = c0;
-        a.bias = p->dev_weights + p->conv[i].bias_off;
+        a.bias = p->dev_weights + p->conv[ci].bias_off;
         a.dst = tptr(o.dst);
-        mt.dst_t = o.dst;
-        a.dst_ctotal = (int)p->tensors[o.dst].channels;
-        a.dst_choff = (int)o.dst_choff;
+        a.dst_ctotal = (int)p->tensors[o.dst].channels; a.dst_choff = (int)o.dst_choff;
         a.Cin = (int)o.cin; a.Cout = (int)o.cout;
         a.Hin = in.h; a.Win = in.w; a.Hout = out.h; a.Wout = out.w;
         a.relu = (int)o.relu;
         a.zero_page = p->dev_weights;   // first 64 floats of the weight arena are zeros
         a.ntiles = ((int)o.cout + 15) / 16;
-        a.src_begin = 0;
         a.src_end = a.n_src;
         a.acc_scale = 1.0f;
-        a.status = status_of(o.dst);
-        a.range_slot = slot_of(i, o.dst);
-        static const bool probe_on = ab_env("PF_PROBE") != nullptr;
-        a.probe = probe_on ? probe_buffer() : nullptr;
+        a.status = status_of(o.dst); a.range_slot = slot_of(ci, o.dst);
+        return st;
     };
-    // need: bit 1 = even tile rows (pooling epilogue), bit 2 = fused stage (not available on the generic path)
-    auto launch_conv_op = [&](const BlobOp &o, size_t i, ConvArgs &a, const ConvMeta &mt, int need) -> int {
+    // its fp32-source kernel (conv_select.cpp, pf_debug_force_conv) and what it can read / write as S4
+    auto choose = [&](Step &st, int need) {
+        const BlobOp &o = p->ops[st.ci];
+        const ConvPlan &cp = p->conv[st.ci];
+        const ConvArgs &a = st.u.c;
         const bool generic = (a.Win & 3) != 0;
         ConvChoice ch{0, 0, 0, 0};
         if (!generic) {
-            ch = choose_conv((int)o.k, (int)o.stride, a.Cin, a.Cout, a.Hout, a.Wout, p->opt_table_batch > 0 ? p->opt_table_batch : B, need,
-                             p->opt_use_tuned);
+            ch = choose_conv((int)o.k, (int)o.stride, a.Cin, a.Cout, a.Hout, a.Wout, Bt, need, p->opt_use_tuned);
             if (g_conv_force.kind == 2 && o.stride == 1) {
                 ch = g_conv_force;
                 if ((need & 2) && ch.p0 == 1) ch.p0 = 2;
             }
             if (g_conv_force.kind == 1) ch = g_conv_force;
-            if (g_conv_force.kind == 4 && p->conv[i].has_split && (!need || o.k == 1)) ch = g_conv_force;
-            if (ch.kind == 4 && (!p->conv[i].has_split || (need && o.k != 1) || !p->opt_split)) ch = ConvChoice{1, 0, 0, 0};
+            if (g_conv_force.kind == 4 && cp.has_split && (!need || o.k == 1)) ch = g_conv_force;
+            if (ch.kind == 4 && (!cp.has_split || (need && o.k != 1) || !p->opt_split)) ch = ConvChoice{1, 0, 0, 0};
             if (ch.kind == 3) ch = ConvChoice{1, 0, 0, 0};   // (kind 3 was conv_valu, removed in round 3: selected by no table row)
             // pf_debug_force_conv(5, ..): launches that cannot read S4 (fp32 sources) still have to be able to WRITE it
             if (g_conv_force.kind == 5) ch = ConvChoice{1, 0, 0, 0};
         }
-        if (dry) {
-            ConvRec r;
-            memset(&r, 0, sizeof(r));
-            memcpy(r.src_t, mt.src_t, sizeof(r.src_t));
-            r.dst_t = mt.dst_t;
-            r.sb = a.src_begin;
-            r.se = a.src_end;
-            // reads S4: the layers the table gives to the split kernels (same tile parameters), big 1x1 convs, or all
-            // eligible convs under pf_debug_force_conv(5, nt, wide)
-            const bool forced = g_conv_force.kind == 5;
-            const long px = (long)(p->opt_table_batch > 0 ? p->opt_table_batch : B) * a.Hout * a.Wout;   // (the pinned batch decides, like every other choice)
-            bool want = ch.kind == 4 || (o.k == 1 && px >= 32768 && ch.kind == 1) || forced;
-            r.nt = forced ? g_conv_force.p0 : (o.k == 1 ? 4 : (ch.kind == 4 ? ch.p0 : 2));
-            r.wide = forced ? g_conv_force.p1 : (ch.kind == 4 ? ch.p1 : 0);
-            ConvChoice s4c;   // measured conv_s4 row of this layer (conv_select.cpp): decides, and names the shape
-            if (!forced && !generic && p->opt_use_tuned &&
-                choose_s4((int)o.k, a.Cin, a.Cout, a.Hout, a.Wout, p->opt_table_batch > 0 ? p->opt_table_batch : B, &s4c)) {
-                want = s4c.kind == 5;
-                if (want) { r.nt = s4c.p0; r.wide = s4c.p1; }
-            }
-            bool res_fits = true;
-            if (a.res) {
-                const int nt1 = r.nt < 1 ? 1 : (r.nt > a.ntiles ? a.ntiles : r.nt);
-                res_fits = (size_t)nt1 * 16 * res_chan_stride(res_extent(8, a.res_sh), res_extent(32, a.res_sw)) * sizeof(float) <= 60 * 1024;
-            }
-            r.can_read = s4_allowed && !generic && o.stride == 1 && o.kind == OP_CONV && p->conv[i].has_s4 && (need == 0 || o.k == 1) && want &&
-                         res_fits && ((a.src_begin == 0 && a.src_end == a.n_src) || p->conv[i].s4_pad);
-            r.can_write_s4 = s4_allowed && !generic && (a.dst_choff & 1) == 0;
-            r.can_write = r.can_write_s4 && (ch.kind == 1 || ch.kind == 4);
-            // channel bookkeeping of the destination: zero-fill the tail of the last group unless its owner wrote it already
-            std::vector<uint8_t> &wr = written[mt.dst_t];
-            const int lo = a.dst_choff, hi = a.dst_choff + a.Cout;
-            if ((lo & 3) == 2 && !wr[lo - 2]) cand[mt.dst_t] = 0;   // would expose an unwritten half group to readers of this range
-            r.dst_limit = ((hi & 3) != 0 && !wr[hi]) ? (hi + 3) / 4 * 4 : hi;
-            for (int c = lo; c < hi; ++c) wr[c] = 1;
-            recs.push_back(r);
-            return PF_OK;
+        st.ch = ch; st.need = need; st.sb = a.src_begin; st.se = a.src_end;
+        // reads S4: the layers the table gives to the split kernels (same tile parameters), big 1x1 convs, or all
+        // eligible convs under pf_debug_force_conv(5, nt, wide)
+        const bool forced = g_conv_force.kind == 5;
+        const long px = (long)Bt * a.Hout * a.Wout;
+        bool want = ch.kind == 4 || (o.k == 1 && px >= 32768 && ch.kind == 1) || forced;
+        st.nt = forced ? g_conv_force.p0 : (o.k == 1 ? 4 : (ch.kind == 4 ? ch.p0 : 2));
+        st.wide = forced ? g_conv_force.p1 : (ch.kind == 4 ? ch.p1 : 0);
+        ConvChoice s4c;   // measured conv_s4 row of this layer (conv_select.cpp): decides, and names the shape
+        if (!forced && !generic && p->opt_use_tuned && choose_s4((int)o.k, a.Cin, a.Cout, a.Hout, a.Wout, Bt, &s4c)) {
+            want = s4c.kind == 5;
+            if (want) { st.nt = s4c.p0; st.wide = s4c.p1; }
         }
-        const ConvRec &rec = recs[rec_i++];
-        a.dst_fmt = fmt[rec.dst_t];
-        a.dst_c4 = (a.dst_ctotal + 3) / 4;
-        a.dst_limit = rec.dst_limit;
-        bool read_s4 = rec.can_read;
-        for (int j = rec.sb; j < rec.se; ++j) read_s4 = read_s4 && fmt[rec.src_t[j]];
-        if (read_s4) {
-            const int per = o.k == 3 ? 2 : 8;
-            int e = 0;
-            for (int j = 0; j < a.n_src; ++j) {
-                const int ch0 = a.src_choff[j], chn = a.src_cstart[j + 1] - a.src_cstart[j];
-                a.src_c4[j] = (a.src_ctotal[j] + 3) / 4;
-                a.src_g0[j] = ch0 / 4;
-                a.src_gn[j] = (ch0 + chn + 3) / 4 - ch0 / 4;
-                a.src_ent0[j] = e;
-                e += p->conv[i].s4_pad ? (a.src_gn[j] + per - 1) / per * per : a.src_gn[j];
-            }
-            for (int j = a.n_src; j <= kConvMaxSrc; ++j) a.src_ent0[j] = e;
-            a.src_fmt = 1;
-            a.acc_scale = p->conv[i].split_acc_scale;
-            a.wpk = p->dev_weights + p->conv[i].s4_off;
-            a.nchunks = p->conv[i].s4_rounds;
-            a.chunk_begin = a.src_ent0[a.src_begin] / per;
-            a.chunk_end = (a.src_ent0[a.src_end] + per - 1) / per;
-            return launch_conv_s4(a, (int)o.k, rec.nt, rec.wide, B, s);
-        }
-        if (generic) {
-            if (need) return fail(PF_EUNSUPPORTED, "fused conv on a width that is not a multiple of 4");
-            a.wpk = p->dev_weights + p->conv[i].wpk_off;
-            a.nchunks = p->conv[i].tiling.nchunks;
-            return launch_conv(a, p->conv[i].tiling, B, s);
-        }
-        int rc = PF_EUNSUPPORTED;
-        auto set_chunks = [&](int kc) {
-            a.src_chunk0[0] = 0;
-            for (int j = 0; j < kConvMaxSrc; ++j)
-                a.src_chunk0[j + 1] = a.src_chunk0[j] + (j < a.n_src ? ((int)o.src[j].ch + kc - 1) / kc : 0);
-            a.chunk_begin = a.src_chunk0[a.src_begin];
-            a.chunk_end = a.src_chunk0[a.src_end];
-        };
-        if (ch.kind == 4) {
-            a.wpk = p->dev_weights + p->conv[i].split_off;
-            a.acc_scale = p->conv[i].split_acc_scale;
-            a.nchunks = p->conv[i].split_chunks;
-            set_chunks(o.k == 1 ? 32 : 8);
-            rc = o.k == 1 ? launch_conv_split1(a, ch.p0, B, s) : launch_conv_split(a, ch.p0, ch.p1, B, s);
-            if (rc != PF_EUNSUPPORTED) return rc;
-            ch = ConvChoice{1, 0, 0, 0};
-        }
-        if (ch.kind == 2) {
-            a.wpk = p->dev_weights + p->conv[i].wave_off;
-            a.nchunks = p->conv[i].wave_chunks;
-            set_chunks(wave_kc((int)o.k));
-            rc = launch_conv_wave(a, (int)o.k, ch.p0, ch.p1 < a.ntiles ? ch.p1 : a.ntiles, ch.p2, B, s);
-            if (rc == PF_EUNSUPPORTED) ch = ConvChoice{1, 0, 0, 0};   // shape not built: conv_dma with its cost model
-        }
-        if (ch.kind != 2) {
-            a.wpk = p->dev_weights + p->conv[i].tiled_off;
-            a.nchunks = p->conv[i].tiled_chunks;
-            set_chunks(dma_kc((int)o.k, (int)o.stride));
-            // the trailing rem_count output channels of a big image go to the vector ALU instead of an MFMA tile
-            // (conv_dma WM=4 shapes only: forced or cost-model-chosen WM is checked inside, which falls back)
-            a.rem = 0;
-            if (p->opt_valu_rem && p->conv[i].rem_off && !need && !a.dst_fmt && a.src_begin == 0 && a.src_end == a.n_src &&
-                (ch.p0 == 0 || ch.p0 == 4)) {
-                a.rem = p->conv[i].rem_count;
-                a.wrem = p->dev_weights + p->conv[i].rem_off;
-                a.ntiles = ((int)o.cout - a.rem) / 16;
-                rc = launch_conv_dma(a, (int)o.k, (int)o.stride, B, s, 4, ch.p0 == 4 && ch.p1 > 0 ? ch.p1 : 0, p->opt_table_batch);
-                if (rc == PF_EUNSUPPORTED) {
-                    a.rem = 0;
-                    a.ntiles = ((int)o.cout + 15) / 16;
-                }
-            }
-            if (a.rem == 0) rc = launch_conv_dma(a, (int)o.k, (int)o.stride, B, s, ch.p0, ch.p1, p->opt_table_batch);
-        }
-        return rc;
+        const int nt1 = st.nt < 1 ? 1 : (st.nt > a.ntiles ? a.ntiles : st.nt);
+        const bool res_fits = !a.res || (size_t)nt1 * 16 * res_chan_stride(res_extent(8, a.res_sh), res_extent(32, a.res_sw)) * sizeof(float) <= 60 * 1024;
+        st.can_read = s4_allowed && !generic && o.stride == 1 && o.kind == OP_CONV && cp.has_s4 && (need == 0 || o.k == 1) && want &&
+                      res_fits && ((a.src_begin == 0 && a.src_end == a.n_src) || cp.s4_pad);
+        st.can_write_s4 = s4_allowed && !generic && (a.dst_choff & 1) == 0;
+        st.can_write = st.can_write_s4 && (ch.kind == 1 || ch.kind == 4);
+        st.u.c.dst_limit = claim(st.dst_t, a.dst_choff, a.dst_choff + a.Cout);
     };
     // pf_set_option("fuse_upsample", 0/1); at B=4: transUp.3 + conv1x1_up.3 144 us fused vs 233 us as two passes
     const bool fuse_up = p->opt_fuse_upsample != 0;   // option "fuse_upsample"
@@ -443,320 +387,347 @@ int run_net(const pf_plan *p, const StemArgs *stem, const float *dense_x, int B,
                2 * in.h <= out.h + 1 && 2 * in.w <= out.w + 1;   // >= ~2x upsampling: the residual window of a tile stays small
     };
 
-    static const bool sync_ops = ab_env("PF_SYNC_OPS") != nullptr;   // debugging: localise a faulting launch
+    // ---- 2. one walk over the ops: fusions (front, pool, commuted upsample) and each convolution's choice
     cand[input] = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-    dry = pass == 0;
     for (size_t i = 0; i < p->ops.size(); ++i) {
-        if (sync_ops && !dry) {
-            const hipError_t e = hipStreamSynchronize(s);
-            fprintf(stderr, "[pf] before op %zu (%s): %s\n", i, p->tensors[p->ops[i].dst].name, hipGetErrorString(e));
-        }
         const BlobOp &o = p->ops[i];
         const Dims in = d[o.src[0].tensor];
         const Dims out = o.kind == OP_HEAD ? in : d[o.dst];
-        if (tag_ops && prof_enabled() && !dry) {
-            char tag[96];
-            snprintf(tag, sizeof(tag), "%02zu %s %u->%u %dx%d", i, p->tensors[o.dst].name, o.cin, o.cout, out.h, out.w);
-            prof_set_tag(tag);
-        }
-        // ops executed by kernels that only know fp32 NCHW pin their tensors to it
-        auto pin_fp32 = [&](const BlobOp &op) {
-            for (uint32_t j = 0; j < op.n_src; ++j) cand[op.src[j].tensor] = 0;
-            cand[op.dst] = 0;
-        };
-        // stem -> [3x3 s1 16 -> 24] -> [3x3 s2 24 -> <= 32] with single readers: the two convs run as conv_front.hip on the
-        // packed-pair stem output; the tensor between them is never stored
-        bool front = false;
-        if (o.kind == OP_STEM && stem && s4_allowed && p->opt_fuse_front && i + 2 < p->ops.size()) {
-            const BlobOp &n1 = p->ops[i + 1], &n2 = p->ops[i + 2];
-            StemArgs probe = *stem;
-            probe.wdep = p->dev_weights + p->conv[i].dep_off;
-            probe.woh = p->conv[i].has_oh ? p->dev_weights + p->conv[i].oh_off : nullptr;
-            probe.Hout = out.h; probe.Wout = out.w;
-            front = n1.kind == OP_CONV && n1.k == 3 && n1.stride == 1 && n1.n_src == 1 && n1.src[0].tensor == o.dst && n1.src[0].choff == 0 &&
-                    n1.src[0].ch == p->tensors[o.dst].channels && n1.dst_choff == 0 && n1.cout == p->tensors[n1.dst].channels &&
-                    p->readers[o.dst] == 1 && p->readers[n1.dst] == 1 && n1.relu && p->conv[i + 1].has_s4 && p->conv[i + 1].s4_rounds == 2 &&
-                    n2.kind == OP_CONV && n2.k == 3 && n2.stride == 2 && n2.n_src == 1 && n2.src[0].tensor == n1.dst && n2.src[0].choff == 0 &&
-                    n2.src[0].ch == n1.cout && p->conv[i + 2].has_front && (n2.dst_choff & 3) == 0 &&
-                    conv_front_supports((int)o.cout, (int)n1.cout, (int)n2.cout, out.h, out.w, (int)p->tensors[n2.dst].channels) && stem_writes_s4(probe) && g_conv_force.kind == 0;
-        }
-        if (front) {
-            const BlobOp &n1 = p->ops[i + 1], &n2 = p->ops[i + 2];
-            const Dims o2 = d[n2.dst];
-            if (dry) {
-                cand[o.dst] = 0; cand[n1.dst] = 0;   // (not subject to the format decision: the stem output is packed, the middle tensor never exists)
-                ConvRec r;
-                memset(&r, 0, sizeof(r));
-                r.dst_t = n2.dst;
-                r.sb = r.se = 0;
-                r.can_read = false; r.can_write = true; r.can_write_s4 = true;
-                std::vector<uint8_t> &wr = written[n2.dst];
-                const int lo = (int)n2.dst_choff, hi = lo + (int)n2.cout;
-                if ((lo & 3) == 2 && !wr[lo - 2]) cand[n2.dst] = 0;
-                r.dst_limit = ((hi & 3) != 0 && !wr[hi]) ? (hi + 3) / 4 * 4 : hi;
-                for (int c = lo; c < hi; ++c) wr[c] = 1;
-                recs.push_back(r);
-                i += 2;
+        if (o.kind == OP_STEM && stem) {
+            StemArgs a = *stem;
+            a.w = p->dev_weights + p->conv[i].raw_off; a.wdep = p->dev_weights + p->conv[i].dep_off;
+            a.woh = p->conv[i].has_oh ? p->dev_weights + p->conv[i].oh_off : nullptr; a.bias = p->dev_weights + p->conv[i].bias_off;
+            a.status = status_of(o.dst); a.range_slot = slot_of(i, o.dst);
+            a.lut = p->dev_lut; a.dst = tptr(o.dst); a.Hout = out.h; a.Wout = out.w;
+            // stem -> [3x3 s1 16 -> 24] -> [3x3 s2 24 -> <= 32] with single readers: the two convs run as conv_front.hip on the
+            // packed-pair stem output; the tensor between them is never stored
+            bool front = false;
+            if (s4_allowed && p->opt_fuse_front && i + 2 < p->ops.size()) {
+                const BlobOp &n1 = p->ops[i + 1], &n2 = p->ops[i + 2];
+                front = n1.kind == OP_CONV && n1.k == 3 && n1.stride == 1 && n1.n_src == 1 && n1.src[0].tensor == o.dst && n1.src[0].choff == 0 &&
+                        n1.src[0].ch == p->tensors[o.dst].channels && n1.dst_choff == 0 && n1.cout == p->tensors[n1.dst].channels &&
+                        p->readers[o.dst] == 1 && p->readers[n1.dst] == 1 && n1.relu && p->conv[i + 1].has_s4 && p->conv[i + 1].s4_rounds == 2 &&
+                        n2.kind == OP_CONV && n2.k == 3 && n2.stride == 2 && n2.n_src == 1 && n2.src[0].tensor == n1.dst && n2.src[0].choff == 0 &&
+                        n2.src[0].ch == n1.cout && p->conv[i + 2].has_front && (n2.dst_choff & 3) == 0 &&
+                        conv_front_supports((int)o.cout, (int)n1.cout, (int)n2.cout, out.h, out.w, (int)p->tensors[n2.dst].channels) && stem_writes_s4(a) && g_conv_force.kind == 0;
+            }
+            if (!front) {
+                if (o.cout != 16 || o.k != 3 || o.stride != 2 || o.dst_choff != 0 ||
+                    p->tensors[o.dst].channels != 16 || (uint32_t)(a.T * (a.n_cls + 1)) != o.cin)
+                    return fail(PF_EUNSUPPORTED, "fused stem expects a 3x3/s2 conv %d->16, got %u->%u k%u s%u",
+                                a.T * (a.n_cls + 1), o.cin, o.cout, o.k, o.stride);
+                static const int stem_plane_pad = ab_env("PF_DBG_PLANE_PAD") ? atoi(ab_env("PF_DBG_PLANE_PAD")) : 0;
+                a.dbg_plane_pad = stem_plane_pad;
+                push(S_STEM, i).u.sf.stem = a;
+                pin_fp32(o);
                 continue;
             }
-            const ConvRec &rec = recs[rec_i++];
-            StemArgs a = *stem;
-            a.w = p->dev_weights + p->conv[i].raw_off;
-            a.wdep = p->dev_weights + p->conv[i].dep_off;
-            a.woh = p->conv[i].has_oh ? p->dev_weights + p->conv[i].oh_off : nullptr;
-            a.bias = p->dev_weights + p->conv[i].bias_off;
-            a.status = status_of(o.dst);
-            a.range_slot = slot_of(i, o.dst);
-            a.lut = p->dev_lut;
-            a.dst = tptr(o.dst);
-            a.dst_fmt = 1;
-            a.Hout = out.h; a.Wout = out.w;
-            if ((rc = launch_stem(a, s))) return rc;
-            FrontArgs f;
-            memset(&f, 0, sizeof(f));
+            const BlobOp &n1 = p->ops[i + 1], &n2 = p->ops[i + 2];
+            const Dims o2 = d[n2.dst];   // (the front end's output)
+            cand[o.dst] = 0; cand[n1.dst] = 0;   // (not subject to the format decision: the stem output is packed, the middle tensor never exists)
+            Step &st = push(S_STEM_FRONT, i);
+            st.u.sf.stem = a; st.u.sf.stem.dst_fmt = 1;
+            FrontArgs &f = st.u.sf.front;
             f.x = tptr(o.dst);
-            f.w1 = p->dev_weights + p->conv[i + 1].s4_off;
-            f.w2 = p->dev_weights + p->conv[i + 2].front_off;
-            f.bias1 = p->dev_weights + p->conv[i + 1].bias_off;
-            f.bias2 = p->dev_weights + p->conv[i + 2].bias_off;
-            f.scale1 = p->conv[i + 1].split_acc_scale;
-            f.scale2 = p->conv[i + 2].split_acc_scale;
+            f.w1 = p->dev_weights + p->conv[i + 1].s4_off; f.w2 = p->dev_weights + p->conv[i + 2].front_off;
+            f.bias1 = p->dev_weights + p->conv[i + 1].bias_off; f.bias2 = p->dev_weights + p->conv[i + 2].bias_off;
+            f.scale1 = p->conv[i + 1].split_acc_scale; f.scale2 = p->conv[i + 2].split_acc_scale;
             f.dst = tptr(n2.dst);
-            f.dst_fmt = fmt[n2.dst];
-            f.dst_ctotal = (int)p->tensors[n2.dst].channels;
-            f.dst_c4 = (f.dst_ctotal + 3) / 4;
-            f.dst_choff = (int)n2.dst_choff;
-            f.dst_limit = rec.dst_limit;
+            f.dst_ctotal = (int)p->tensors[n2.dst].channels; f.dst_c4 = (f.dst_ctotal + 3) / 4; f.dst_choff = (int)n2.dst_choff;
+            f.dst_limit = claim(n2.dst, f.dst_choff, f.dst_choff + (int)n2.cout);
             f.H1 = out.h; f.W1 = out.w; f.H2 = o2.h; f.W2 = o2.w;
             f.C1 = (int)n1.cout; f.C2 = (int)n2.cout; f.relu1 = (int)n1.relu; f.relu2 = (int)n2.relu;
             f.status = status_all;
-            f.range_slot_mid = slot_of(i + 1, n1.dst);
-            f.range_slot = slot_of(i + 2, n2.dst);
-            static const bool front_probe = ab_env("PF_PROBE") != nullptr;
-            f.probe = front_probe ? probe_buffer() : nullptr;
-            if (tag_ops && prof_enabled()) {
-                char tag[96];
-                snprintf(tag, sizeof(tag), "%02zu+%02zu %s+%s %u->%u->%u %dx%d", i + 1, i + 2, p->tensors[n1.dst].name, p->tensors[n2.dst].name, o.cout,
-                         n1.cout, n2.cout, o2.h, o2.w);
-                prof_set_tag(tag);
-            }
-            if ((rc = launch_conv_front(f, B, s))) return rc;
-            fmt[o.dst] = 1;            // pf_hardnet_tensor_read unpacks the stem output
-            p->last_fmt = fmt;
-            p->last_fmt[n1.dst] = 0xFF;   // ... and refuses the tensor between the two convs: it is never stored
+            f.range_slot_mid = slot_of(i + 1, n1.dst); f.range_slot = slot_of(i + 2, n2.dst);
+            st.dst_t = n2.dst; st.can_write = st.can_write_s4 = true;
+            if (tags)
+                snprintf(st.u.sf.front_tag, sizeof(st.u.sf.front_tag), "%02zu+%02zu %s+%s %u->%u->%u %dx%d", i + 1, i + 2, p->tensors[n1.dst].name,
+                         p->tensors[n2.dst].name, o.cout, n1.cout, n2.cout, o2.h, o2.w);
             i += 2;
-            continue;
-        }
-        // ---- an odd HarDBlock layer inside its consumer (conv_pair.hip): decided in the REAL pass only - the dry pass recorded the two
-        //      launches as they would run alone, so the formats are what the unfused plan has, and any pair whose tensors did not all
-        //      end up as packed pairs simply runs as two launches
-        if (!dry && p->opt_fuse_pairs && is_conv_pair(p, i) && p->conv[i + 1].has_pair && (in.w & 3) == 0 && (g_conv_force.kind == 0 || g_conv_force.kind == 5) &&
-            rec_i + 1 < recs.size()) {
-            const BlobOp &C = p->ops[i + 1];
-            const ConvRec &rp = recs[rec_i], &rc_ = recs[rec_i + 1];
-            bool ok = rp.can_read && rc_.can_read && fmt[o.dst] && fmt[C.dst] && fmt[o.src[0].tensor];
-            for (uint32_t j = 1; j < C.n_src; ++j) ok = ok && fmt[C.src[j].tensor];
-            const int Bt = p->opt_table_batch > 0 ? p->opt_table_batch : B;
-            ok = ok && pair_wanted((int)o.cin, (int)o.cout, (int)C.cin, (int)C.cout, out.h, out.w, Bt, p->opt_fuse_pairs);
-            if (ok) {
-                PairArgs pa;
-                memset(&pa, 0, sizeof(pa));
-                ConvMeta mt;
-                fill_conv_args(C, i + 1, in, out, pa.c, mt);
-                ConvArgs &a = pa.c;
-                // K order [S, others.., P]: source j of the launch = source (j + 1) % n of the op
-                const int n = (int)C.n_src;
-                int e = 0;
-                for (int j = 0; j < n; ++j) {
-                    const BlobSrc &sj = C.src[(j + 1) % n];
-                    const bool isP = j == n - 1;
-                    a.src[j] = tptr(sj.tensor);
-                    a.src_ctotal[j] = (int)p->tensors[sj.tensor].channels;
-                    a.src_choff[j] = (int)sj.choff;
-                    a.src_c4[j] = (a.src_ctotal[j] + 3) / 4;
-                    a.src_g0[j] = isP ? 0 : (int)sj.choff / 4;
-                    a.src_gn[j] = isP ? ((int)sj.ch + 3) / 4 : ((int)sj.choff + (int)sj.ch + 3) / 4 - (int)sj.choff / 4;
-                    a.src_ent0[j] = e;
-                    e += (a.src_gn[j] + 1) / 2 * 2;
-                }
-                for (int j = n; j <= kConvMaxSrc; ++j) a.src_ent0[j] = e;
-                a.src_fmt = 1;
-                a.dst_fmt = 1;
-                a.dst_c4 = (a.dst_ctotal + 3) / 4;
-                a.dst_limit = rc_.dst_limit;
-                a.acc_scale = p->conv[i + 1].split_acc_scale;
-                a.wpk = p->dev_weights + p->conv[i + 1].pair_c_off;
-                a.nchunks = p->conv[i + 1].pair_rounds;
-                pa.p_wpk = p->dev_weights + p->conv[i + 1].pair_two_off;
-                pa.p_w9 = p->dev_weights + p->conv[i + 1].pair_nine_off;
-                pa.p_bias = p->dev_weights + p->conv[i].bias_off;
-                pa.p_acc_scale = p->conv[i].split_acc_scale;
-                pa.p_dst = tptr(o.dst);
-                pa.p_dst_c4 = ((int)p->tensors[o.dst].channels + 3) / 4;
-                pa.p_dst_choff = (int)o.dst_choff;
-                pa.p_dst_limit = rp.dst_limit;
-                pa.p_cout = (int)o.cout;
-                pa.p_cin = (int)o.cin;
-                pa.p_ntiles = ((int)o.cout + 15) / 16;
-                pa.p_relu = (int)o.relu;
-                pa.p_range_slot = slot_of(i, o.dst);
-                pa.rounds_s = a.src_ent0[1] / 2;
-                pa.round_d = a.src_ent0[n - 1] / 2;
-                pa.merged = p->conv[i + 1].pair_merged && p->opt_fuse_pairs != 3;
-                if (tag_ops && prof_enabled()) {
-                    char tag[96];
-                    snprintf(tag, sizeof(tag), "%02zu+%02zu %s+%s %u->%u->%u %dx%d", i, i + 1, p->tensors[o.dst].name, p->tensors[C.dst].name, o.cin,
-                             o.cout, C.cout, out.h, out.w);
-                    prof_set_tag(tag);
-                }
-                if ((rc = launch_conv_pair(pa, B, s))) return rc;
-                rec_i += 2;
-                ++i;
-                continue;
-            }
-        }
-        if (o.kind == OP_STEM && stem) {
-            if (dry) { pin_fp32(o); continue; }
-            StemArgs a = *stem;
-            a.w = p->dev_weights + p->conv[i].raw_off;
-            a.wdep = p->dev_weights + p->conv[i].dep_off;
-            a.woh = p->conv[i].has_oh ? p->dev_weights + p->conv[i].oh_off : nullptr;
-            static const bool stem_probe = ab_env("PF_PROBE") != nullptr;     // read once, not per forward
-            static const int stem_plane_pad = ab_env("PF_DBG_PLANE_PAD") ? atoi(ab_env("PF_DBG_PLANE_PAD")) : 0;
-            a.probe = stem_probe ? probe_buffer() : nullptr;
-            a.dbg_plane_pad = stem_plane_pad;
-            a.bias = p->dev_weights + p->conv[i].bias_off;
-            a.status = status_of(o.dst);
-            a.range_slot = slot_of(i, o.dst);
-            a.lut = p->dev_lut;
-            a.dst = tptr(o.dst);
-            a.Hout = out.h;
-            a.Wout = out.w;
-            if (o.cout != 16 || o.k != 3 || o.stride != 2 || o.dst_choff != 0 ||
-                p->tensors[o.dst].channels != 16 || (uint32_t)(a.T * (a.n_cls + 1)) != o.cin)
-                return fail(PF_EUNSUPPORTED, "fused stem expects a 3x3/s2 conv %d->16, got %u->%u k%u s%u",
-                            a.T * (a.n_cls + 1), o.cin, o.cout, o.k, o.stride);
-            if ((rc = launch_stem(a, s))) return rc;
         } else if (o.kind == OP_STEM || o.kind == OP_CONV) {
             if (o.src[0].tensor == input && !dense_x)
                 return fail(PF_EINVAL, "network input is consumed by a generic conv: use pf_hardnet_forward_dense");
             // a caller-provided dense input has no producer kernel that could have checked its range
             // (its maximum goes to the last slot of the block: the input has no op of its own)
-            if (o.src[0].tensor == input && !dry && status_all &&
-                (rc = launch_range_check(dense_x, (size_t)B * p->tensors[input].channels * in.h * in.w, status_all, st_words + kSlot0 + kMaxSlots - 1, s)))
-                return rc;
+            if (o.src[0].tensor == input && status_all) {
+                PlainArgs &x = push(S_RANGE_CHECK, i).u.x;
+                x.src = dense_x; x.n = (size_t)B * p->tensors[input].channels * in.h * in.w;
+                x.status = status_all; x.slot = st_words + kSlot0 + kMaxSlots - 1;
+            }
             // conv + AvgPool2d(2,2): pool in the conv epilogue, the full-resolution tensor is never written
             const BlobOp *pool = nullptr;
             if (fuse && i + 1 < p->ops.size() && p->ops[i + 1].kind == OP_POOL && o.stride == 1 && o.k == 1 && (in.w & 3) == 0 &&
                 p->ops[i + 1].src[0].tensor == o.dst && o.dst_choff == 0 && o.cout == p->tensors[o.dst].channels &&
                 p->readers[o.dst] == 1 && out.h >= 2 && out.w >= 2)
                 pool = &p->ops[i + 1];
-            ConvArgs a;
-            ConvMeta mt;
-            fill_conv_args(o, i, in, out, a, mt);
+            Step &st = conv_step(i, i, in, out);
             if (pool) {
-                a.pool = 1;
-                a.dst = tptr(pool->dst);
-                mt.dst_t = pool->dst;
-                a.dst_ctotal = (int)p->tensors[pool->dst].channels;
-                a.status = status_of(pool->dst);
-                a.range_slot = slot_of(i, pool->dst);
+                ConvArgs &a = st.u.c;
+                a.pool = 1; a.dst = tptr(pool->dst); a.dst_ctotal = (int)p->tensors[pool->dst].channels;
+                st.dst_t = pool->dst;
+                a.status = status_of(pool->dst); a.range_slot = slot_of(i, pool->dst);
+                ++i;   // the pool op is done
             }
-            if ((rc = launch_conv_op(o, i, a, mt, pool ? 2 : 0))) return rc;
-            if (pool) ++i;   // the pool op is done
-        } else if (o.kind == OP_POOL) {
-            if (dry) { pin_fp32(o); continue; }
-            if ((rc = launch_avgpool2(tptr(o.src[0].tensor), tptr(o.dst), B * (int)o.cin, in.h, in.w, status_of(o.dst), slot_of(i, o.dst), s))) return rc;
+            choose(st, pool ? 2 : 0);
         } else if (o.kind == OP_UPSAMPLE && can_commute_upsample(i, in, out)) {
             // TransitionUp + 1x1 conv over cat([up(x), skip])  ==  W_skip*skip + up(W_x*x)   (conv_epilogue.h)
             const BlobOp &n = p->ops[i + 1];
             const Dims hi = out;   // = size of the skip tensor
-            ConvArgs lo;
-            ConvMeta lo_mt;
-            fill_conv_args(n, i + 1, in, in, lo, lo_mt);
-            lo.src[0] = tptr(o.src[0].tensor);                 // x at the low resolution
-            lo_mt.src_t[0] = o.src[0].tensor;
-            lo.src_ctotal[0] = (int)p->tensors[o.src[0].tensor].channels;
-            lo.src_choff[0] = (int)o.src[0].choff;
-            lo.dst = tptr(o.dst);                              // scratch: the slot of the (never built) upsampled tensor
-            lo_mt.dst_t = o.dst;
-            if (dry) cand[o.dst] = 0;                          // sampled as an fp32 residual by the other half
-            lo.dst_ctotal = (int)n.cout;
-            lo.dst_choff = 0;
-            lo.relu = 0;
-            lo.no_bias = 1;
-            lo.status = nullptr;                               // an fp32 residual of the other half, never a split operand
-            lo.range_slot = nullptr;
-            lo.Cin = (int)n.src[0].ch;
-            lo.src_begin = 0;
-            lo.src_end = 1;
-            auto tag_half = [&](const char *half, int cin, const Dims &dd) {
-                if (!(tag_ops && prof_enabled()) || dry) return;
-                char tag[96];
-                snprintf(tag, sizeof(tag), "%02zu%c %s.%s %d->%u %dx%d", i + 1, half[0] == 'l' ? 'a' : 'b', p->tensors[n.dst].name,
-                         half, cin, n.cout, dd.h, dd.w);
-                prof_set_tag(tag);
+            cand[o.dst] = 0;       // sampled as an fp32 residual by the other half
+            auto tag_half = [&](Step &st, const char *half, int cin, const Dims &dd) {
+                if (tags)
+                    snprintf(st.tag, sizeof(st.tag), "%02zu%c %s.%s %d->%u %dx%d", i + 1, half[0] == 'l' ? 'a' : 'b', p->tensors[n.dst].name,
+                             half, cin, n.cout, dd.h, dd.w);
             };
-            tag_half("lo", lo.Cin, in);
-            if ((rc = launch_conv_op(n, i + 1, lo, lo_mt, 4))) return rc;
-            if (sync_ops && !dry) fprintf(stderr, "[pf]   low-resolution half: %s\n", hipGetErrorString(hipStreamSynchronize(s)));
-            ConvArgs hi_a;
-            ConvMeta hi_mt;
-            fill_conv_args(n, i + 1, hi, hi, hi_a, hi_mt);
-            hi_a.Cin = (int)n.src[1].ch;
-            hi_a.src_begin = 1;
-            hi_a.src_end = 2;
-            tag_half("hi", hi_a.Cin, hi);
-            hi_a.res = tptr(o.dst);
-            hi_a.res_ctotal = (int)n.cout;
-            hi_a.res_choff = 0;
-            hi_a.Hres = in.h;
-            hi_a.Wres = in.w;
-            hi_a.res_sh = hi.h > 1 ? (float)(in.h - 1) / (float)(hi.h - 1) : 0.f;
-            hi_a.res_sw = hi.w > 1 ? (float)(in.w - 1) / (float)(hi.w - 1) : 0.f;
-            if ((rc = launch_conv_op(n, i + 1, hi_a, hi_mt, 4))) return rc;
+            Step &ls = conv_step(i, i + 1, in, in);
+            ConvArgs &lo = ls.u.c;
+            lo.src[0] = tptr(o.src[0].tensor);                 // x at the low resolution
+            ls.src_t[0] = o.src[0].tensor;
+            lo.src_ctotal[0] = (int)p->tensors[o.src[0].tensor].channels; lo.src_choff[0] = (int)o.src[0].choff;
+            lo.dst = tptr(o.dst);                              // scratch: the slot of the (never built) upsampled tensor
+            ls.dst_t = o.dst;
+            lo.dst_ctotal = (int)n.cout; lo.dst_choff = 0;
+            lo.relu = 0; lo.no_bias = 1;
+            lo.status = nullptr; lo.range_slot = nullptr;      // an fp32 residual of the other half, never a split operand
+            lo.Cin = (int)n.src[0].ch;
+            lo.src_end = 1;
+            tag_half(ls, "lo", lo.Cin, in);
+            choose(ls, 4);
+            Step &hs = conv_step(i, i + 1, hi, hi);
+            ConvArgs &ha = hs.u.c;
+            ha.Cin = (int)n.src[1].ch;
+            ha.src_begin = 1; ha.src_end = 2;
+            tag_half(hs, "hi", ha.Cin, hi);
+            ha.res = tptr(o.dst); ha.res_ctotal = (int)n.cout;
+            ha.Hres = in.h; ha.Wres = in.w;
+            ha.res_sh = hi.h > 1 ? (float)(in.h - 1) / (float)(hi.h - 1) : 0.f;
+            ha.res_sw = hi.w > 1 ? (float)(in.w - 1) / (float)(hi.w - 1) : 0.f;
+            choose(hs, 4);
             ++i;   // the 1x1 conv is done
-        } else if (o.kind == OP_UPSAMPLE) {
-            if (dry) { pin_fp32(o); continue; }
-            if ((rc = launch_upsample(tptr(o.src[0].tensor), tptr(o.dst), B * (int)o.cin, in.h, in.w, out.h, out.w, status_of(o.dst), slot_of(i, o.dst), s)))
-                return rc;
         } else if (o.kind == OP_HEAD) {
-            if (dry) { pin_fp32(o); continue; }
-            HeadArgs a;
+            pin_fp32(o);
+            Step &st = push(S_HEAD, i);
+            HeadArgs &a = st.u.head.h;
             a.logits = tptr(o.src[0].tensor);
             a.out_seg = out_seg; a.out_logits = out_logits; a.out_is_i64 = out_seg_is_i64;
             a.B = B; a.C = (int)o.cin; a.Hin = in.h; a.Win = in.w; a.Hout = out_h; a.Wout = out_w;
-            if (out_orig && (rc = launch_copy(out_orig, a.logits, (size_t)B * a.C * in.h * in.w * sizeof(float), s))) return rc;
-            if ((rc = launch_head(a, s))) return rc;
+            st.u.head.orig = out_orig; st.u.head.orig_bytes = (size_t)B * a.C * in.h * in.w * sizeof(float);
+        } else {   // OP_POOL, OP_UPSAMPLE
+            pin_fp32(o);
+            PlainArgs &x = push(o.kind == OP_POOL ? S_POOL : S_UPSAMPLE, i).u.x;
+            x.src = tptr(o.src[0].tensor); x.dst = tptr(o.dst); x.planes = B * (int)o.cin;
+            x.hin = in.h; x.win = in.w; x.hout = out.h; x.wout = out.w;
+            x.status = status_of(o.dst); x.slot = slot_of(i, o.dst);
         }
     }
-    if (dry) {
-        // fixpoint: a launch reads S4 only if ALL the ranges it accumulates are S4; a tensor stays S4 only while all its
-        // readers do and all its writers can
-        if (!s4_allowed) std::fill(cand.begin(), cand.end(), 0);
-        for (bool changed = true; changed;) {
-            changed = false;
-            for (const ConvRec &r : recs) {
-                bool all = r.can_read;
-                for (int j = r.sb; j < r.se; ++j) all = all && cand[r.src_t[j]];
-                if (!all)
-                    for (int j = r.sb; j < r.se; ++j)
-                        if (cand[r.src_t[j]]) { cand[r.src_t[j]] = 0; changed = true; }
-                if (!(r.can_write || (all && r.can_write_s4)) && cand[r.dst_t]) { cand[r.dst_t] = 0; changed = true; }
+
+    // ---- 3. formats, a fixpoint: a launch reads S4 only if ALL the ranges it accumulates are S4; a tensor stays S4 only while
+    //      all its readers do and all its writers can
+    if (!s4_allowed) std::fill(cand.begin(), cand.end(), 0);
+    for (bool changed = true; changed;) {
+        changed = false;
+        for (const Step &r : steps) {
+            if (r.kind != S_CONV && r.kind != S_STEM_FRONT) continue;
+            bool all = r.can_read;
+            for (int j = r.sb; j < r.se; ++j) all = all && cand[r.src_t[j]];
+            if (!all)
+                for (int j = r.sb; j < r.se; ++j)
+                    if (cand[r.src_t[j]]) { cand[r.src_t[j]] = 0; changed = true; }
+            if (!(r.can_write || (all && r.can_write_s4)) && cand[r.dst_t]) { cand[r.dst_t] = 0; changed = true; }
+        }
+    }
+    // a tensor nobody reads as S4 (network outputs tapped by the caller) stays fp32
+    std::vector<uint8_t> read_s4(nT, 0);
+    for (const Step &r : steps)
+        if (r.kind == S_CONV)
+            for (int j = r.sb; j < r.se; ++j) read_s4[r.src_t[j]] = 1;
+    for (size_t t = 0; t < nT; ++t) fmt[t] = cand[t] && read_s4[t];
+
+    // ---- 4. each convolution's kernel: S4 sources, or its fp32-source kernel where that one has a kernel for the launch, else conv_dma
+    for (Step &st : steps) {
+        if (st.kind == S_STEM_FRONT) {
+            st.u.sf.front.dst_fmt = fmt[st.dst_t];
+            fmt[p->ops[st.op].dst] = 1;            // pf_hardnet_tensor_read unpacks the stem output
+            fmt[p->ops[st.op + 1].dst] = 0xFF;     // ... and refuses the tensor between the two convs: it is never stored
+        }
+        if (st.kind != S_CONV) continue;
+        const BlobOp &o = p->ops[st.ci];
+        const ConvPlan &cp = p->conv[st.ci];
+        ConvArgs &a = st.u.c;
+        a.dst_fmt = fmt[st.dst_t]; a.dst_c4 = (a.dst_ctotal + 3) / 4;
+        bool s4 = st.can_read;
+        for (int j = st.sb; j < st.se; ++j) s4 = s4 && fmt[st.src_t[j]];
+        if (s4) {
+            const int per = o.k == 3 ? 2 : 8;
+            int e = 0;
+            for (int j = 0; j < a.n_src; ++j) {
+                const int ch0 = a.src_choff[j], chn = a.src_cstart[j + 1] - a.src_cstart[j];
+                a.src_c4[j] = (a.src_ctotal[j] + 3) / 4;
+                a.src_g0[j] = ch0 / 4;
+                a.src_gn[j] = (ch0 + chn + 3) / 4 - ch0 / 4;
+                a.src_ent0[j] = e;
+                e += cp.s4_pad ? (a.src_gn[j] + per - 1) / per * per : a.src_gn[j];
+            }
+            for (int j = a.n_src; j <= kConvMaxSrc; ++j) a.src_ent0[j] = e;
+            a.src_fmt = 1; a.acc_scale = cp.split_acc_scale;
+            a.wpk = p->dev_weights + cp.s4_off; a.nchunks = cp.s4_rounds;
+            a.chunk_begin = a.src_ent0[a.src_begin] / per;
+            a.chunk_end = (a.src_ent0[a.src_end] + per - 1) / per;
+            st.kind = S_CONV_S4; continue;
+        }
+        if ((a.Win & 3) != 0) {
+            if (st.need) return fail(PF_EUNSUPPORTED, "fused conv on a width that is not a multiple of 4");
+            a.wpk = p->dev_weights + cp.wpk_off; a.nchunks = cp.tiling.nchunks;
+            st.kind = S_CONV_GENERIC; continue;
+        }
+        auto use = [&](size_t wpk_off, int nchunks, int kc) {   // a packing of the weights in chunks of kc input channels
+            a.wpk = p->dev_weights + wpk_off;
+            a.nchunks = nchunks;
+            a.src_chunk0[0] = 0;
+            for (int j = 0; j < kConvMaxSrc; ++j)
+                a.src_chunk0[j + 1] = a.src_chunk0[j] + (j < a.n_src ? ((int)o.src[j].ch + kc - 1) / kc : 0);
+            a.chunk_begin = a.src_chunk0[a.src_begin];
+            a.chunk_end = a.src_chunk0[a.src_end];
+        };
+        ConvChoice &ch = st.ch;
+        if (ch.kind == 4) {
+            use(cp.split_off, cp.split_chunks, o.k == 1 ? 32 : 8);
+            a.acc_scale = cp.split_acc_scale;
+            st.kind = o.k == 1 ? S_CONV_SPLIT1 : S_CONV_SPLIT;
+            if (o.k == 1 ? conv_split1_supported(a, ch.p0) : conv_split_supported(a)) continue;
+            ch = ConvChoice{1, 0, 0, 0};
+        }
+        if (ch.kind == 2) {
+            use(cp.wave_off, cp.wave_chunks, wave_kc((int)o.k));
+            ch.p1 = ch.p1 < a.ntiles ? ch.p1 : a.ntiles;
+            st.kind = S_CONV_WAVE;
+            if (conv_wave_supported(a, (int)o.k, ch.p0, ch.p1, ch.p2)) continue;
+            ch = ConvChoice{1, 0, 0, 0};   // shape not built: conv_dma with its cost model
+        }
+        use(cp.tiled_off, cp.tiled_chunks, dma_kc((int)o.k, (int)o.stride));
+        st.kind = S_CONV_DMA;
+        // the trailing rem_count output channels of a big image go to the vector ALU instead of an MFMA tile
+        // (conv_dma WM=4 shapes only, forced or cost-model-chosen)
+        int wm, nt;
+        if (p->opt_valu_rem && cp.rem_off && !st.need && !a.dst_fmt && a.src_begin == 0 && a.src_end == a.n_src && (ch.p0 == 0 || ch.p0 == 4)) {
+            ConvArgs r = a;
+            r.rem = cp.rem_count;
+            r.wrem = p->dev_weights + cp.rem_off;
+            r.ntiles = ((int)o.cout - r.rem) / 16;
+            if (conv_dma_supported(r, (int)o.k, (int)o.stride, B, 4, ch.p0 == 4 && ch.p1 > 0 ? ch.p1 : 0, p->opt_table_batch, &wm, &nt)) {
+                a = r;
+                ch = ConvChoice{1, wm, nt, 0};
+                continue;
             }
         }
-        // a tensor nobody reads as S4 (network outputs tapped by the caller) stays fp32
-        std::vector<uint8_t> read_s4(nT, 0);
-        for (const ConvRec &r : recs)
-            for (int j = r.sb; j < r.se; ++j) read_s4[r.src_t[j]] = 1;
-        for (size_t t = 0; t < nT; ++t) fmt[t] = cand[t] && read_s4[t];
-        p->last_fmt = fmt;
+        conv_dma_supported(a, (int)o.k, (int)o.stride, B, ch.p0, ch.p1, p->opt_table_batch, &wm, &nt);   // (no kernel: the launcher says so)
+        ch = ConvChoice{1, wm, nt, 0};
     }
+
+    // ---- 5. an odd HarDBlock layer inside its consumer (conv_pair.hip): two adjacent steps P = op i, C = op i + 1 that both read
+    //      and write packed pairs become one
+    size_t w = 0;
+    for (size_t k = 0; k < steps.size(); ++k, ++w) {
+        const size_t i = (size_t)steps[k].op;
+        // (reading S4 implies a width % 4 == 0 and no forced kernel but conv_s4)
+        const bool pair = p->opt_fuse_pairs && k + 1 < steps.size() && steps[k].kind == S_CONV_S4 && steps[k + 1].kind == S_CONV_S4 &&
+                          steps[k + 1].op == (int)i + 1 && is_conv_pair(p, i) && p->conv[i + 1].has_pair && steps[k].u.c.dst_fmt && steps[k + 1].u.c.dst_fmt;
+        const BlobOp &o = p->ops[i];
+        if (!pair || !pair_wanted((int)o.cin, (int)o.cout, (int)p->ops[i + 1].cin, (int)p->ops[i + 1].cout, d[o.dst].h, d[o.dst].w, Bt,
+                                  p->opt_fuse_pairs)) {
+            if (w != k) steps[w] = steps[k];
+            continue;
+        }
+        // the consumer's S4 launch (pa.c) with its sources in the K order [S, others.., P]: source j of the launch = source (j + 1) % n
+        // of the op
+        const BlobOp &C = p->ops[i + 1];
+        Step st = steps[k + 1];
+        st.kind = S_PAIR; st.op = (int)i;
+        if (tags)
+            snprintf(st.tag, sizeof(st.tag), "%02zu+%02zu %s+%s %u->%u->%u %dx%d", i, i + 1, p->tensors[o.dst].name, p->tensors[C.dst].name, o.cin,
+                     o.cout, C.cout, d[o.dst].h, d[o.dst].w);
+        PairArgs &pa = st.u.pair;
+        ConvArgs &a = pa.c;
+        const int n = (int)C.n_src;
+        int e = 0;
+        for (int j = 0; j < n; ++j) {
+            const BlobSrc &sj = C.src[(j + 1) % n];
+            const bool isP = j == n - 1;
+            a.src[j] = tptr(sj.tensor);
+            a.src_ctotal[j] = (int)p->tensors[sj.tensor].channels;
+            a.src_choff[j] = (int)sj.choff;
+            a.src_c4[j] = (a.src_ctotal[j] + 3) / 4;
+            a.src_g0[j] = isP ? 0 : (int)sj.choff / 4;
+            a.src_gn[j] = isP ? ((int)sj.ch + 3) / 4 : ((int)sj.choff + (int)sj.ch + 3) / 4 - (int)sj.choff / 4;
+            a.src_ent0[j] = e;
+            e += (a.src_gn[j] + 1) / 2 * 2;
+        }
+        for (int j = n; j <= kConvMaxSrc; ++j) a.src_ent0[j] = e;
+        a.chunk_begin = a.chunk_end = 0;
+        a.wpk = p->dev_weights + p->conv[i + 1].pair_c_off; a.nchunks = p->conv[i + 1].pair_rounds;
+        pa.p_wpk = p->dev_weights + p->conv[i + 1].pair_two_off; pa.p_w9 = p->dev_weights + p->conv[i + 1].pair_nine_off;
+        pa.p_bias = p->dev_weights + p->conv[i].bias_off; pa.p_acc_scale = p->conv[i].split_acc_scale;
+        pa.p_dst = tptr(o.dst); pa.p_dst_c4 = ((int)p->tensors[o.dst].channels + 3) / 4;
+        pa.p_dst_choff = (int)o.dst_choff; pa.p_dst_limit = steps[k].u.c.dst_limit;
+        pa.p_cout = (int)o.cout; pa.p_cin = (int)o.cin; pa.p_ntiles = ((int)o.cout + 15) / 16; pa.p_relu = (int)o.relu;
+        pa.p_range_slot = slot_of(i, o.dst);
+        pa.rounds_s = a.src_ent0[1] / 2; pa.round_d = a.src_ent0[n - 1] / 2;
+        pa.merged = p->conv[i + 1].pair_merged && p->opt_fuse_pairs != 3;
+        steps[w] = st;
+        ++k;
     }
-    if (tag_ops) prof_set_tag(nullptr);
+    steps.resize(w);
+    return PF_OK;
+}
+
+int run_net(const pf_plan *p, const StemArgs *stem, const float *dense_x, int B, int H, int W, int out_h, int out_w,
+            void *out_seg, int out_seg_is_i64, float *out_logits, float *out_orig, void *ws, size_t ws_bytes,
+            hipStream_t s) {
+    std::vector<Step> steps;   // (per call: no state kept across forwards)
+    std::vector<uint8_t> fmt;
+    int rc = build_schedule(p, stem, dense_x, B, H, W, out_h, out_w, out_seg, out_seg_is_i64, out_logits, out_orig, ws, ws_bytes, steps, fmt);
+    if (rc) return rc;
+    p->last_fmt = fmt;
+    static const bool sync_ops = ab_env("PF_SYNC_OPS") != nullptr;   // debugging: localise a faulting launch
+    static const bool probe_on = ab_env("PF_PROBE") != nullptr;      // read once, not per forward
+    long long *const probe = probe_on ? probe_buffer() : nullptr;
+    for (size_t k = 0; k < steps.size(); ++k) {
+        Step &st = steps[k];
+        if (sync_ops && (k == 0 || steps[k - 1].op != st.op))
+            fprintf(stderr, "[pf] before op %d (%s): %s\n", st.op, p->tensors[p->ops[st.op].dst].name, hipGetErrorString(hipStreamSynchronize(s)));
+        else if (sync_ops && is_conv_step(steps[k - 1].kind) && steps[k - 1].u.c.no_bias)
+            fprintf(stderr, "[pf]   low-resolution half: %s\n", hipGetErrorString(hipStreamSynchronize(s)));
+        if (st.tag[0]) prof_set_tag(st.tag);
+        const BlobOp &o = p->ops[st.ci];
+        ConvArgs &a = st.u.c;   // (the conv kinds)
+        const PlainArgs &x = st.u.x;
+        if (is_conv_step(st.kind)) a.probe = probe;
+        switch (st.kind) {
+            case S_RANGE_CHECK: rc = launch_range_check(x.src, x.n, x.status, x.slot, s); break;
+            case S_STEM: st.u.sf.stem.probe = probe; rc = launch_stem(st.u.sf.stem, s); break;
+            case S_STEM_FRONT:   // (conv_front under a label of its own)
+                if ((rc = launch_stem(st.u.sf.stem, s))) break;
+                if (st.u.sf.front_tag[0]) prof_set_tag(st.u.sf.front_tag);
+                st.u.sf.front.probe = probe; rc = launch_conv_front(st.u.sf.front, B, s); break;
+            case S_PAIR: st.u.pair.c.probe = probe; rc = launch_conv_pair(st.u.pair, B, s); break;
+            case S_CONV_S4: rc = launch_conv_s4(a, (int)o.k, st.nt, st.wide, B, s); break;
+            case S_CONV_GENERIC: rc = launch_conv(a, p->conv[st.ci].tiling, B, s); break;
+            case S_CONV_SPLIT: rc = launch_conv_split(a, st.ch.p0, st.ch.p1, B, s); break;
+            case S_CONV_SPLIT1: rc = launch_conv_split1(a, st.ch.p0, B, s); break;
+            case S_CONV_WAVE: rc = launch_conv_wave(a, (int)o.k, st.ch.p0, st.ch.p1, st.ch.p2, B, s); break;
+            case S_CONV_DMA: rc = launch_conv_dma(a, (int)o.k, (int)o.stride, B, s, st.ch.p0, st.ch.p1, p->opt_table_batch); break;
+            case S_POOL: rc = launch_avgpool2(x.src, x.dst, x.planes, x.hin, x.win, x.status, x.slot, s); break;
+            case S_UPSAMPLE: rc = launch_upsample(x.src, x.dst, x.planes, x.hin, x.win, x.hout, x.wout, x.status, x.slot, s); break;
+            case S_HEAD:
+                if (st.u.head.orig && (rc = launch_copy(st.u.head.orig, st.u.head.h.logits, st.u.head.orig_bytes, s))) break;
+                rc = launch_head(st.u.head.h, s); break;
+            case S_CONV: break;   // (never left in a schedule)
+        }
+        if (rc) return rc;
+    }
+    if (p->opt_tag_ops != 0 || g_opt_tag_ops != 0) prof_set_tag(nullptr);
     // the dense input's slot is the last word of the block: the finalizer scans all of it (unused slots stay 0)
-    return launch_range_finalize(st_words, kLiveWord, kSlot0, kMaxSlots, kStickyWord, s);
+    return launch_range_finalize(reinterpret_cast<unsigned *>(ws), kLiveWord, kSlot0, kMaxSlots, kStickyWord, s);
 }
 
 }  // namespace

@@ -217,7 +217,11 @@ def test_execution_options_do_not_change_the_result(opts):
         m = _model(h, w)
         inp = synth.make_bg_inputs(b=2, h=h, w=w, seed=21)
         ref = hardnet_ref.bg_predict(_sd(), inp, final_size=(h, w))
+        # a successful forward leaves pf_last_error alone (no kernel is tried and then replaced by another one)
+        assert L.pf_set_option(b'no_such_option', 1) == -1
+        before = L.pf_last_error()
         out = m.predict({k: v.cuda() for k, v in inp.items()}, None)
+        assert L.pf_last_error() == before, L.pf_last_error()
         assert (out['orig_size_logits'].cpu() - ref['orig_size_logits']).abs().max() <= LOGIT_TOL
         assert (out['seg'].cpu() == ref['seg']).float().mean() >= AGREE
     finally:

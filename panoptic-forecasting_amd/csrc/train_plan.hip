@@ -13,10 +13,14 @@
 //     without       :  bias[cout]                                                          (finalConv, hardnet.py:325-327)
 //
 // Convolutions run on the fp32 matrix cores: forward and backward-data through the LDS-DMA kernels of the inference path
-// (conv_dma.hip; the generic implicit-GEMM kernel of conv_mfma.hip for widths that are not a multiple of 4) with the
-// weights re-packed on the device every step (forward order, or transposed + flipped per input range; stride-2
-// backward-data = stride-1 conv over the zero-stuffed gradient; a tensor's gradient accumulates over its consumers in
-// the store), backward-weight through the LDS-tiled wgrad kernels of train_kernels.hip.
+// (conv_dma.hip; widths that are not a multiple of 4 on copies with padded rows) with the weights re-packed on the device
+// every step (forward order, or transposed + flipped per input range; stride-2 backward-data = stride-1 conv over the
+// zero-stuffed gradient; a tensor's gradient accumulates over its consumers in the store), backward-weight through the
+// LDS-tiled wgrad kernels of train_kernels.hip.
+//
+// A step = build_train_schedule (host code only: the whole step as a flat list of TSteps, each naming exactly one kernel or
+// stream operation with all of its arguments; every kernel and shape is chosen there through predicates, so a geometry
+// without a kernel fails before anything is enqueued) + the enqueue loop of train_pass, a switch with one call per step.
 #include <algorithm>
 #include <array>
 #include <cstring>
@@ -45,7 +49,7 @@ struct pf_train {
     std::vector<size_t> w_off, aux_off;   // per op (floats into theta); aux = gamma (BN) or bias
     std::vector<int> bn;                  // per op: 1 = conv + BN (+ ReLU), 0 = plain conv with bias
     size_t n_params = 0;
-    float *dev_zero = nullptr;            // 1024 zeros (bias of the BN-less generic conv launches)
+    float *dev_zero = nullptr;            // 1024 zeros (the zero bias and zero page of the conv launches)
     // the weight gradients are leaves of the backward pass: they run on this plan's own lower-priority stream, forked from and
     // joined to the caller's stream inside every pf_train_forward_backward (so a stream capture of the call stays one graph).
     // Option "train_side_stream" (read when the plan is created; 0 = everything on the caller's stream)
@@ -63,11 +67,8 @@ struct pf_train {
     int fwd_s4 = 0;                       // option "train_forward_s4" when the plan was created: forward convolutions on conv_s4 (train_s4.hip)
     mutable std::map<std::array<int, 8>, std::pair<int, int>> tuned;   // (ks, stride, Cin, Cout, Hin, Win, B, accum) -> (wm, nt)
     mutable hipEvent_t tune_ev[2] = {nullptr, nullptr};
-    // the measurements run in a pass of their own in front of the first real pass of a configuration (B, H, W, out_h, out_w):
-    // its launches repeat, so what they accumulate is garbage - it goes to a scratch gradient and leaves theta alone
-    mutable bool measuring = false;
-    // pf_train_path_stats: which code paths the LAST pf_train_forward_backward took (tests assert that a timed configuration
-    // really ran the table's shapes and the padded odd-width forms, not a fallback)
+    // pf_train_path_stats: which code paths the LAST pf_train_forward_backward took, counted from its schedule (tests assert that
+    // a timed configuration really ran the table's shapes and the padded odd-width forms)
     mutable int stats[8] = {};
     mutable std::vector<std::array<int, 5>> measured_configs;
 };
@@ -89,68 +90,6 @@ struct TrainTuned {
 const TrainTuned kTrainTuned[] = {
 #include "train_tuned.inc"
     {{0, 0, 0, 0, 0, 0, 0, 0}, 0, 0}};
-
-// conv_dma with the measured shape for the geometry: this plan's own measurement (pf_train::autotune, measuring first if need
-// be), else the table's, else the cost model's
-int train_conv_dma(const pf_train *p, const ConvArgs &c0, int ks, int stride, int B, hipStream_t s) {
-    // blocked summation in the 3x3 convolutions of a training step (conv_dma.hip: KACC; option train_blocked_sum, on)
-    ConvArgs c = c0;
-    c.kacc = (g_opt_train_kacc && ks == 3) ? 1 : 0;
-    const std::array<int, 8> key{ks, stride, c.Cin, c.Cout, c.Hin, c.Win, B, c.accum};
-    auto it = p->autotune ? p->tuned.find(key) : p->tuned.end();
-    if (it == p->tuned.end() && !p->measuring) {
-        if (g_opt_use_tuned) {
-            // option "train_table_batch" = n > 0: look the table up as if the batch were n (the rows are keyed on the batch they
-            // were measured at; a parity test of the timed configuration's kernels on a batch the CPU oracle can afford pins n = 8)
-            std::array<int, 8> tkey = key;
-            if (g_opt_train_table_batch > 0) tkey[6] = g_opt_train_table_batch;
-            for (const TrainTuned &t : kTrainTuned)
-                if (t.wm && std::equal(tkey.begin(), tkey.end(), t.key)) {
-                    const int rc = launch_conv_dma(c, ks, stride, B, s, t.wm, t.nt);
-                    if (rc != PF_EUNSUPPORTED) {
-                        ++p->stats[0];
-                        return rc;
-                    }
-                    break;      // a row this build has no kernel for: the cost model's shape
-                }
-        }
-        ++p->stats[1];
-        return launch_conv_dma(c, ks, stride, B, s);
-    }
-    if (it == p->tuned.end()) {
-        if (!p->tune_ev[0] && (hipEventCreate(&p->tune_ev[0]) != hipSuccess || hipEventCreate(&p->tune_ev[1]) != hipSuccess))
-            return fail(PF_EHIP, "autotune: hipEventCreate failed");
-        // candidate (0, 0) = the cost model's own choice: measured first, kept unless a forced shape is at least 3 % faster
-        float model_ms = 0.f, best = 1e30f;
-        std::pair<int, int> pick{0, 0};
-        const int wms[4] = {0, 4, 2, 1};
-        for (int wi = 0; wi < 4; ++wi) {
-            const int wm = wms[wi], ntmax = wm == 0 ? 1 : (wm == 1 ? 2 : 4);
-            for (int nt = 1; nt <= ntmax && (wm == 0 || nt <= c.ntiles); ++nt) {
-                int rc = PF_OK;
-                for (int rep = 0; rep < 4 && rc == PF_OK; ++rep) {      // 1 warm-up + 3 timed
-                    if (rep == 1) PF_HIP_CHECK(hipEventRecord(p->tune_ev[0], s));
-                    rc = wm ? launch_conv_dma(c, ks, stride, B, s, wm, nt) : launch_conv_dma(c, ks, stride, B, s);
-                }
-                if (rc == PF_EUNSUPPORTED && wm) continue;
-                if (rc) return rc;
-                PF_HIP_CHECK(hipEventRecord(p->tune_ev[1], s));
-                PF_HIP_CHECK(hipEventSynchronize(p->tune_ev[1]));
-                float ms = 0.f;
-                PF_HIP_CHECK(hipEventElapsedTime(&ms, p->tune_ev[0], p->tune_ev[1]));
-                if (!wm) model_ms = ms;
-                else if (ms < best) {
-                    best = ms;
-                    pick = {wm, nt};
-                }
-            }
-        }
-        if (!(best < 0.97f * model_ms)) pick = {0, 0};
-        it = p->tuned.emplace(key, pick).first;
-    }
-    ++p->stats[2];
-    return it->second.first ? launch_conv_dma(c, ks, stride, B, s, it->second.first, it->second.second) : launch_conv_dma(c, ks, stride, B, s);
-}
 
 struct TDims {
     int h = 0, w = 0;
@@ -234,8 +173,11 @@ GradFirst grad_first_writers(const pf_train *p, const std::vector<TDims> &d) {
 struct TLayout {
     std::vector<size_t> act, grad;     // per tensor (bytes); act[input] = the dense one-hot/depth tensor
     std::vector<size_t> ypre, stat;    // per op: pre-BN conv output, {mean[cout], invstd[cout]}
-    std::vector<size_t> xpad;          // per op of an odd-width level: its gathered, row-padded input, kept from the forward pass for the weight gradient
-    size_t dy = 0, wpk = 0, wpart = 0, dfull = 0, cepart = 0, bnpart = 0, out3 = 0, total = 0;
+    // per conv op: stride 1 on a width that is not a multiple of 4 - its output keeps rows padded to 4 (ypre, dy), and ONE
+    // backward-data conv covers all its input ranges
+    std::vector<uint8_t> odd;
+    std::vector<size_t> xpad;          // per odd op: its gathered, row-padded input, kept from the forward pass for the weight gradient
+    size_t dy = 0, wpart = 0, dfull = 0, cepart = 0, bnpart = 0, out3 = 0, total = 0;
     size_t pad_in = 0, pad_out = 0;    // odd-width convs: gathered input / result with the row pitch rounded up to 4
     size_t dy_more[pf_train::kDySlots] = {}, wpart_more[pf_train::kSideStreams] = {};   // side streams: further dy slots, per stream the partial sums
     size_t up_tmp = 0;                 // scratch of the two-pass bilinear transpose
@@ -288,36 +230,24 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<TDims> &d, int out_
     for (size_t t = 0; t < nt; ++t)
         if (d[t].h && t != input) L.grad[t] = take(tbytes(t));
     L.grad_end = cur;
-    size_t max_dy = 0, max_wpk = 0, max_wpart = 0, max_c = 16, max_pin = 256, max_pout = 256;
+    L.odd.assign(p->ops.size(), 0);
+    size_t max_dy = 0, max_wpart = 0, max_c = 16, max_pin = 256, max_pout = 256;
     for (size_t i = 0; i < p->ops.size(); ++i) {
         const BlobOp &o = p->ops[i];
         if (o.kind != OP_STEM && o.kind != OP_CONV) continue;
         const TDims in = d[o.src[0].tensor], out = d[o.dst];
-        const size_t ybytes = (size_t)B * o.cout * out.h * out.w * sizeof(float);
+        L.odd[i] = (in.w & 3) && o.stride == 1;
+        // the conv output (y, dy) in padded rows on an odd level
+        const size_t ybytes = (size_t)B * o.cout * out.h * (L.odd[i] ? (out.w + 3) / 4 * 4 : out.w) * sizeof(float);
         if (p->bn[i]) {
-            // (odd width, stride 1: y keeps the tiled kernel's padded rows)
-            L.ypre[i] = take((in.w & 3) && o.stride == 1 ? (size_t)B * o.cout * out.h * ((out.w + 3) / 4 * 4) * sizeof(float) : ybytes);
+            L.ypre[i] = take(ybytes);
             L.stat[i] = take(2 * (size_t)o.cout * sizeof(float));
         }
         // dy scratch: the conv-output gradient, and (stride 2) its zero-stuffed copy at the input resolution
         size_t need = ybytes;
-        if ((in.w & 3) && o.stride == 1) need = (size_t)B * o.cout * out.h * ((out.w + 3) / 4 * 4) * sizeof(float);   // written with padded rows
         if (o.stride == 2) need += align_up((size_t)B * o.cout * in.h * in.w * sizeof(float), 256);
         max_dy = need > max_dy ? need : max_dy;
-        const ConvTiling tf = choose_tiling((int)o.k, (int)o.stride, (int)o.cin, (int)o.cout, 0);
-        max_wpk = tf.packed_floats() > max_wpk ? tf.packed_floats() : max_wpk;
-        int src_ch[kMaxSrc];
-        for (uint32_t j = 0; j < o.n_src; ++j) src_ch[j] = (int)o.src[j].ch;
-        size_t tp = tiled_packed_floats(src_ch, (int)o.n_src, (int)o.cout, (int)o.k, (int)o.stride);
-        max_wpk = tp > max_wpk ? tp : max_wpk;
-        for (uint32_t j = 0; j < o.n_src; ++j) {
-            const ConvTiling tb = choose_tiling((int)o.k, 1, (int)o.cout, (int)o.src[j].ch, 0);
-            max_wpk = tb.packed_floats() > max_wpk ? tb.packed_floats() : max_wpk;
-            const int one = (int)o.cout;
-            tp = tiled_packed_floats(&one, 1, (int)o.src[j].ch, (int)o.k, 1);
-            max_wpk = tp > max_wpk ? tp : max_wpk;
-        }
-        if ((in.w & 3) && o.stride == 1) L.xpad[i] = take((size_t)B * o.cin * in.h * ((in.w + 3) / 4 * 4) * sizeof(float));
+        if (L.odd[i]) L.xpad[i] = take((size_t)B * o.cin * in.h * ((in.w + 3) / 4 * 4) * sizeof(float));
         if (in.w & 3) {     // padded copies (forward: cin -> cout at the output size; backward-data: cout -> cin at the input size)
             const size_t wp_in = (size_t)(in.w + 3) / 4 * 4, cmax = o.cin > o.cout ? o.cin : o.cout;
             const size_t bytes = (size_t)B * cmax * in.h * wp_in * sizeof(float);
@@ -331,7 +261,6 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<TDims> &d, int out_
     }
     // the step's packing jobs (the padded copies of odd-width levels read ONE gathered range)
     {
-        const uint32_t input_t = p->ops[0].src[0].tensor;
         L.fwd_job.assign(p->ops.size(), -1);
         L.bwd_job.assign(p->ops.size(), std::vector<int>());
         L.bwd_all_job.assign(p->ops.size(), -1);
@@ -359,12 +288,12 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<TDims> &d, int out_
             L.bwd_job[i].assign(o.n_src, -1);
             int c0 = 0;
             const int dy_ch = (int)o.cout;
-            if ((d[o.src[0].tensor].w & 3) && o.stride == 1) {
+            if (L.odd[i]) {
                 L.bwd_all_job[i] = add(p->w_off[i], (int)o.cin, (int)o.cout, (int)o.k, 1, &dy_ch, 1, 1, 0, (int)o.cin);
                 continue;
             }
             for (uint32_t j = 0; j < o.n_src; ++j) {
-                if (o.src[j].tensor != input_t) L.bwd_job[i][j] = add(p->w_off[i], (int)o.cin, (int)o.cout, (int)o.k, 1, &dy_ch, 1, 1, c0, (int)o.src[j].ch);
+                if (o.src[j].tensor != input) L.bwd_job[i][j] = add(p->w_off[i], (int)o.cin, (int)o.cout, (int)o.k, 1, &dy_ch, 1, 1, c0, (int)o.src[j].ch);
                 c0 += (int)o.src[j].ch;
             }
         }
@@ -397,10 +326,8 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<TDims> &d, int out_
     }
     if (p->autotune) L.tune_grad = take(p->n_params * sizeof(float));
     L.dy = take(max_dy + 256);
-    if (p->side) {
+    if (p->side)
         for (int k = 1; k < pf_train::kDySlots; ++k) L.dy_more[k] = take(max_dy + 256);
-    }
-    L.wpk = take(max_wpk * sizeof(float));
     L.wpart = take(max_wpart * sizeof(float));
     if (p->side)
         for (int k = 1; k < pf_train::kSideStreams; ++k) L.wpart_more[k] = take(max_wpart * sizeof(float));
@@ -584,22 +511,424 @@ extern "C" int pf_train_tensor_view(const pf_train *p, const char *name, int wan
     return fail(PF_EINVAL, "no tensor named '%s'", name);
 }
 
-static int train_pass(const pf_train *p, float *theta, float *grad, int accumulate_grads, const void *seg, int seg_is_i64,
-                      const float *depth, const uint8_t *depth_mask, float depth_mean, float depth_std, int T,
-                      const float *x_dense, int B, int H, int W, const void *labels, int labels_i64, int out_h, int out_w,
-                      int ignore_index, float loss_scale, float bn_momentum, float bn_eps, int update_running_stats,
-                      double *out3, void *ws, size_t ws_bytes, void *stream) {
-    if (!p || !theta || !grad || !labels || !out3 || !ws) return fail(PF_EINVAL, "pf_train_forward_backward: null pointer argument");
-    if (!x_dense && (!seg || !depth || !depth_mask)) return fail(PF_EINVAL, "pf_train_forward_backward: pass seg+depth+depth_mask or x_dense");
-    if (B <= 0 || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0) return fail(PF_EINVAL, "pf_train_forward_backward: bad dims");
-    hipStream_t s = (hipStream_t)stream;
+namespace {
+
+// the arguments of one pf_train_forward_backward
+struct TCall {
+    float *theta, *grad;
+    int accumulate_grads;
+    const void *seg; int seg_is_i64; const float *depth; const uint8_t *depth_mask; float depth_mean, depth_std; int T;
+    const float *x_dense; int B, H, W;
+    const void *labels; int labels_i64, out_h, out_w, ignore_index;
+    float loss_scale, bn_momentum, bn_eps; int update_running_stats;
+    double *out3; void *ws; size_t ws_bytes; hipStream_t s;
+};
+
+// ---- One step of the schedule: a kernel (its arguments in the member of `u` named after it, convolutions in `a`) or a stream
+//      operation of the side streams (fork = record ev_dy[slot] on the caller's stream + wait on the side stream; wg_done = record
+//      ev_wg[slot] on the side stream; wait_wg = the caller's stream waits for it before the slot is overwritten)
+enum TStepKind : uint8_t {
+    T_COPY, T_ONEHOT, T_PACK_TILED, T_PACK_S4, T_ZERO_CHANNELS, T_ZERO_FILL,
+    T_PAD_GATHER, T_CONV_DMA, T_CONV_DMA_MEASURE, T_CONV_S4, T_UNPAD, T_UNPAD_MULTI, T_BN_FWD, T_S4_ACT, T_POOL, T_UPSAMPLE, T_CE,
+    T_UPSAMPLE_BWD, T_POOL_BWD, T_BN_BWD, T_BIAS_BWD, T_ZERO_STUFF, T_WGRAD, T_WAIT_WG, T_FORK, T_WG_DONE };
+struct TCopyArgs { void *dst; const void *src; size_t bytes; };       // copy; zero fill (src unused)
+struct TOneHotArgs { const void *seg; int seg_i64; const float *depth; const uint8_t *mask; float mean, stdv; int T, n_cls, H, W; float *x; };
+struct TPackArgs { const float *theta; float *arena; const void *jobs; int n; };   // PackJob / S4WJob list
+struct TZeroChArgs { float *t; int ctotal, c0, n; long long hw; };
+struct TUnpadArgs { const float *src; int C, H, W, Wp; float *dst; int ctotal, choff, accum; };
+struct TUnpadMultiArgs { const float *src; int C, H, W, Wp, n; float *dst[kMaxSrc]; int ctotal[kMaxSrc], choff[kMaxSrc], ch[kMaxSrc], overwrite[kMaxSrc]; };
+struct TBnFwdArgs {
+    const float *y; int C, H, W; float eps, momentum; const float *gamma, *beta; float *rmean, *rvar, *mean, *invstd; double *part;
+    float *dst; int dst_ctotal, dst_choff, relu, y_pitch;
+};
+struct TS4ActArgs { const float *src; int ctotal, c0, c1, fill_lo, fill_up, H, W, Wp; void *dst; };
+// pool, upsample, zero-stuff: [planes][hin][win] -> [planes][hout][wout]; pool backward: dst (+)= from src, overwrite
+struct TPlainArgs { const float *src; float *dst; int planes, hin, win, hout, wout, overwrite; };
+struct TCeArgs { const float *logits; int C, hi, wi; const void *labels; int lab_i64, ho, wo, ignore; float *dfull; double *part, *out3; };
+struct TUpBwdArgs { const float *gout; int planes, hi, wi, ho, wo; const double *count; float scale; int accumulate; float *gin, *tmp; };
+struct TBnBwdArgs {      // (bias backward: g .. choff, C, H, W, dgamma = dbias, part, dy, dy_pitch)
+    const float *g; int t_ctotal, choff; const float *y, *mean, *invstd, *gamma, *beta; int C, H, W, relu; float *dgamma, *dbeta;
+    double *part; float *dy; int dy_pitch, y_pitch;
+};
+struct TWgradArgs { const float *dy; float *partial, *dw; };
+struct TStep {
+    TStepKind kind;
+    uint8_t stats;       // bit k: the step counts in pf_train_path_stats slot k
+    int side, slot;      // side stream of the step (-1: the caller's stream); the dy slot of fork / wait_wg / wg_done
+    ConvArgs a;          // conv_dma, conv_s4, pad_gather (the ranges it gathers), wgrad (the forward conv)
+    int ks, stride, wm, nt, wide;   // conv_dma: wm x nt (measure: chosen at enqueue); conv_s4: nt, wide; wgrad: ks, stride
+    int Wp;              // pad_gather: the pitch of the gathered copy and where it goes
+    float *gather;
+    char tag[64];        // wgrad: profile tag of its launches (set when profiling)
+    union {
+        TCopyArgs copy; TOneHotArgs onehot; TPackArgs pack; TZeroChArgs zch; TUnpadArgs unpad; TUnpadMultiArgs unpadm; TBnFwdArgs bnf;
+        TS4ActArgs s4act; TPlainArgs plain; TCeArgs ce; TUpBwdArgs upb; TBnBwdArgs bnb; TWgradArgs wg;
+    } u;
+};
+
+std::array<int, 8> tune_key(const ConvArgs &c, int ks, int stride, int B) { return {ks, stride, c.Cin, c.Cout, c.Hin, c.Win, B, c.accum}; }
+
+// pf_train_autotune, T_CONV_DMA_MEASURE: the workgroup shape of this geometry is measured unless an earlier conv of the pass did:
+// every candidate of conv_dma's shape list, 1 warm-up + 3 timed launches; candidate (0, 0) = the cost model's own choice, kept
+// unless a forced shape is at least 3 % faster.  Then the conv itself, with the shape kept
+int tune_conv_dma(const pf_train *p, const ConvArgs &c, int ks, int stride, int B, hipStream_t s) {
+    const std::array<int, 8> key = tune_key(c, ks, stride, B);
+    auto it = p->tuned.find(key);
+    if (it == p->tuned.end()) {
+        if (!p->tune_ev[0] && (hipEventCreate(&p->tune_ev[0]) != hipSuccess || hipEventCreate(&p->tune_ev[1]) != hipSuccess))
+            return fail(PF_EHIP, "autotune: hipEventCreate failed");
+        float model_ms = 0.f, best = 1e30f;
+        std::pair<int, int> pick{0, 0};
+        const int wms[4] = {0, 4, 2, 1};
+        for (int wi = 0; wi < 4; ++wi) {
+            const int wm = wms[wi], ntmax = wm == 0 ? 1 : (wm == 1 ? 2 : 4);
+            for (int nt = 1; nt <= ntmax && (wm == 0 || nt <= c.ntiles); ++nt) {
+                int swm, snt;
+                if (wm && !conv_dma_supported(c, ks, stride, B, wm, nt, 0, &swm, &snt)) continue;
+                for (int rep = 0; rep < 4; ++rep) {      // 1 warm-up + 3 timed
+                    if (rep == 1) PF_HIP_CHECK(hipEventRecord(p->tune_ev[0], s));
+                    const int rc = wm ? launch_conv_dma(c, ks, stride, B, s, wm, nt) : launch_conv_dma(c, ks, stride, B, s);
+                    if (rc) return rc;
+                }
+                PF_HIP_CHECK(hipEventRecord(p->tune_ev[1], s));
+                PF_HIP_CHECK(hipEventSynchronize(p->tune_ev[1]));
+                float ms = 0.f;
+                PF_HIP_CHECK(hipEventElapsedTime(&ms, p->tune_ev[0], p->tune_ev[1]));
+                if (!wm) model_ms = ms;
+                else if (ms < best) best = ms, pick = {wm, nt};
+            }
+        }
+        if (!(best < 0.97f * model_ms)) pick = {0, 0};
+        it = p->tuned.emplace(key, pick).first;
+    }
+    return it->second.first ? launch_conv_dma(c, ks, stride, B, s, it->second.first, it->second.second) : launch_conv_dma(c, ks, stride, B, s);
+}
+
+// conv `c` reading ONE source instead of its ranges: all `cin` channels of buffer x, rows of `win` pixels (the gathered copy of an
+// odd-width conv, the backward-data convs over dy)
+ConvArgs over_buffer(ConvArgs c, const float *x, int cin, int win, int wout) {
+    c.n_src = 1;
+    c.src[0] = x; c.src_ctotal[0] = cin; c.src_choff[0] = 0;
+    for (int k = 0; k <= kConvMaxSrc; ++k) c.src_cstart[k] = k ? cin : 0;
+    c.src_begin = 0; c.src_end = 1;
+    c.Cin = cin; c.Win = win; c.Wout = wout;
+    return c;
+}
+
+// The whole step (input, weight packings, gradient clears, forward, loss, backward) into `steps`, every argument resolved into
+// the call's theta, gradient and workspace.  Kernel choices are made here, through predicates: a geometry without a kernel
+// fails before anything is enqueued.  measuring: the autotune pass - a conv_dma geometry this plan has not measured is measured
+// at enqueue time (T_CONV_DMA_MEASURE)
+int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<TDims> &d, const TLayout &L, const GradFirst &gfirst,
+                         bool measuring, std::vector<TStep> &steps) {
+    // the options read per call
+    const int kacc = g_opt_train_kacc, use_tuned = g_opt_use_tuned, table_batch = g_opt_train_table_batch;
+    const bool tagged = prof_enabled();
+    const int B = k.B;
+    char *wsb = (char *)k.ws;
+    auto buf = [&](size_t off) { return reinterpret_cast<float *>(wsb + off); };
+    auto act = [&](uint32_t t) { return buf(L.act[t]); };
+    auto gradt = [&](uint32_t t) { return buf(L.grad[t]); };
+    const uint32_t input = p->ops[0].src[0].tensor;
+    const int in_ch = (int)p->tensors[input].channels, n_cls = (int)p->hdr.n_cls;
+    float *dy_slot[pf_train::kDySlots];
+    for (int j = 0; j < pf_train::kDySlots; ++j) dy_slot[j] = buf(p->side && j ? L.dy_more[j] : L.dy);
+    float *wpk_arena = buf(L.wpk_arena), *pad_in = buf(L.pad_in), *pad_out = buf(L.pad_out), *dfull = buf(L.dfull);
+    float *up_tmp = g_opt_up_two_pass ? buf(L.up_tmp) : nullptr;
+    double *cepart = reinterpret_cast<double *>(wsb + L.cepart), *bnpart = reinterpret_cast<double *>(wsb + L.bnpart);
+    double *loss3 = reinterpret_cast<double *>(wsb + L.out3);
+    steps.clear();
+    auto add = [&](TStepKind kind, uint8_t stats = 0, int side = -1, int slot = 0) -> TStep & {
+        TStep &st = steps.emplace_back();     // (zero-initialised)
+        st.kind = kind; st.stats = stats; st.side = side; st.slot = slot;
+        return st;
+    };
+    auto conv_args = [&](const BlobOp &o, const TDims &in, const TDims &out) {
+        ConvArgs a;
+        memset(&a, 0, sizeof(a));
+        a.n_src = (int)o.n_src;
+        int c0 = 0;
+        for (int j = 0; j < a.n_src; ++j) {
+            a.src[j] = act(o.src[j].tensor);
+            a.src_ctotal[j] = (int)p->tensors[o.src[j].tensor].channels;
+            a.src_choff[j] = (int)o.src[j].choff;
+            a.src_cstart[j] = c0;
+            c0 += (int)o.src[j].ch;
+        }
+        for (int j = a.n_src; j <= kConvMaxSrc; ++j) a.src_cstart[j] = c0;
+        a.bias = a.zero_page = p->dev_zero;
+        a.Cin = (int)o.cin; a.Cout = (int)o.cout; a.ntiles = ((int)o.cout + 15) / 16;
+        a.Hin = in.h; a.Win = in.w; a.Hout = out.h; a.Wout = out.w;
+        a.src_end = a.n_src;
+        return a;
+    };
+    // backward-data conv: `ch` gradient channels into dst from the cout_f channels of dy ([B][cout_f][h][w])
+    auto bwd_data_args = [&](const float *dy, int cout_f, int ch, int h, int w, float *dst, int dst_ctotal, int dst_choff, int accum) {
+        ConvArgs b;
+        memset(&b, 0, sizeof(b));
+        b.bias = b.zero_page = p->dev_zero;
+        b.dst = dst; b.dst_ctotal = dst_ctotal; b.dst_choff = dst_choff; b.accum = accum;
+        b.Cout = ch; b.Hin = h; b.Hout = h; b.ntiles = (ch + 15) / 16;
+        return over_buffer(b, dy, cout_f, w, w);
+    };
+    // conv_dma over c with the tiled packing `job` and the measured shape of its geometry (autotune), else the table's row, else
+    // the cost model's (path stats 2 / 0 / 1)
+    auto dma = [&](ConvArgs c, int ks, int stride, int job, uint8_t stats) -> int {
+        const PackJob &q = L.jobs[job];
+        if (q.n_src != c.n_src) return fail(PF_EUNSUPPORTED, "training: a conv reads %d ranges, its weight packing %d", c.n_src, q.n_src);
+        c.wpk = wpk_arena + q.out_off;
+        const int kc = dma_kc(ks, stride);
+        c.src_chunk0[0] = 0;
+        for (int j = 0; j < kConvMaxSrc; ++j)
+            c.src_chunk0[j + 1] = c.src_chunk0[j] + (j < c.n_src ? (c.src_cstart[j + 1] - c.src_cstart[j] + kc - 1) / kc : 0);
+        c.nchunks = c.chunk_end = c.src_chunk0[c.n_src]; c.chunk_begin = 0; c.rem = 0;
+        c.kacc = (kacc && ks == 3) ? 1 : 0;     // blocked summation in the 3x3 convolutions (conv_dma.hip: KACC; option train_blocked_sum)
+        const std::array<int, 8> key = tune_key(c, ks, stride, B);
+        int wm = 0, nt = 0, src = 1;
+        const auto it = p->autotune ? p->tuned.find(key) : p->tuned.end();
+        if (it != p->tuned.end()) {
+            wm = it->second.first, nt = it->second.second, src = 2;
+        } else if (measuring) {
+            src = 2;
+        } else if (use_tuned) {
+            // option "train_table_batch" = n > 0: look the table up as if the batch were n (the rows are keyed on the batch they
+            // were measured at; a parity test of the timed configuration's kernels on a batch the CPU oracle can afford pins n = 8)
+            std::array<int, 8> tkey = key;
+            if (table_batch > 0) tkey[6] = table_batch;
+            for (const TrainTuned &t : kTrainTuned)
+                if (t.wm && std::equal(tkey.begin(), tkey.end(), t.key)) {
+                    wm = t.wm, nt = t.nt, src = 0;
+                    break;
+                }
+        }
+        TStep &st = add(src == 2 && it == p->tuned.end() ? T_CONV_DMA_MEASURE : T_CONV_DMA, stats | (uint8_t)(1u << src));
+        st.a = c; st.ks = ks; st.stride = stride;
+        if (st.kind == T_CONV_DMA && !conv_dma_supported(c, ks, stride, B, wm, nt, 0, &st.wm, &st.nt))
+            return fail(PF_EUNSUPPORTED, "training: conv_dma has no kernel for ks=%d stride=%d wm=%d nt=%d", ks, stride, st.wm, st.nt);
+        return PF_OK;
+    };
+    // the gathered, row-padded copy of the input ranges of `a` (path stats 3; 4: the conv keeps its output in padded rows)
+    auto pad_gather = [&](const ConvArgs &a, int Wp, float *to, bool keep_padded) {
+        TStep &st = add(T_PAD_GATHER, keep_padded ? 0x18 : 0x08);
+        st.a = a; st.Wp = Wp; st.gather = to;
+    };
+    // one convolution on conv_dma.  Odd width: the same kernel on the input ranges gathered into `gather` with rows padded to a
+    // multiple of 4; the output left in padded rows at a.dst (keep_padded: the BatchNorm kernels read that pitch) or scattered
+    // back from pad_out
+    auto conv = [&](const ConvArgs &a, int ks, int stride, int job, float *gather, bool keep_padded) -> int {
+        if ((a.Win & 3) == 0) return dma(a, ks, stride, job, 0);
+        const int Wp = (a.Win + 3) / 4 * 4, Wop = (Wp + 2 * (ks / 2) - ks) / stride + 1;
+        pad_gather(a, Wp, gather, keep_padded);
+        ConvArgs c = over_buffer(a, gather, a.Cin, Wp, Wop);
+        c.dst = keep_padded ? a.dst : pad_out; c.dst_ctotal = a.Cout; c.dst_choff = 0; c.accum = 0;
+        const int rc = dma(c, ks, stride, job, 0);
+        if (rc || keep_padded) return rc;
+        add(T_UNPAD).u.unpad = {pad_out, a.Cout, a.Hout, a.Wout, Wop, a.dst, a.dst_ctotal, a.dst_choff, a.accum};
+        return PF_OK;
+    };
+    // the packed-pair shadow of channels [c0, c1) of tensor t, for the convolutions that read it through conv_s4
+    // (a slice that starts or ends in the middle of a 4-channel group also zero-fills the group's other half while no producer has
+    //  written it in this pass: a reader of this slice multiplies those channels by zero weights, and 0 x a stale NaN pattern is NaN)
+    std::vector<std::vector<char>> s4_written(p->tensors.size());
+    auto shadow = [&](uint32_t t, int c0, int c1) {
+        if (L.s4act[t] == (size_t)-1) return;
+        const int ct = (int)p->tensors[t].channels;
+        std::vector<char> &wr = s4_written[t];
+        if (wr.empty()) wr.assign((size_t)ct + 4, 0);
+        const int fill_lo = (c0 & 2) && !wr[c0 - 2], fill_up = (c1 & 3) == 2 && c1 < ct && !wr[c1];
+        for (int c = c0; c < c1; ++c) wr[c] = 1;
+        add(T_S4_ACT).u.s4act = {act(t), ct, c0, c1, fill_lo, fill_up, d[t].h, d[t].w, (d[t].w + 3) / 4 * 4, wsb + L.s4act[t]};
+    };
+    int rc;
+
+    // ---- input tensor (bg_model.py:61-69), weight packings (theta does not move inside this call), gradient clears
+    if (k.x_dense) {
+        add(T_COPY).u.copy = {act(input), k.x_dense, (size_t)B * in_ch * k.H * k.W * sizeof(float)};
+    } else {
+        if (k.T * (n_cls + 1) != in_ch) return fail(PF_EINVAL, "T=%d frames x (%d classes + depth) != %d input channels", k.T, n_cls, in_ch);
+        add(T_ONEHOT).u.onehot = {k.seg, k.seg_is_i64, k.depth, k.depth_mask, k.depth_mean, k.depth_std, k.T, n_cls, k.H, k.W, act(input)};
+    }
+    add(T_PACK_TILED).u.pack = {k.theta, wpk_arena, L.jobs.data(), (int)L.jobs.size()};
+    if (!L.s4jobs.empty()) add(T_PACK_S4).u.pack = {k.theta, buf(L.s4w_arena), L.s4jobs.data(), (int)L.s4jobs.size()};
+    for (const auto &c : gfirst.clear)     // (no cleared gradient arena: first writers store)
+        add(T_ZERO_CHANNELS).u.zch = {gradt((uint32_t)c[0]), (int)p->tensors[c[0]].channels, c[1], c[2], (long long)d[c[0]].h * d[c[0]].w};
+    if (!k.accumulate_grads) add(T_ZERO_FILL).u.copy = {k.grad, nullptr, p->n_params * sizeof(float)};
+
+    // ================================================================ forward (training mode)
+    for (size_t i = 0; i < p->ops.size(); ++i) {
+        const BlobOp &o = p->ops[i];
+        const TDims in = d[o.src[0].tensor];
+        const TDims out = o.kind == OP_HEAD ? in : d[o.dst];
+        if (o.kind == OP_STEM || o.kind == OP_CONV) {
+            ConvArgs a = conv_args(o, in, out);
+            float *gather = L.odd[i] ? buf(L.xpad[i]) : pad_in;     // (an odd op keeps its copy for the weight gradient)
+            const int Wp = (in.w + 3) / 4 * 4;
+            if (!p->bn[i]) {
+                a.bias = k.theta + p->aux_off[i];
+                a.dst = act(o.dst); a.dst_ctotal = (int)p->tensors[o.dst].channels; a.dst_choff = (int)o.dst_choff; a.relu = (int)o.relu;
+                if ((rc = conv(a, (int)o.k, (int)o.stride, L.fwd_job[i], gather, false))) return rc;
+                shadow(o.dst, (int)o.dst_choff, (int)o.dst_choff + (int)o.cout);
+                continue;
+            }
+            float *y = buf(L.ypre[i]);
+            a.dst = y; a.dst_ctotal = (int)o.cout; a.dst_choff = 0; a.relu = 0;
+            if (L.s4_job[i] < 0) {
+                if ((rc = conv(a, (int)o.k, (int)o.stride, L.fwd_job[i], gather, L.odd[i]))) return rc;
+            } else {
+                // train_s4.hip: conv_s4 on the shadows of the input ranges; y in fp32 (rows padded to 4 on an odd-width level, as
+                // the tiled fp32 path leaves them).  The weight gradient of an odd-width layer still reads the gathered, row-padded
+                // fp32 copy of x
+                const S4WJob &jb = L.s4jobs[L.s4_job[i]];
+                const int per = o.k == 3 ? 2 : 8;
+                if (L.odd[i]) pad_gather(a, Wp, gather, true);
+                ConvArgs c = a;
+                int e = 0;
+                for (int j = 0; j < c.n_src; ++j) {
+                    const int ch0 = (int)o.src[j].choff, chn = (int)o.src[j].ch;
+                    c.src[j] = buf(L.s4act[o.src[j].tensor]);
+                    c.src_c4[j] = (c.src_ctotal[j] + 3) / 4;
+                    c.src_g0[j] = ch0 / 4;
+                    c.src_gn[j] = (ch0 + chn + 3) / 4 - ch0 / 4;
+                    c.src_ent0[j] = e;
+                    e += jb.pad ? (c.src_gn[j] + per - 1) / per * per : c.src_gn[j];
+                }
+                for (int j = c.n_src; j <= kConvMaxSrc; ++j) c.src_ent0[j] = e;
+                c.src_fmt = 1; c.dst_fmt = 0; c.src_begin = 0;
+                c.Win = Wp; c.Wout = Wp;
+                c.acc_scale = 1.0f / (kS4TrainWeightScale * kS4TrainActScale);
+                c.wpk = buf(L.s4w_arena) + jb.out_off;
+                c.nchunks = c.chunk_end = jb.rounds; c.chunk_begin = 0;
+                c.kacc = (kacc && o.k == 3) ? 1 : 0;      // blocked summation, as in the fp32 step (conv_s4_kernel.inc: KACC)
+                TStep &st = add(T_CONV_S4, 0x80);
+                st.a = c; st.ks = (int)o.k;
+                st.nt = c.ntiles == 3 ? 3 : (c.ntiles < 2 ? 1 : 2);
+                ConvChoice ch4;
+                if (use_tuned && choose_s4((int)o.k, c.Cin, c.Cout, c.Hout, c.Wout, B, &ch4) && ch4.kind == 5) { st.nt = ch4.p0; st.wide = ch4.p1; }
+            }
+            float *aux = k.theta + p->aux_off[i], *stat = buf(L.stat[i]);
+            add(T_BN_FWD).u.bnf = {y, (int)o.cout, out.h, out.w, k.bn_eps, k.bn_momentum, aux, aux + o.cout,
+                                   k.update_running_stats ? aux + 2 * o.cout : nullptr, k.update_running_stats ? aux + 3 * o.cout : nullptr,
+                                   stat, stat + o.cout, bnpart, act(o.dst), (int)p->tensors[o.dst].channels, (int)o.dst_choff, (int)o.relu,
+                                   L.odd[i] ? (out.w + 3) / 4 * 4 : 0};
+            shadow(o.dst, (int)o.dst_choff, (int)o.dst_choff + (int)o.cout);
+        } else if (o.kind == OP_POOL) {
+            add(T_POOL).u.plain = {act(o.src[0].tensor), act(o.dst), B * (int)o.cin, in.h, in.w, 0, 0, 0};
+            shadow(o.dst, 0, (int)p->tensors[o.dst].channels);
+        } else if (o.kind == OP_UPSAMPLE) {
+            add(T_UPSAMPLE).u.plain = {act(o.src[0].tensor), act(o.dst), B * (int)o.cin, in.h, in.w, out.h, out.w, 0};
+            shadow(o.dst, 0, (int)p->tensors[o.dst].channels);
+        } else if (o.kind == OP_HEAD) {
+            add(T_CE).u.ce = {act(o.src[0].tensor), (int)o.cin, in.h, in.w, k.labels, k.labels_i64, k.out_h, k.out_w, k.ignore_index, dfull, cepart, loss3};
+            add(T_COPY).u.copy = {k.out3, loss3, 3 * sizeof(double)};
+        }
+    }
+
+    // ================================================================ backward
+    // With the side streams: layer n's conv-output gradient goes to dy slot n % kDySlots; the weight gradient (and its padded
+    // copy of x) reads it on side stream n % kSideStreams while the caller's stream goes on to the input gradients and the next
+    // layers; before it overwrites a slot it waits for the weight gradient of layer n - kDySlots that last read it.
+    int n_conv = 0;
+    for (size_t ii = p->ops.size(); ii-- > 0;) {
+        const BlobOp &o = p->ops[ii];
+        const TDims in = d[o.src[0].tensor];
+        const TDims out = o.kind == OP_HEAD ? in : d[o.dst];
+        const int store = gfirst.store[ii][0];
+        if (o.kind == OP_HEAD) {
+            // d loss / d logits = bilinear^T (softmax - onehot) * loss_scale / n_valid   (mean over the valid pixels, bg_model.py:81)
+            add(T_UPSAMPLE_BWD).u.upb = {dfull, B * (int)o.cin, in.h, in.w, k.out_h, k.out_w, loss3 + 1, k.loss_scale, !store, gradt(o.src[0].tensor), up_tmp};
+        } else if (o.kind == OP_POOL) {
+            add(T_POOL_BWD).u.plain = {gradt(o.dst), gradt(o.src[0].tensor), B * (int)o.cin, in.h, in.w, 0, 0, store};
+        } else if (o.kind == OP_UPSAMPLE) {
+            add(T_UPSAMPLE_BWD).u.upb = {gradt(o.dst), B * (int)o.cin, in.h, in.w, out.h, out.w, nullptr, 1.f, !store, gradt(o.src[0].tensor), up_tmp};
+        } else if (o.kind == OP_STEM || o.kind == OP_CONV) {
+            if (!p->bn[ii] && o.relu) return fail(PF_EUNSUPPORTED, "training: ReLU without BatchNorm (op %zu)", ii);
+            const int t_ctotal = (int)p->tensors[o.dst].channels;
+            float *aux = k.theta + p->aux_off[ii], *gaux = k.grad + p->aux_off[ii];
+            const int slot = n_conv % pf_train::kDySlots, sidx = n_conv % pf_train::kSideStreams;
+            float *dy = dy_slot[slot];
+            // odd-width levels: dy goes out with its rows padded to a multiple of 4 floats and zero pad columns - the form the
+            // tiled weight-gradient and backward-data kernels read - and ONE backward-data conv covers all input ranges
+            const bool odd = L.odd[ii];
+            const int Wp = (in.w + 3) / 4 * 4, pitch = odd ? Wp : 0;
+            if (p->side && n_conv >= pf_train::kDySlots) add(T_WAIT_WG, 0, -1, slot);
+            ++n_conv;
+            if (p->bn[ii]) {
+                const float *stat = buf(L.stat[ii]);
+                add(T_BN_BWD).u.bnb = {gradt(o.dst), t_ctotal, (int)o.dst_choff, buf(L.ypre[ii]), stat, stat + o.cout, aux, aux + o.cout,
+                                       (int)o.cout, out.h, out.w, (int)o.relu, gaux, gaux + o.cout, bnpart, dy, pitch, pitch};
+            } else {
+                add(T_BIAS_BWD).u.bnb = {gradt(o.dst), t_ctotal, (int)o.dst_choff, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                         (int)o.cout, out.h, out.w, 0, gaux, nullptr, bnpart, dy, pitch, 0};
+            }
+            // dW (odd width: the tiled kernel on the padded copy of x the forward pass gathered and the padded dy; zero pad
+            // columns add nothing)
+            if (p->side) add(T_FORK, 0, sidx, slot);
+            {
+                TStep &st = add(T_WGRAD, 0, p->side ? sidx : -1);
+                const ConvArgs a = conv_args(o, in, out);
+                st.a = odd ? over_buffer(a, buf(L.xpad[ii]), (int)o.cin, Wp, Wp) : a;
+                st.ks = (int)o.k; st.stride = odd ? 1 : (int)o.stride;
+                st.u.wg = {dy, buf(p->side && sidx ? L.wpart_more[sidx] : L.wpart), k.grad + p->w_off[ii]};
+                if (tagged)      // per-layer rows of tools/bench_train.py --layers
+                    snprintf(st.tag, sizeof(st.tag), "%02d %u->%u k%u s%u %dx%d", (int)ii, o.cin, o.cout, o.k, o.stride, out.h, out.w);
+            }
+            if (p->side) add(T_WG_DONE, 0, sidx, slot);
+            // dX per input range (the network input needs none)
+            const float *dsrc = dy;
+            if (o.stride == 2) {
+                float *up = dy + align_up((size_t)B * o.cout * out.h * out.w * sizeof(float), 256) / sizeof(float);
+                bool needed = false;
+                for (uint32_t j = 0; j < o.n_src; ++j) needed = needed || o.src[j].tensor != input;
+                if (needed) add(T_ZERO_STUFF).u.plain = {dy, up, B * (int)o.cout, out.h, out.w, in.h, in.w, 0};
+                dsrc = up;
+            }
+            if (odd) {
+                const ConvArgs b = bwd_data_args(dy, (int)o.cout, (int)o.cin, in.h, Wp, pad_out, (int)o.cin, 0, 0);
+                if ((rc = dma(b, (int)o.k, 1, L.bwd_all_job[ii], 0x20))) return rc;
+                TUnpadMultiArgs &m = add(T_UNPAD_MULTI).u.unpadm;
+                m = {pad_out, (int)o.cin, in.h, in.w, Wp, (int)o.n_src, {}, {}, {}, {}, {}};
+                for (uint32_t j = 0; j < o.n_src; ++j) {
+                    m.dst[j] = o.src[j].tensor != input ? gradt(o.src[j].tensor) : nullptr;
+                    m.ctotal[j] = (int)p->tensors[o.src[j].tensor].channels;
+                    m.choff[j] = (int)o.src[j].choff;
+                    m.ch[j] = (int)o.src[j].ch;
+                    m.overwrite[j] = gfirst.store[ii][j];
+                }
+                continue;
+            }
+            for (uint32_t j = 0; j < o.n_src; ++j) {
+                const uint32_t t = o.src[j].tensor;
+                if (t == input) continue;
+                const ConvArgs b = bwd_data_args(dsrc, (int)o.cout, (int)o.src[j].ch, in.h, in.w, gradt(t), (int)p->tensors[t].channels,
+                                                 (int)o.src[j].choff, gfirst.store[ii][j] ? 0 : 1);
+                if ((rc = conv(b, (int)o.k, 1, L.bwd_job[ii][j], pad_in, false))) return rc;
+            }
+        }
+    }
+    return PF_OK;
+}
+
+// One pass of a step: its schedule, then the enqueue loop - one launch or stream operation per step
+// (measuring: the autotune pass - into the scratch gradient L.tune_grad, theta's running statistics left alone)
+int train_pass(const pf_train *p, TCall k, bool measuring) {
+    if (!p || !k.theta || !k.grad || !k.labels || !k.out3 || !k.ws) return fail(PF_EINVAL, "pf_train_forward_backward: null pointer argument");
+    if (!k.x_dense && (!k.seg || !k.depth || !k.depth_mask)) return fail(PF_EINVAL, "pf_train_forward_backward: pass seg+depth+depth_mask or x_dense");
+    if (k.B <= 0 || k.H <= 0 || k.W <= 0 || k.out_h <= 0 || k.out_w <= 0) return fail(PF_EINVAL, "pf_train_forward_backward: bad dims");
     std::vector<TDims> d;
-    int rc = t_propagate(p, H, W, d);
+    int rc = t_propagate(p, k.H, k.W, d);
     if (rc) return rc;
-    const TLayout L = t_layout(p, B, d, out_h, out_w);
-    if (ws_bytes < L.total) return fail(PF_EWORKSPACE, "workspace %zu B < required %zu B", ws_bytes, L.total);
-    char *wsb = (char *)ws;
+    const TLayout L = t_layout(p, k.B, d, k.out_h, k.out_w);
+    if (k.ws_bytes < L.total) return fail(PF_EWORKSPACE, "workspace %zu B < required %zu B", k.ws_bytes, L.total);
+    if (measuring) {
+        k.grad = reinterpret_cast<float *>((char *)k.ws + L.tune_grad);
+        k.accumulate_grads = 0;
+        k.update_running_stats = 0;
+    }
     for (int &v : p->stats) v = 0;
+    static thread_local std::vector<TStep> steps;     // (its storage is reused from call to call)
+    if ((rc = build_train_schedule(p, k, d, L, grad_first_writers(p, d), measuring, steps))) return rc;
+    for (const TStep &st : steps)
+        for (int j = 0; j < 8; ++j) p->stats[j] += (st.stats >> j) & 1;
     // Every exit of this function - an error return in the middle of the backward pass included - leaves the side streams
     // JOINED to the caller's stream: a fork that is never joined invalidates an enclosing stream capture and lets the caller's
     // stream run ahead of weight gradients still in flight.
@@ -618,376 +947,88 @@ static int train_pass(const pf_train *p, float *theta, float *grad, int accumula
             return PF_OK;
         }
         ~SideJoin() { (void)join(); }
-    } side_join{p, s};
-    auto act = [&](uint32_t t) { return reinterpret_cast<float *>(wsb + L.act[t]); };
-    auto gradt = [&](uint32_t t) { return reinterpret_cast<float *>(wsb + L.grad[t]); };
-    const uint32_t input = p->ops[0].src[0].tensor;
-    const int in_ch = (int)p->tensors[input].channels, n_cls = (int)p->hdr.n_cls;
-    float *dy_slot[pf_train::kDySlots];
-    for (int k = 0; k < pf_train::kDySlots; ++k) dy_slot[k] = reinterpret_cast<float *>(wsb + (p->side && k ? L.dy_more[k] : L.dy));
-    float *wpk = reinterpret_cast<float *>(wsb + L.wpk);
-    float *wpart = reinterpret_cast<float *>(wsb + L.wpart);
-    float *pad_in = reinterpret_cast<float *>(wsb + L.pad_in), *pad_out = reinterpret_cast<float *>(wsb + L.pad_out);
-    float *gather_to = pad_in;      // where run_conv's odd-width path puts its gathered input (forward: the op's kept copy)
-    bool keep_padded = false;       // run_conv's odd-width path leaves its result in a.dst with padded rows (forward, conv + BN: the
-                                    // BatchNorm kernels read y with that pitch, forward and backward - no unpad pass)
-    float *dfull = reinterpret_cast<float *>(wsb + L.dfull);
-    double *cepart = reinterpret_cast<double *>(wsb + L.cepart);
-    float *up_tmp = g_opt_up_two_pass ? reinterpret_cast<float *>(wsb + L.up_tmp) : nullptr;
-    double *bnpart = reinterpret_cast<double *>(wsb + L.bnpart);
-    double *loss3 = reinterpret_cast<double *>(wsb + L.out3);
-
-    // ---- input tensor (bg_model.py:61-69)
-    if (x_dense) {
-        if ((rc = launch_copy(act(input), x_dense, (size_t)B * in_ch * H * W * sizeof(float), s))) return rc;
-    } else {
-        if (T * (n_cls + 1) != in_ch) return fail(PF_EINVAL, "T=%d frames x (%d classes + depth) != %d input channels", T, n_cls, in_ch);
-        if ((rc = launch_onehot_dense(seg, seg_is_i64, depth, depth_mask, depth_mean, depth_std, B, T, n_cls, H, W, act(input), s))) return rc;
-    }
-    float *wpk_arena = reinterpret_cast<float *>(wsb + L.wpk_arena);
-    if ((rc = launch_pack_weights_batch(theta, wpk_arena, L.jobs.data(), (int)L.jobs.size(), s))) return rc;   // theta does not move inside this call
-    float *s4w_arena = reinterpret_cast<float *>(wsb + L.s4w_arena);
-    if (!L.s4jobs.empty() && (rc = launch_s4_pack_weights_dev(theta, s4w_arena, L.s4jobs.data(), (int)L.s4jobs.size(), kS4TrainWeightScale, s))) return rc;
-    // the packed-pair shadow of channels [c0, c1) of tensor t, for the convolutions that read it through conv_s4
-    // (a slice that starts or ends in the middle of a 4-channel group also zero-fills the group's other half while no producer has
-    //  written it in this pass: a reader of this slice multiplies those channels by zero weights, and 0 x a stale NaN pattern is NaN)
-    std::vector<std::vector<char>> s4_written(p->tensors.size());
-    auto shadow = [&](uint32_t t, int c0, int c1) -> int {
-        if (L.s4act[t] == (size_t)-1) return PF_OK;
-        const int ct = (int)p->tensors[t].channels;
-        std::vector<char> &wr = s4_written[t];
-        if (wr.empty()) wr.assign((size_t)ct + 4, 0);
-        const int fill_lo = (c0 & 2) && !wr[c0 - 2], fill_up = (c1 & 3) == 2 && c1 < ct && !wr[c1];
-        for (int c = c0; c < c1; ++c) wr[c] = 1;
-        return launch_s4_pack_act(act(t), B, ct, c0, c1, fill_lo, fill_up, d[t].h, d[t].w, (d[t].w + 3) / 4 * 4, wsb + L.s4act[t], kS4TrainActScale, s);
-    };
-    const GradFirst gfirst = grad_first_writers(p, d);      // (no cleared gradient arena: first writers store)
-    for (const auto &c : gfirst.clear)
-        if ((rc = launch_zero_channels(gradt((uint32_t)c[0]), B, (int)p->tensors[c[0]].channels, c[1], c[2], (long long)d[c[0]].h * d[c[0]].w, s))) return rc;
-    if (!accumulate_grads && (rc = launch_zero_fill(grad, p->n_params * sizeof(float), s))) return rc;
-
-    auto conv_args = [&](const BlobOp &o, const TDims &in, const TDims &out, ConvArgs &a) {
-        memset(&a, 0, sizeof(a));
-        a.n_src = (int)o.n_src;
-        int c0 = 0;
-        for (int j = 0; j < a.n_src; ++j) {
-            a.src[j] = act(o.src[j].tensor);
-            a.src_ctotal[j] = (int)p->tensors[o.src[j].tensor].channels;
-            a.src_choff[j] = (int)o.src[j].choff;
-            a.src_cstart[j] = c0;
-            c0 += (int)o.src[j].ch;
+    } side_join{p, k.s};
+    const hipStream_t s = k.s;
+    const int B = k.B;
+    for (const TStep &st : steps) {
+        const hipStream_t ss = st.side >= 0 ? p->sides[st.side] : s;
+        const auto &u = st.u;
+        switch (st.kind) {
+            case T_COPY: rc = launch_copy(u.copy.dst, u.copy.src, u.copy.bytes, s); break;
+            case T_ONEHOT: { const TOneHotArgs &x = u.onehot;
+                rc = launch_onehot_dense(x.seg, x.seg_i64, x.depth, x.mask, x.mean, x.stdv, B, x.T, x.n_cls, x.H, x.W, x.x, s); break; }
+            case T_PACK_TILED: rc = launch_pack_weights_batch(u.pack.theta, u.pack.arena, (const PackJob *)u.pack.jobs, u.pack.n, s); break;
+            case T_PACK_S4: rc = launch_s4_pack_weights_dev(u.pack.theta, u.pack.arena, (const S4WJob *)u.pack.jobs, u.pack.n, kS4TrainWeightScale, s); break;
+            case T_ZERO_CHANNELS: rc = launch_zero_channels(u.zch.t, B, u.zch.ctotal, u.zch.c0, u.zch.n, u.zch.hw, s); break;
+            case T_ZERO_FILL: rc = launch_zero_fill(u.copy.dst, u.copy.bytes, s); break;
+            case T_PAD_GATHER: rc = launch_pad_gather(st.a, B, st.Wp, st.gather, s); break;
+            case T_CONV_DMA: rc = launch_conv_dma(st.a, st.ks, st.stride, B, s, st.wm, st.nt); break;
+            case T_CONV_DMA_MEASURE: rc = tune_conv_dma(p, st.a, st.ks, st.stride, B, s); break;
+            case T_CONV_S4: rc = launch_conv_s4(st.a, st.ks, st.nt, st.wide, B, s); break;
+            case T_UNPAD: { const TUnpadArgs &x = u.unpad;
+                rc = launch_unpad_scatter(x.src, B, x.C, x.H, x.W, x.Wp, x.dst, x.ctotal, x.choff, x.accum, s); break; }
+            case T_UNPAD_MULTI: { const TUnpadMultiArgs &x = u.unpadm;
+                rc = launch_unpad_scatter_multi(x.src, B, x.C, x.H, x.W, x.Wp, x.dst, x.ctotal, x.choff, x.ch, x.overwrite, x.n, s); break; }
+            case T_BN_FWD: { const TBnFwdArgs &x = u.bnf;
+                rc = launch_bn_forward(x.y, B, x.C, x.H, x.W, x.eps, x.momentum, x.gamma, x.beta, x.rmean, x.rvar, x.mean, x.invstd, x.part,
+                                       x.dst, x.dst_ctotal, x.dst_choff, x.relu, x.y_pitch, s); break; }
+            case T_S4_ACT: { const TS4ActArgs &x = u.s4act;
+                rc = launch_s4_pack_act(x.src, B, x.ctotal, x.c0, x.c1, x.fill_lo, x.fill_up, x.H, x.W, x.Wp, x.dst, kS4TrainActScale, s); break; }
+            case T_POOL: rc = launch_avgpool2(u.plain.src, u.plain.dst, u.plain.planes, u.plain.hin, u.plain.win, nullptr, nullptr, s); break;
+            case T_UPSAMPLE: { const TPlainArgs &x = u.plain;
+                rc = launch_upsample(x.src, x.dst, x.planes, x.hin, x.win, x.hout, x.wout, nullptr, nullptr, s); break; }
+            case T_CE: { const TCeArgs &x = u.ce;
+                rc = launch_ce_fwd_bwd(x.logits, B, x.C, x.hi, x.wi, x.labels, x.lab_i64, x.ho, x.wo, x.ignore, x.dfull, x.part, x.out3, s); break; }
+            case T_UPSAMPLE_BWD: { const TUpBwdArgs &x = u.upb;
+                rc = launch_upsample_bwd(x.gout, x.planes, x.hi, x.wi, x.ho, x.wo, x.count, x.scale, x.accumulate, x.gin, x.tmp, s); break; }
+            case T_POOL_BWD: rc = launch_avgpool2_bwd(u.plain.src, u.plain.planes, u.plain.hin, u.plain.win, u.plain.overwrite, u.plain.dst, s); break;
+            case T_BN_BWD: { const TBnBwdArgs &x = u.bnb;
+                rc = launch_bn_backward(x.g, x.t_ctotal, x.choff, x.y, x.mean, x.invstd, x.gamma, x.beta, B, x.C, x.H, x.W, x.relu, x.dgamma,
+                                        x.dbeta, x.part, x.dy, x.dy_pitch, x.y_pitch, s); break; }
+            case T_BIAS_BWD: { const TBnBwdArgs &x = u.bnb;
+                rc = launch_bias_backward(x.g, x.t_ctotal, x.choff, B, x.C, x.H, x.W, x.dgamma, x.part, x.dy, x.dy_pitch, s); break; }
+            case T_ZERO_STUFF: rc = launch_zero_stuff(u.plain.src, u.plain.planes, u.plain.hin, u.plain.win, u.plain.hout, u.plain.wout, u.plain.dst, s); break;
+            case T_WGRAD:
+                if (st.tag[0]) prof_set_tag(st.tag);
+                rc = launch_wgrad(st.a, st.ks, st.stride, u.wg.dy, B, u.wg.partial, u.wg.dw, ss);
+                if (st.tag[0]) prof_set_tag(nullptr);
+                break;
+            case T_WAIT_WG: PF_HIP_CHECK(hipStreamWaitEvent(s, p->ev_wg[st.slot], 0)); break;
+            case T_FORK:
+                PF_HIP_CHECK(hipEventRecord(p->ev_dy[st.slot], s));
+                PF_HIP_CHECK(hipStreamWaitEvent(ss, p->ev_dy[st.slot], 0));
+                ++side_join.forked;
+                break;
+            case T_WG_DONE: PF_HIP_CHECK(hipEventRecord(p->ev_wg[st.slot], ss)); break;
         }
-        for (int j = a.n_src; j <= kConvMaxSrc; ++j) a.src_cstart[j] = c0;
-        a.bias = p->dev_zero;
-        a.Cin = (int)o.cin; a.Cout = (int)o.cout;
-        a.Hin = in.h; a.Win = in.w; a.Hout = out.h; a.Wout = out.w;
-        a.zero_page = p->dev_zero;
-        a.ntiles = ((int)o.cout + 15) / 16;
-        a.src_end = a.n_src;
-    };
-
-    // one convolution: a = sources / destination / shapes filled, weights = OIHW in theta.  fwd: the op's own conv (input
-    // ranges src_ch); else the backward-data conv of forward input range [c0, c0 + ch) (one range: the cout_f channels of dy)
-    // job: the conv's entry in L.jobs (its tiled packing is already in the arena), or -1
-    auto run_conv = [&](ConvArgs &a, int ks, int stride, const float *w, int cin_f, int cout_f, const int *src_ch, int n_src, int tflip, int c0,
-                        int ch, int job) -> int {
-        int rc2 = PF_EUNSUPPORTED;
-        auto fast = [&](ConvArgs &c, const int *chs, int ns) -> int {
-            if (job >= 0 && L.jobs[job].n_src == ns) {
-                c.wpk = wpk_arena + L.jobs[job].out_off;
-            } else {
-                int r2 = launch_pack_weights_tiled(w, cin_f, cout_f, ks, stride, chs, ns, tflip, c0, ch, wpk, s);
-                if (r2) return r2;
-                c.wpk = wpk;
-            }
-            const int kc = dma_kc(ks, stride);
-            c.src_chunk0[0] = 0;
-            for (int j = 0; j < kConvMaxSrc; ++j) c.src_chunk0[j + 1] = c.src_chunk0[j] + (j < ns ? (chs[j] + kc - 1) / kc : 0);
-            c.nchunks = c.src_chunk0[ns];
-            c.chunk_begin = 0;
-            c.chunk_end = c.nchunks;
-            c.rem = 0;
-            return train_conv_dma(p, c, ks, stride, B, s);
-        };
-        if ((a.Win & 3) == 0) {
-            rc2 = fast(a, src_ch, n_src);
-            if (rc2 != PF_EUNSUPPORTED) return rc2;
-        } else {
-            // odd width: the same kernels on copies whose rows are padded to a multiple of 4 (train_kernels.hip)
-            const int Wp = (a.Win + 3) / 4 * 4, pad = ks / 2;
-            const int Wop = (Wp + 2 * pad - ks) / stride + 1;
-            if ((rc2 = launch_pad_gather(a, B, Wp, gather_to, s))) return rc2;
-            ++p->stats[3];
-            ConvArgs c = a;
-            c.n_src = 1;
-            c.src[0] = gather_to; c.src_ctotal[0] = a.Cin; c.src_choff[0] = 0; c.src_cstart[0] = 0;
-            for (int k = 1; k <= kConvMaxSrc; ++k) c.src_cstart[k] = a.Cin;
-            c.src_begin = 0; c.src_end = 1;
-            c.Win = Wp; c.Wout = Wop;
-            c.dst = keep_padded ? a.dst : pad_out; c.dst_ctotal = a.Cout; c.dst_choff = 0; c.accum = 0;
-            const int one = a.Cin;
-            rc2 = fast(c, &one, 1);
-            if (rc2 == PF_OK && keep_padded) {
-                ++p->stats[4];
-                return PF_OK;
-            }
-            if (keep_padded && rc2 == PF_EUNSUPPORTED) return fail(PF_EUNSUPPORTED, "training: no tiled kernel for an odd-width conv + BatchNorm layer");
-            if (rc2 == PF_OK) return launch_unpad_scatter(pad_out, B, a.Cout, a.Hout, a.Wout, Wop, a.dst, a.dst_ctotal, a.dst_choff, a.accum, s);
-            if (rc2 != PF_EUNSUPPORTED) return rc2;
-        }
-        ++p->stats[6];      // the generic register-staged kernel (no tiled kernel took the geometry)
-        const ConvTiling t = choose_tiling(ks, stride, tflip ? cout_f : cin_f, tflip ? ch : cout_f, 0);
-        if ((rc2 = launch_pack_weights(w, cin_f, cout_f, t, tflip, c0, ch, wpk, s))) return rc2;
-        a.wpk = wpk;
-        a.nchunks = t.nchunks;
-        return launch_conv(a, t, B, s);
-    };
-
-    // ================================================================ forward (training mode)
-    for (size_t i = 0; i < p->ops.size(); ++i) {
-        const BlobOp &o = p->ops[i];
-        const TDims in = d[o.src[0].tensor];
-        const TDims out = o.kind == OP_HEAD ? in : d[o.dst];
-        if (o.kind == OP_STEM || o.kind == OP_CONV) {
-            int src_ch[kMaxSrc];
-            for (uint32_t j = 0; j < o.n_src; ++j) src_ch[j] = (int)o.src[j].ch;
-            ConvArgs a;
-            conv_args(o, in, out, a);
-            gather_to = L.xpad[i] != (size_t)-1 ? reinterpret_cast<float *>(wsb + L.xpad[i]) : pad_in;
-            if (p->bn[i]) {
-                float *y = reinterpret_cast<float *>(wsb + L.ypre[i]);
-                a.dst = y; a.dst_ctotal = (int)o.cout; a.dst_choff = 0; a.relu = 0;
-                const bool odd_f = (in.w & 3) != 0 && o.stride == 1;
-                if (L.s4_job[i] >= 0) {
-                    // train_s4.hip: conv_s4 on the shadows of the input ranges; y in fp32 (rows padded to 4 on an odd-width level,
-                    // as the tiled fp32 path leaves them).  The weight gradient of an odd-width layer still reads the gathered,
-                    // row-padded fp32 copy of x
-                    const S4WJob &jb = L.s4jobs[L.s4_job[i]];
-                    const int Wp = (in.w + 3) / 4 * 4, per = o.k == 3 ? 2 : 8;
-                    if (odd_f) {
-                        if ((rc = launch_pad_gather(a, B, Wp, gather_to, s))) return rc;
-                        ++p->stats[3];
-                        ++p->stats[4];
-                    }
-                    ConvArgs c = a;
-                    int e = 0;
-                    for (int j = 0; j < c.n_src; ++j) {
-                        const int ch0 = (int)o.src[j].choff, chn = (int)o.src[j].ch;
-                        c.src[j] = reinterpret_cast<const float *>(wsb + L.s4act[o.src[j].tensor]);
-                        c.src_c4[j] = (c.src_ctotal[j] + 3) / 4;
-                        c.src_g0[j] = ch0 / 4;
-                        c.src_gn[j] = (ch0 + chn + 3) / 4 - ch0 / 4;
-                        c.src_ent0[j] = e;
-                        e += jb.pad ? (c.src_gn[j] + per - 1) / per * per : c.src_gn[j];
-                    }
-                    for (int j = c.n_src; j <= kConvMaxSrc; ++j) c.src_ent0[j] = e;
-                    c.src_fmt = 1;
-                    c.dst_fmt = 0;
-                    c.src_begin = 0;
-                    c.Win = Wp; c.Wout = Wp;
-                    c.acc_scale = 1.0f / (kS4TrainWeightScale * kS4TrainActScale);
-                    c.wpk = s4w_arena + jb.out_off;
-                    c.nchunks = jb.rounds;
-                    c.chunk_begin = 0;
-                    c.chunk_end = jb.rounds;
-                    c.kacc = (g_opt_train_kacc && o.k == 3) ? 1 : 0;      // blocked summation, as in the fp32 step (conv_s4_kernel.inc: KACC)
-                    ConvChoice ch4;
-                    int nt4 = c.ntiles == 3 ? 3 : (c.ntiles < 2 ? 1 : 2), wide4 = 0;
-                    if (g_opt_use_tuned && choose_s4((int)o.k, c.Cin, c.Cout, c.Hout, c.Wout, B, &ch4) && ch4.kind == 5) { nt4 = ch4.p0; wide4 = ch4.p1; }
-                    if ((rc = launch_conv_s4(c, (int)o.k, nt4, wide4, B, s))) return rc;
-                    ++p->stats[7];
-                } else {
-                keep_padded = odd_f;
-                rc = run_conv(a, (int)o.k, (int)o.stride, theta + p->w_off[i], (int)o.cin, (int)o.cout, src_ch, (int)o.n_src, 0, 0, 0, L.fwd_job[i]);
-                keep_padded = false;
-                if (rc) return rc;
-                }
-                float *aux = theta + p->aux_off[i];
-                float *stat = reinterpret_cast<float *>(wsb + L.stat[i]);
-                if ((rc = launch_bn_forward(y, B, (int)o.cout, out.h, out.w, bn_eps, bn_momentum, aux, aux + o.cout,
-                                            update_running_stats ? aux + 2 * o.cout : nullptr, update_running_stats ? aux + 3 * o.cout : nullptr,
-                                            stat, stat + o.cout, bnpart, act(o.dst), (int)p->tensors[o.dst].channels, (int)o.dst_choff,
-                                            (int)o.relu, odd_f ? (out.w + 3) / 4 * 4 : 0, s)))
-                    return rc;
-                if ((rc = shadow(o.dst, (int)o.dst_choff, (int)o.dst_choff + (int)o.cout))) return rc;
-            } else {
-                a.bias = theta + p->aux_off[i];
-                a.dst = act(o.dst); a.dst_ctotal = (int)p->tensors[o.dst].channels; a.dst_choff = (int)o.dst_choff; a.relu = (int)o.relu;
-                if ((rc = run_conv(a, (int)o.k, (int)o.stride, theta + p->w_off[i], (int)o.cin, (int)o.cout, src_ch, (int)o.n_src, 0, 0, 0, L.fwd_job[i]))) return rc;
-                if ((rc = shadow(o.dst, (int)o.dst_choff, (int)o.dst_choff + (int)o.cout))) return rc;
-            }
-        } else if (o.kind == OP_POOL) {
-            if ((rc = launch_avgpool2(act(o.src[0].tensor), act(o.dst), B * (int)o.cin, in.h, in.w, nullptr, nullptr, s))) return rc;
-            if ((rc = shadow(o.dst, 0, (int)p->tensors[o.dst].channels))) return rc;
-        } else if (o.kind == OP_UPSAMPLE) {
-            if ((rc = launch_upsample(act(o.src[0].tensor), act(o.dst), B * (int)o.cin, in.h, in.w, out.h, out.w, nullptr, nullptr, s))) return rc;
-            if ((rc = shadow(o.dst, 0, (int)p->tensors[o.dst].channels))) return rc;
-        } else if (o.kind == OP_HEAD) {
-            if ((rc = launch_ce_fwd_bwd(act(o.src[0].tensor), B, (int)o.cin, in.h, in.w, labels, labels_i64, out_h, out_w, ignore_index, dfull,
-                                        cepart, loss3, s)))
-                return rc;
-            if ((rc = launch_copy(out3, loss3, 3 * sizeof(double), s))) return rc;
-        }
-    }
-
-    // ================================================================ backward
-    gather_to = pad_in;
-    // With the side streams: layer n's conv-output gradient goes to dy slot n % kDySlots; the weight gradient (and its padded
-    // copy of x) reads it on side stream n % kSideStreams while the caller's stream goes on to the input gradients and the next
-    // layers; before it overwrites a slot it waits for the weight gradient of layer n - kDySlots that last read it.
-    int n_conv = 0;
-    for (size_t ii = p->ops.size(); ii-- > 0;) {
-        const BlobOp &o = p->ops[ii];
-        const TDims in = d[o.src[0].tensor];
-        const TDims out = o.kind == OP_HEAD ? in : d[o.dst];
-        if (o.kind == OP_HEAD) {
-            // d loss / d logits = bilinear^T (softmax - onehot) * loss_scale / n_valid   (mean over the valid pixels, bg_model.py:81)
-            if ((rc = launch_upsample_bwd(dfull, B * (int)o.cin, in.h, in.w, out_h, out_w, loss3 + 1, loss_scale, gfirst.store[ii][0] ? 0 : 1, gradt(o.src[0].tensor), up_tmp, s))) return rc;
-        } else if (o.kind == OP_POOL) {
-            if ((rc = launch_avgpool2_bwd(gradt(o.dst), B * (int)o.cin, in.h, in.w, gfirst.store[ii][0], gradt(o.src[0].tensor), s))) return rc;
-        } else if (o.kind == OP_UPSAMPLE) {
-            if ((rc = launch_upsample_bwd(gradt(o.dst), B * (int)o.cin, in.h, in.w, out.h, out.w, nullptr, 1.f, gfirst.store[ii][0] ? 0 : 1, gradt(o.src[0].tensor), up_tmp, s))) return rc;
-        } else if (o.kind == OP_STEM || o.kind == OP_CONV) {
-            const int t_ctotal = (int)p->tensors[o.dst].channels;
-            float *aux = theta + p->aux_off[ii], *gaux = grad + p->aux_off[ii];
-            const int slot = n_conv % pf_train::kDySlots, sidx = n_conv % pf_train::kSideStreams;
-            float *dy = dy_slot[slot];
-            // odd-width levels (stride 1): dy goes out with its rows padded to a multiple of 4 floats and zero pad columns - the
-            // form the tiled weight-gradient and backward-data kernels read - and ONE backward-data conv covers all input ranges
-            const bool odd = (in.w & 3) != 0 && o.stride == 1;
-            const int Wp = (in.w + 3) / 4 * 4;
-            if (p->side && n_conv >= pf_train::kDySlots) PF_HIP_CHECK(hipStreamWaitEvent(s, p->ev_wg[slot], 0));
-            ++n_conv;
-            if (p->bn[ii]) {
-                const float *stat = reinterpret_cast<const float *>(wsb + L.stat[ii]);
-                if ((rc = launch_bn_backward(gradt(o.dst), t_ctotal, (int)o.dst_choff, reinterpret_cast<const float *>(wsb + L.ypre[ii]),
-                                             stat, stat + o.cout, aux, aux + o.cout, B, (int)o.cout, out.h, out.w, (int)o.relu, gaux, gaux + o.cout, bnpart,
-                                             dy, odd ? Wp : 0, odd ? Wp : 0, s)))
-                    return rc;
-            } else {
-                if (o.relu) return fail(PF_EUNSUPPORTED, "training: ReLU without BatchNorm (op %zu)", ii);
-                if ((rc = launch_bias_backward(gradt(o.dst), t_ctotal, (int)o.dst_choff, B, (int)o.cout, out.h, out.w, gaux, bnpart, dy, odd ? Wp : 0, s))) return rc;
-            }
-            // dW
-            hipStream_t sw = s;
-            float *wpart_l = wpart;
-            if (p->side) {
-                PF_HIP_CHECK(hipEventRecord(p->ev_dy[slot], s));
-                sw = p->sides[sidx];
-                PF_HIP_CHECK(hipStreamWaitEvent(sw, p->ev_dy[slot], 0));
-                side_join.forked = n_conv;
-                if (sidx) wpart_l = reinterpret_cast<float *>(wsb + L.wpart_more[sidx]);
-            }
-            ConvArgs a;
-            conv_args(o, in, out, a);
-            if (prof_enabled()) {      // per-layer rows of tools/bench_train.py --layers
-                char tag[64];
-                snprintf(tag, sizeof(tag), "%02d %u->%u k%u s%u %dx%d", (int)ii, o.cin, o.cout, o.k, o.stride, out.h, out.w);
-                prof_set_tag(tag);
-            }
-            if (odd) {
-                // odd width: the tiled kernel on the padded copy of x the forward pass gathered (all ranges) and the padded dy; zero
-                // pad columns add nothing
-                ConvArgs ap = a;
-                ap.n_src = 1;
-                ap.src[0] = reinterpret_cast<float *>(wsb + L.xpad[ii]); ap.src_ctotal[0] = (int)o.cin; ap.src_choff[0] = 0; ap.src_cstart[0] = 0;
-                for (int k = 1; k <= kConvMaxSrc; ++k) ap.src_cstart[k] = (int)o.cin;
-                ap.Win = Wp; ap.Wout = Wp;
-                if ((rc = launch_wgrad(ap, (int)o.k, 1, dy, B, wpart_l, grad + p->w_off[ii], sw))) return rc;
-            } else if ((rc = launch_wgrad(a, (int)o.k, (int)o.stride, dy, B, wpart_l, grad + p->w_off[ii], sw))) {
-                return rc;
-            }
-            if (prof_enabled()) prof_set_tag(nullptr);
-            if (p->side) PF_HIP_CHECK(hipEventRecord(p->ev_wg[slot], sw));
-            // dX per input range (the network input needs none)
-            const float *dsrc = dy;
-            if (o.stride == 2) {
-                float *up = dy + align_up((size_t)B * o.cout * out.h * out.w * sizeof(float), 256) / sizeof(float);
-                bool needed = false;
-                for (uint32_t j = 0; j < o.n_src; ++j) needed = needed || o.src[j].tensor != input;
-                if (needed && (rc = launch_zero_stuff(dy, B * (int)o.cout, out.h, out.w, in.h, in.w, up, s))) return rc;
-                dsrc = up;
-            }
-            if (odd) {
-                const PackJob &q = L.jobs[L.bwd_all_job[ii]];
-                ConvArgs b;
-                memset(&b, 0, sizeof(b));
-                b.n_src = 1;
-                b.src[0] = dy; b.src_ctotal[0] = (int)o.cout; b.src_choff[0] = 0; b.src_cstart[0] = 0;
-                for (int k = 1; k <= kConvMaxSrc; ++k) b.src_cstart[k] = (int)o.cout;
-                b.bias = p->dev_zero; b.zero_page = p->dev_zero;
-                b.dst = pad_out; b.dst_ctotal = (int)o.cin; b.dst_choff = 0;
-                b.Cin = (int)o.cout; b.Cout = (int)o.cin; b.Hin = in.h; b.Win = Wp; b.Hout = in.h; b.Wout = Wp;
-                b.ntiles = ((int)o.cin + 15) / 16; b.src_end = 1;
-                b.wpk = wpk_arena + q.out_off;
-                const int kc = dma_kc((int)o.k, 1);
-                b.src_chunk0[0] = 0;
-                for (int j = 0; j < kConvMaxSrc; ++j) b.src_chunk0[j + 1] = j == 0 ? ((int)o.cout + kc - 1) / kc : b.src_chunk0[j];
-                b.nchunks = b.src_chunk0[1];
-                b.chunk_begin = 0;
-                b.chunk_end = b.nchunks;
-                if ((rc = train_conv_dma(p, b, (int)o.k, 1, B, s))) return rc;
-                ++p->stats[5];
-                float *dsts[kMaxSrc];
-                int ct[kMaxSrc], co[kMaxSrc], chs[kMaxSrc], ow[kMaxSrc];
-                for (uint32_t j = 0; j < o.n_src; ++j) {
-                    ow[j] = gfirst.store[ii][j];
-                    dsts[j] = o.src[j].tensor != input ? gradt(o.src[j].tensor) : nullptr;
-                    ct[j] = (int)p->tensors[o.src[j].tensor].channels;
-                    co[j] = (int)o.src[j].choff;
-                    chs[j] = (int)o.src[j].ch;
-                }
-                if ((rc = launch_unpad_scatter_multi(pad_out, B, (int)o.cin, in.h, in.w, Wp, dsts, ct, co, chs, ow, (int)o.n_src, s))) return rc;
-                continue;
-            }
-            int c0 = 0;
-            for (uint32_t j = 0; j < o.n_src; ++j) {
-                const int ch = (int)o.src[j].ch;
-                if (o.src[j].tensor != input) {
-                    ConvArgs b;
-                    memset(&b, 0, sizeof(b));
-                    b.n_src = 1;
-                    b.src[0] = dsrc; b.src_ctotal[0] = (int)o.cout; b.src_choff[0] = 0; b.src_cstart[0] = 0;
-                    for (int k = 1; k <= kConvMaxSrc; ++k) b.src_cstart[k] = (int)o.cout;
-                    b.bias = p->dev_zero; b.zero_page = p->dev_zero;
-                    b.dst = gradt(o.src[j].tensor); b.dst_ctotal = (int)p->tensors[o.src[j].tensor].channels; b.dst_choff = (int)o.src[j].choff;
-                    b.Cin = (int)o.cout; b.Cout = ch; b.Hin = in.h; b.Win = in.w; b.Hout = in.h; b.Wout = in.w;
-                    b.ntiles = (ch + 15) / 16; b.src_end = 1; b.accum = gfirst.store[ii][j] ? 0 : 1;
-                    const int dy_ch = (int)o.cout;
-                    if ((rc = run_conv(b, (int)o.k, 1, theta + p->w_off[ii], (int)o.cin, (int)o.cout, &dy_ch, 1, 1, c0, ch, L.bwd_job[ii][j]))) return rc;
-                }
-                c0 += ch;
-            }
-        }
+        if (rc) return rc;
     }
     return side_join.join();   // the caller's stream carries every gradient when this call's work is done
 }
+
+}  // namespace
 
 extern "C" int pf_train_forward_backward(const pf_train *p, float *theta, float *grad, int accumulate_grads, const void *seg, int seg_is_i64,
                                          const float *depth, const uint8_t *depth_mask, float depth_mean, float depth_std, int T,
                                          const float *x_dense, int B, int H, int W, const void *labels, int labels_i64, int out_h, int out_w,
                                          int ignore_index, float loss_scale, float bn_momentum, float bn_eps, int update_running_stats,
                                          double *out3, void *ws, size_t ws_bytes, void *stream) {
+    const TCall k{theta, grad, accumulate_grads, seg, seg_is_i64, depth, depth_mask, depth_mean, depth_std, T, x_dense, B, H, W, labels, labels_i64,
+                  out_h, out_w, ignore_index, loss_scale, bn_momentum, bn_eps, update_running_stats, out3, ws, ws_bytes, (hipStream_t)stream};
     if (p && p->autotune && ws) {
+        // pf_train_autotune: the measurements run in a pass of their own in front of the first real pass of a configuration
+        // (B, H, W, out_h, out_w) outside a capture: its launches repeat, so what they accumulate is garbage - it goes to a scratch
+        // gradient and leaves theta alone
         const std::array<int, 5> cfg{B, H, W, out_h, out_w};
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         const bool seen = std::find(p->measured_configs.begin(), p->measured_configs.end(), cfg) != p->measured_configs.end();
-        if (!seen && hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
-            std::vector<TDims> d;
-            int rc = t_propagate(p, H, W, d);
-            if (rc) return rc;
-            const TLayout L = t_layout(p, B, d, out_h, out_w);
-            if (ws_bytes < L.total) return fail(PF_EWORKSPACE, "workspace %zu B < required %zu B", ws_bytes, L.total);
-            p->measuring = true;
-            rc = train_pass(p, theta, reinterpret_cast<float *>((char *)ws + L.tune_grad), 0, seg, seg_is_i64, depth, depth_mask, depth_mean, depth_std, T,
-                            x_dense, B, H, W, labels, labels_i64, out_h, out_w, ignore_index, loss_scale, bn_momentum, bn_eps, 0, out3, ws, ws_bytes, stream);
-            p->measuring = false;
+        if (!seen && hipStreamIsCapturing(k.s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
+            const int rc = train_pass(p, k, true);
             if (rc) return rc;
             p->measured_configs.push_back(cfg);
         }
     }
-    return train_pass(p, theta, grad, accumulate_grads, seg, seg_is_i64, depth, depth_mask, depth_mean, depth_std, T, x_dense, B, H, W, labels,
-                      labels_i64, out_h, out_w, ignore_index, loss_scale, bn_momentum, bn_eps, update_running_stats, out3, ws, ws_bytes, stream);
+    return train_pass(p, k, false);
 }
 
 extern "C" int pf_sgd_workspace(size_t *bytes) {

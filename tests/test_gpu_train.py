@@ -552,6 +552,7 @@ def test_forward_on_packed_pairs_is_the_same_step_to_rounding():
 
 def _mini_network_step(size):
     from tests.helpers import MiniTrain
+    from panoptic_forecasting_amd import lib as pflib
     h, w = size
     sp = _mini_net()
     g = torch.Generator().manual_seed(17)
@@ -569,7 +570,12 @@ def _mini_network_step(size):
     lab[lab == 11] = 255
     want_loss, leaves, kept = _mini_torch(sp, params, x, lab)
     net = MiniTrain(sp, params)
+    # a successful step leaves pf_last_error alone (no kernel is tried and then replaced by another one)
+    L = pflib.load()
+    assert L.pf_set_option(b'no_such_option', 1) == -1
+    before = L.pf_last_error()
     got_loss = net.step(x.cuda(), lab.cuda())
+    assert L.pf_last_error() == before, L.pf_last_error()
     assert abs(got_loss - want_loss) <= 1e-5 * abs(want_loss)
     bad = []
     for name, t in kept.items():

@@ -256,6 +256,28 @@ int pf_fg_forward(const float *packed, int flags, int N, int T_in, int T_out, in
                   float *traj_norm, float *traj_unnorm, float *mask_feats, float *output_feats, float *masks,
                   void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * odometry forecaster network - replaces OdomModel.forward (models/odom/odom_model.py:79-106) of the shipped odom config
+ * (pretrained_models/odom/config.yaml: normalize_input, rnn_hidden 128, no inp_emb_layers / out_layers):
+ * nn.GRU(2, 128) + Linear(128, 2) on normalised [speed, yaw_rate].  csrc/odom_net.hip, one launch per forecast.
+ *   flags      bit 0: predict_type offset (current = current + out); clear: direct (current = out).  Other bits:
+ *              PF_EUNSUPPORTED.
+ *   pf_odom_weights_size: raw = the 8 state_dict tensors of the reference (odom_mean, odom_std, rnn.weight_ih_l0,
+ *              rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0, out.0.weight, out.0.bias), flattened and concatenated in
+ *              that order (fp32, 50 950 floats); packed = the device buffer pf_odom_pack fills (raw copy + W_hh re-tiled,
+ *              the r, z, n rows of 16 hidden units side by side).  Both in floats.
+ *   pf_odom_pack(raw, packed): device buffers; enqueued on stream.  Re-run after the parameters change.
+ *   pf_odom_forward: B sequences, T_in input steps (the GRU runs over the first T_in - 1, the decoder starts from the
+ *              last), T_out forecast steps:
+ *     inps [B,T_in,2] f32 (unnormalised)  ->  out [B,T_out,2] (unnormalised), out_norm [B,T_out,2] (normalised)
+ *   Dimensions are checked before any device work: B >= 0, 2 <= T_in <= 64, 1 <= T_out <= 64, no null buffer when B > 0
+ *   (PF_EINVAL).  B = 0 enqueues nothing.  No workspace: the state lives in LDS and registers.
+ */
+int pf_odom_weights_size(int flags, size_t *raw_floats, size_t *packed_floats);
+int pf_odom_pack(const float *raw, float *packed, int flags, void *stream);
+int pf_odom_forward(const float *packed, int flags, int B, int T_in, int T_out, const float *inps, float *out,
+                    float *out_norm, void *stream);
+
 /* Process-wide execution options (not thread-safe; set before launching work):
  *   "fuse_pool"     (default 1) a 1x1 conv followed by AvgPool2d(2,2) (hardnet.py:296) pools in the conv epilogue;
  *   "fuse_upsample" (default 1) TransitionUp + 1x1 conv over cat([up(x), skip]) (hardnet.py:248-258,365-368) is

@@ -54,14 +54,19 @@ def intrinsics_matrix(fx, fy, u0, v0):
     return K
 
 
+def planar_motion(speed, yaw_rate, dt):
+    """Unicycle step ``(x, y, theta)``: the current vehicle pose in the previous vehicle frame (``data_utils.py:137-150``,
+    the ``dx, dy, dtheta`` that ``get_vehicle_now_T_prev`` also returns).  Scalars keep their numpy types, as there."""
+    if abs(yaw_rate) < ANGLE_RAD_EPS:
+        return dt * speed, 0.0, 0.0
+    r = speed / yaw_rate
+    wt = yaw_rate * dt
+    return r * np.sin(wt), r - r * np.cos(wt), wt
+
+
 def now_T_prev(speed, yaw_rate, dt):
     """Unicycle step: pose of the previous vehicle frame expressed in the current one."""
-    if abs(yaw_rate) < ANGLE_RAD_EPS:
-        x, y, theta = dt * speed, 0.0, 0.0
-    else:
-        r = speed / yaw_rate
-        wt = yaw_rate * dt
-        x, y, theta = r * np.sin(wt), r - r * np.cos(wt), wt
+    x, y, theta = planar_motion(speed, yaw_rate, dt)
     c, s = np.cos(theta), np.sin(theta)
     prev_T_now = affine(np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]], dtype=np.float64),
                         np.array([x, y, 0.0]))

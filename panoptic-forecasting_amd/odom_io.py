@@ -72,6 +72,58 @@ class OdometryFile:
         self.close()
 
 
+SNIPPET_LEN = 30            # rows of ``odometry`` per snippet in ``{split}_3d_info.pkl``
+WINDOW_ROWS = 18            # odom_dataset.py:76 (``np.arange(18)``, independent of input_len / output_len)
+
+
+def odom_windows(odometry, input_len=9, output_len=9):
+    """The odometry forecaster's test-mode windows of one snippet (``OdomDataset(test=True)``, odom_dataset.py:73-83,94-121).
+
+    ``odometry`` [30, >= 2] (columns ``[:, :2]`` = speed, yaw_rate are used).  Returns ``(inputs [N, input_len, 2],
+    labels [N, output_len, 2], start_frames [N])`` as float32 / float32 / int64 in the dataset's order: ``start_ind`` 0 ..
+    30 - input_len (rows ``start_ind + arange(18)`` clipped at 29; inputs = the first input_len rows, labels = the rest),
+    then the two padded windows ``start_ind`` -1 and -2 (first row repeated; labels = the last output_len rows of
+    ``arange(18)[:-k]``).  ``start_frames`` = snippet index of the last input row = the export key's last field.
+    """
+    odom = np.asarray(odometry)[:, :2].astype(np.float32)
+    inds = np.arange(WINDOW_ROWS)
+    wins = [(s, (s + inds).clip(max=SNIPPET_LEN - 1)) for s in range(SNIPPET_LEN - input_len + 1)]
+    wins += [(-1, inds[:-1]), (-2, inds[:-2])]
+    inputs, labels, starts = [], [], []
+    for start, cur in wins:
+        o = odom[cur]
+        if start < 0:
+            inputs.append(np.concatenate([np.repeat(o[0:1], -start, 0), o[:input_len + start]]))
+            labels.append(o[-output_len:])
+            starts.append(cur[input_len - 1 + start])
+        else:
+            inputs.append(o[:input_len])
+            labels.append(o[input_len:])
+            starts.append(cur[input_len - 1])
+    return np.stack(inputs), np.stack(labels), np.asarray(starts, dtype=np.int64)
+
+
+FG_FUTURE_ROWS = (2, 5, 8)  # fg_scene_dataset.py:489: the forecast rows the fg model takes
+
+
+def fg_odometry(inp_odom, odom_preds, inp_times):
+    """The odometry ``FGModel`` consumes with predicted odometry (fg_scene_dataset.py:465-492), float32 [T_in + 3, 5].
+
+    ``inp_odom`` [T_in, 5] measured rows of the input frames, ``odom_preds`` [>= 9, 2] this snippet's forecast (the export's
+    rows), ``inp_times`` the timestamps of every frame from the first to the last input frame: each forecast row becomes
+    ``[speed, yaw_rate, x, y, theta]`` with the planar motion of ``dt = mean(diff(inp_times))`` (``ego.planar_motion``),
+    and rows 2, 5 and 8 follow the inputs.
+    """
+    times = np.asarray(inp_times)
+    dt = np.mean(times[1:] - times[:-1])
+    rows = []
+    for speed, yaw_rate in np.asarray(odom_preds)[:, :2]:
+        x, y, theta = ego.planar_motion(speed, yaw_rate, dt)
+        rows.append(np.array([speed, yaw_rate, x, y, theta]))
+    final = np.stack(rows)[list(FG_FUTURE_ROWS)]
+    return np.concatenate([np.asarray(inp_odom), final]).astype(np.float32)
+
+
 def write_npz(path, entries):
     """entries: {(city, seq, frame, start_frame): [n,2] array} -> .npz with the H5 key names."""
     np.savez_compressed(path, **{odom_key(*k): np.asarray(v, dtype=np.float32) for k, v in entries.items()})

@@ -3,8 +3,8 @@
 Call contract of the reference's ``panoptic_forecasting.models.build_model`` (``models/__init__.py:16-41``), so its
 experiment scripts run with one import changed: the task comes from ``params['task']``; the model is
 moved to the GPU unless ``params['no_gpu']``; ``load_best_model`` restores ``<working_dir>/best_model``, otherwise
-``load_model`` names a checkpoint.  The task outside the hot path (``odom``) is refused with a pointer to the
-reference — this package has no fallback implementations.
+``load_model`` names a checkpoint.  All four reference tasks are built (``odom``: the shipped odom config, see
+``odom_model.check_config``); this package has no fallback implementations.
 """
 import importlib
 import os
@@ -17,8 +17,8 @@ _TASKS = {
     'pc_transform': ('pc_transform_model', 'PCTransformModel'),
     'bg_forecast': ('bg_forecast_model', 'BGForecastModel'),       # the two stages fused on the device (new)
     'fg': ('fg_model', 'FGModel'),                                  # shipped fg config only (fg_model.check_config)
+    'odom': ('odom_model', 'OdomModel'),                            # simple_odom only (odom_model.check_config)
 }
-_OUT_OF_SCOPE = ('odom',)
 
 
 def _checkpoint_path(params):
@@ -30,8 +30,6 @@ def _checkpoint_path(params):
 def build_model(params):
     task = params['task']
     print("Building model for task: ", task)          # the reference announces the task the same way
-    if task in _OUT_OF_SCOPE:
-        raise ValueError('task %r is outside the MI355X hot path (SURVEY.md §8): use the reference for it' % task)
     if task not in _TASKS:
         raise ValueError('task not recognized: ', task)
     module, cls = _TASKS[task]

@@ -5,11 +5,10 @@
 // "concatenation" (hardnet.py:225-230) as up to four channel ranges of earlier tensors instead of a
 // torch.cat copy.
 #pragma once
+#include "pf_blob.h"
 #include "pf_common.h"
 
 namespace pf {
-
-constexpr int kConvMaxSrc = 4;
 
 struct ConvArgs {
     const float *src[kConvMaxSrc];   // base of each source tensor [B, ctotal, Hin, Win]

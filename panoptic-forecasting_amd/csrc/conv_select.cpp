@@ -4,7 +4,6 @@
 namespace pf {
 
 ConvChoice g_conv_force = {0, 0, 0, 0};
-int g_opt_use_tuned = 1;   // pf_set_option("use_tuned_table", 0/1)
 
 namespace {
 struct Tuned {

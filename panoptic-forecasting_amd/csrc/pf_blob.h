@@ -1,4 +1,4 @@
-// Weight-blob layout (written by panoptic-forecasting_amd/packing.py, read by hardnet_plan.hip).
+// Weight-blob layout (written by panoptic-forecasting_amd/packing.py, read by pf_net.cpp).
 #pragma once
 #include <cstdint>
 
@@ -6,7 +6,7 @@ namespace pf {
 
 constexpr char kBlobMagic[8] = {'P', 'F', 'H', 'N', 'E', 'T', '0', '2'};
 constexpr uint32_t kBlobVersion = 2;
-constexpr int kMaxSrc = 4;
+constexpr int kConvMaxSrc = 4;   // channel ranges a conv reads (BlobOp, ConvArgs)
 
 enum OpKind : uint32_t { OP_STEM = 0, OP_CONV = 1, OP_POOL = 2, OP_UPSAMPLE = 3, OP_HEAD = 4 };
 
@@ -25,7 +25,7 @@ struct BlobSrc {
 };
 struct BlobOp {  // 128 B
     uint32_t kind, k, stride, relu, cin, cout, n_src, dst, dst_choff, pad[3];
-    BlobSrc src[kMaxSrc];
+    BlobSrc src[kConvMaxSrc];
     uint64_t w_off, b_off;  // in floats from weights_off
     uint8_t pad2[16];
 };

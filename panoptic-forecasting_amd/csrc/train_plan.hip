@@ -27,8 +27,7 @@
 #include <map>
 #include <vector>
 
-#include "net_kernels.h"
-#include "pf_blob.h"
+#include "hardnet_plan.h"
 #include "pf_prof.h"
 #include "train_kernels.h"
 
@@ -43,9 +42,7 @@ using namespace pf;
 static_assert(PF_TRAIN_DY_SLOTS % PF_TRAIN_SIDE_STREAMS == 0, "a dy slot belongs to one side stream");
 
 struct pf_train {
-    BlobHeader hdr;
-    std::vector<BlobTensor> tensors;
-    std::vector<BlobOp> ops;
+    NetTable net;
     std::vector<size_t> w_off, aux_off;   // per op (floats into theta); aux = gamma (BN) or bias
     std::vector<int> bn;                  // per op: 1 = conv + BN (+ ReLU), 0 = plain conv with bias
     size_t n_params = 0;
@@ -73,10 +70,12 @@ struct pf_train {
     mutable std::vector<std::array<int, 5>> measured_configs;
 };
 
-namespace pf {
-extern int g_opt_train_kacc;
-extern int g_opt_train_side, g_opt_use_tuned, g_opt_up_two_pass, g_opt_train_table_batch;
-extern int g_opt_train_s4;      // train_forward_s4: the forward convolutions of a step on the packed-pair kernels (train_s4.hip)
+namespace pf {   // the process-wide switches of the training step (pf_set_option: plan_create.hip)
+int g_opt_up_two_pass = 1;         // upsample_bwd_two_pass: the bilinear transposes of large planes as rows-then-columns passes (train_kernels.hip)
+int g_opt_train_table_batch = 0;   // train_table_batch: batch size the rows of train_tuned.inc are looked up with (0 = the call's own)
+int g_opt_train_kacc = 1;          // train_blocked_sum: per-round partial sums in the 3x3 convolutions of a training step (conv_dma.hip: KACC)
+int g_opt_train_s4 = 0;            // train_forward_s4: the forward convolutions of a training step on conv_s4 with blocked sums (train_s4.hip); opt-in
+int g_opt_train_side = 1;          // train_side_stream: weight gradients on the training plan's own stream
 }
 
 namespace {
@@ -91,46 +90,20 @@ const TrainTuned kTrainTuned[] = {
 #include "train_tuned.inc"
     {{0, 0, 0, 0, 0, 0, 0, 0}, 0, 0}};
 
-struct TDims {
-    int h = 0, w = 0;
-};
-
-int t_propagate(const pf_train *p, int H, int W, std::vector<TDims> &d) {
-    d.assign(p->tensors.size(), TDims());
-    d[p->ops[0].src[0].tensor] = {H, W};
-    for (const BlobOp &o : p->ops) {
-        const TDims in = d[o.src[0].tensor];
-        if (in.h <= 0 || in.w <= 0) return fail(PF_EBLOB, "op reads a tensor that was never produced");
-        TDims out = in;
-        if (o.kind == OP_STEM || o.kind == OP_CONV) {
-            const int pad = o.k / 2;
-            out.h = (in.h + 2 * pad - (int)o.k) / (int)o.stride + 1;
-            out.w = (in.w + 2 * pad - (int)o.k) / (int)o.stride + 1;
-        } else if (o.kind == OP_POOL) {
-            out = {in.h / 2, in.w / 2};
-        } else if (o.kind == OP_UPSAMPLE) {
-            out = d[o.src[1].tensor];
-        }
-        if (out.h <= 0 || out.w <= 0) return fail(PF_EINVAL, "input %dx%d is too small for this network", H, W);
-        if (o.kind != OP_HEAD) d[o.dst] = out;
-    }
-    return PF_OK;
-}
-
 // Who writes a tensor's gradient first?  The backward pass visits the ops in reverse; every consumer of a tensor adds its
 // contribution to the tensor's gradient.  The first visitor of a channel range STORES instead (no cleared arena needed: the
 // arena is as large as all activations, 0.2 ms of fill per step at batch 8 of 800x800); a range that is only partly fresh keeps
 // the add and has its fresh channels cleared beforehand, as are channels no consumer ever writes (their producer reads them).
 struct GradFirst {
-    std::vector<std::array<uint8_t, kMaxSrc>> store;     // per op, per input range (conv / stem) or [0] (pool, upsample, head)
+    std::vector<std::array<uint8_t, kConvMaxSrc>> store;     // per op, per input range (conv / stem) or [0] (pool, upsample, head)
     std::vector<std::array<int, 3>> clear;               // (tensor, first channel, channels)
 };
-GradFirst grad_first_writers(const pf_train *p, const std::vector<TDims> &d) {
+GradFirst grad_first_writers(const pf_train *p, const std::vector<Dims> &d) {
     GradFirst g;
-    g.store.assign(p->ops.size(), std::array<uint8_t, kMaxSrc>{});
-    const uint32_t input = p->ops[0].src[0].tensor;
-    std::vector<std::vector<uint8_t>> touched(p->tensors.size());
-    for (size_t t = 0; t < p->tensors.size(); ++t) touched[t].assign(p->tensors[t].channels, 0);
+    g.store.assign(p->net.ops.size(), std::array<uint8_t, kConvMaxSrc>{});
+    const uint32_t input = p->net.ops[0].src[0].tensor;
+    std::vector<std::vector<uint8_t>> touched(p->net.tensors.size());
+    for (size_t t = 0; t < p->net.tensors.size(); ++t) touched[t].assign(p->net.tensors[t].channels, 0);
     auto add_clear = [&](uint32_t t, const std::vector<uint8_t> &want) {       // runs of channels
         for (size_t c = 0; c < want.size();) {
             if (!want[c]) { ++c; continue; }
@@ -140,29 +113,29 @@ GradFirst grad_first_writers(const pf_train *p, const std::vector<TDims> &d) {
             c = e;
         }
     };
-    for (size_t ii = p->ops.size(); ii-- > 0;) {
-        const BlobOp &o = p->ops[ii];
+    for (size_t ii = p->net.ops.size(); ii-- > 0;) {
+        const BlobOp &o = p->net.ops[ii];
         const uint32_t nj = (o.kind == OP_STEM || o.kind == OP_CONV) ? o.n_src : 1;
         for (uint32_t j = 0; j < nj; ++j) {
             const uint32_t t = o.src[j].tensor;
             if (t == input) continue;
             const bool whole = !(o.kind == OP_STEM || o.kind == OP_CONV);      // pool / upsample / head write the whole tensor
-            const uint32_t c0 = whole ? 0 : o.src[j].choff, n = whole ? p->tensors[t].channels : o.src[j].ch;
+            const uint32_t c0 = whole ? 0 : o.src[j].choff, n = whole ? p->net.tensors[t].channels : o.src[j].ch;
             uint32_t fresh = 0;
             for (uint32_t c = c0; c < c0 + n; ++c) fresh += !touched[t][c];
             if (fresh == n) {
                 g.store[ii][j] = 1;
             } else if (fresh) {
-                std::vector<uint8_t> want(p->tensors[t].channels, 0);
+                std::vector<uint8_t> want(p->net.tensors[t].channels, 0);
                 for (uint32_t c = c0; c < c0 + n; ++c) want[c] = !touched[t][c];
                 add_clear(t, want);
             }
             for (uint32_t c = c0; c < c0 + n; ++c) touched[t][c] = 1;
         }
     }
-    for (size_t t = 0; t < p->tensors.size(); ++t) {
+    for (size_t t = 0; t < p->net.tensors.size(); ++t) {
         if (t == input || !d[t].h) continue;
-        std::vector<uint8_t> want(p->tensors[t].channels, 0);
+        std::vector<uint8_t> want(p->net.tensors[t].channels, 0);
         bool any = false;
         for (size_t c = 0; c < want.size(); ++c) any |= (want[c] = !touched[t][c]) != 0;
         if (any) add_clear((uint32_t)t, want);
@@ -200,42 +173,42 @@ struct TLayout {
 // may op i's forward convolution run on conv_s4?  conv + BatchNorm, 3x3 / 1x1, stride 1, every input range at an even channel of a
 // tensor some op produced (the network input stays dense fp32: the stem reads it)
 bool s4_fwd_ok(const pf_train *p, size_t i) {
-    const BlobOp &o = p->ops[i];
+    const BlobOp &o = p->net.ops[i];
     if (!p->fwd_s4 || o.kind != OP_CONV || !p->bn[i] || o.stride != 1 || (o.k != 1 && o.k != 3) || o.n_src > (uint32_t)kConvMaxSrc) return false;
-    const uint32_t input = p->ops[0].src[0].tensor;
+    const uint32_t input = p->net.ops[0].src[0].tensor;
     for (uint32_t j = 0; j < o.n_src; ++j)
         if ((o.src[j].choff & 1) || o.src[j].tensor == input) return false;
     return true;
 }
 
-TLayout t_layout(const pf_train *p, int B, const std::vector<TDims> &d, int out_h, int out_w) {
+TLayout t_layout(const pf_train *p, int B, const std::vector<Dims> &d, int out_h, int out_w) {
     TLayout L;
-    const size_t nt = p->tensors.size();
+    const size_t nt = p->net.tensors.size();
     L.act.assign(nt, (size_t)-1);
     L.grad.assign(nt, (size_t)-1);
-    L.ypre.assign(p->ops.size(), (size_t)-1);
-    L.stat.assign(p->ops.size(), (size_t)-1);
-    L.xpad.assign(p->ops.size(), (size_t)-1);
+    L.ypre.assign(p->net.ops.size(), (size_t)-1);
+    L.stat.assign(p->net.ops.size(), (size_t)-1);
+    L.xpad.assign(p->net.ops.size(), (size_t)-1);
     size_t cur = 0;
     auto take = [&](size_t bytes) {
         const size_t o = cur;
         cur += align_up(bytes, 256);
         return o;
     };
-    auto tbytes = [&](size_t t) { return (size_t)B * p->tensors[t].channels * d[t].h * d[t].w * sizeof(float); };
+    auto tbytes = [&](size_t t) { return (size_t)B * p->net.tensors[t].channels * d[t].h * d[t].w * sizeof(float); };
     for (size_t t = 0; t < nt; ++t)
         if (d[t].h) L.act[t] = take(tbytes(t));
     L.grad_begin = cur;
-    const uint32_t input = p->ops[0].src[0].tensor;
+    const uint32_t input = p->net.ops[0].src[0].tensor;
     for (size_t t = 0; t < nt; ++t)
         if (d[t].h && t != input) L.grad[t] = take(tbytes(t));
     L.grad_end = cur;
-    L.odd.assign(p->ops.size(), 0);
+    L.odd.assign(p->net.ops.size(), 0);
     size_t max_dy = 0, max_wpart = 0, max_c = 16, max_pin = 256, max_pout = 256;
-    for (size_t i = 0; i < p->ops.size(); ++i) {
-        const BlobOp &o = p->ops[i];
+    for (size_t i = 0; i < p->net.ops.size(); ++i) {
+        const BlobOp &o = p->net.ops[i];
         if (o.kind != OP_STEM && o.kind != OP_CONV) continue;
-        const TDims in = d[o.src[0].tensor], out = d[o.dst];
+        const Dims in = d[o.src[0].tensor], out = d[o.dst];
         L.odd[i] = (in.w & 3) && o.stride == 1;
         // the conv output (y, dy) in padded rows on an odd level
         const size_t ybytes = (size_t)B * o.cout * out.h * (L.odd[i] ? (out.w + 3) / 4 * 4 : out.w) * sizeof(float);
@@ -261,9 +234,9 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<TDims> &d, int out_
     }
     // the step's packing jobs (the padded copies of odd-width levels read ONE gathered range)
     {
-        L.fwd_job.assign(p->ops.size(), -1);
-        L.bwd_job.assign(p->ops.size(), std::vector<int>());
-        L.bwd_all_job.assign(p->ops.size(), -1);
+        L.fwd_job.assign(p->net.ops.size(), -1);
+        L.bwd_job.assign(p->net.ops.size(), std::vector<int>());
+        L.bwd_all_job.assign(p->net.ops.size(), -1);
         size_t arena = 0;
         auto add = [&](size_t w_off, int cin_f, int cout_f, int ks, int stride, const int *chs, int ns, int tflip, int c0, int ch) {
             PackJob q;
@@ -272,18 +245,18 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<TDims> &d, int out_
             L.jobs.push_back(q);
             return (int)L.jobs.size() - 1;
         };
-        for (size_t i = 0; i < p->ops.size(); ++i) {
-            const BlobOp &o = p->ops[i];
+        for (size_t i = 0; i < p->net.ops.size(); ++i) {
+            const BlobOp &o = p->net.ops[i];
             if (o.kind != OP_STEM && o.kind != OP_CONV) continue;
-            const TDims in = d[o.src[0].tensor];
-            int src_ch[kMaxSrc];
+            const Dims in = d[o.src[0].tensor];
+            int src_ch[kConvMaxSrc];
             for (uint32_t j = 0; j < o.n_src; ++j) src_ch[j] = (int)o.src[j].ch;
             const int one = (int)o.cin;
             const bool aligned = (in.w & 3) == 0;
             L.fwd_job[i] = add(p->w_off[i], (int)o.cin, (int)o.cout, (int)o.k, (int)o.stride, aligned ? src_ch : &one, aligned ? (int)o.n_src : 1, 0, 0, 0);
         }
-        for (size_t i = 0; i < p->ops.size(); ++i) {
-            const BlobOp &o = p->ops[i];
+        for (size_t i = 0; i < p->net.ops.size(); ++i) {
+            const BlobOp &o = p->net.ops[i];
             if (o.kind != OP_STEM && o.kind != OP_CONV) continue;
             L.bwd_job[i].assign(o.n_src, -1);
             int c0 = 0;
@@ -302,12 +275,12 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<TDims> &d, int out_
     // the forward convolutions that run on the packed-pair kernels: their device-side weight packings, and the shadows of the tensors they read
     {
         L.s4act.assign(nt, (size_t)-1);
-        L.s4_job.assign(p->ops.size(), -1);
+        L.s4_job.assign(p->net.ops.size(), -1);
         std::vector<char> need(nt, 0);
         size_t arena = 0;
-        for (size_t i = 0; i < p->ops.size(); ++i) {
+        for (size_t i = 0; i < p->net.ops.size(); ++i) {
             if (!s4_fwd_ok(p, i)) continue;
-            const BlobOp &o = p->ops[i];
+            const BlobOp &o = p->net.ops[i];
             S4Range rg[kConvMaxSrc];
             for (uint32_t j = 0; j < o.n_src; ++j) {
                 rg[j] = S4Range{(int)o.src[j].choff, (int)o.src[j].ch};
@@ -321,7 +294,7 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<TDims> &d, int out_
             L.s4jobs.push_back(jb);
         }
         for (size_t t = 0; t < nt; ++t)
-            if (need[t] && d[t].h) L.s4act[t] = take((size_t)B * 2 * ((p->tensors[t].channels + 3) / 4) * d[t].h * ((d[t].w + 3) / 4 * 4) * 8);
+            if (need[t] && d[t].h) L.s4act[t] = take((size_t)B * 2 * ((p->net.tensors[t].channels + 3) / 4) * d[t].h * ((d[t].w + 3) / 4 * 4) * 8);
         L.s4w_arena = take(arena * sizeof(float) + 256);
     }
     if (p->autotune) L.tune_grad = take(p->n_params * sizeof(float));
@@ -333,12 +306,12 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<TDims> &d, int out_
         for (int k = 1; k < pf_train::kSideStreams; ++k) L.wpart_more[k] = take(max_wpart * sizeof(float));
     L.pad_in = take(max_pin);
     L.pad_out = take(max_pout);
-    L.dfull = take((size_t)B * p->hdr.n_cls * out_h * out_w * sizeof(float));
+    L.dfull = take((size_t)B * p->net.hdr.n_cls * out_h * out_w * sizeof(float));
     {
         size_t mx = 0;
-        for (size_t i = 0; i < p->ops.size(); ++i) {
-            const BlobOp &o = p->ops[i];
-            const TDims in = d[o.src[0].tensor];
+        for (size_t i = 0; i < p->net.ops.size(); ++i) {
+            const BlobOp &o = p->net.ops[i];
+            const Dims in = d[o.src[0].tensor];
             size_t n = 0;
             if (o.kind == OP_HEAD) n = upsample_bwd_tmp_floats(B * (int)o.cin, in.h, in.w, out_h, out_w);
             else if (o.kind == OP_UPSAMPLE) n = upsample_bwd_tmp_floats(B * (int)o.cin, in.h, in.w, d[o.dst].h, d[o.dst].w);
@@ -357,37 +330,21 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<TDims> &d, int out_
 
 extern "C" int pf_train_create(const void *blob, size_t bytes, int in_ch, int n_cls, pf_train **out) {
     if (!blob || !out) return fail(PF_EINVAL, "pf_train_create: null argument");
-    if (bytes < sizeof(BlobHeader)) return fail(PF_EBLOB, "blob shorter than its header");
-    BlobHeader h;
-    memcpy(&h, blob, sizeof(h));
-    if (memcmp(h.magic, kBlobMagic, 8) != 0 || h.version != kBlobVersion) return fail(PF_EBLOB, "bad blob magic/version");
-    if (h.total_bytes != bytes || h.tensor_off + (uint64_t)h.n_tensors * sizeof(BlobTensor) > bytes ||
-        h.op_off + (uint64_t)h.n_ops * sizeof(BlobOp) > bytes)
-        return fail(PF_EBLOB, "blob table offsets out of range");
-    if ((int)h.in_ch != in_ch || (int)h.n_cls != n_cls) return fail(PF_EINVAL, "blob is for in_ch=%u n_cls=%u", h.in_ch, h.n_cls);
     pf_train *p = new pf_train();
-    p->hdr = h;
-    p->tensors.resize(h.n_tensors);
-    p->ops.resize(h.n_ops);
-    memcpy(p->tensors.data(), (const char *)blob + h.tensor_off, h.n_tensors * sizeof(BlobTensor));
-    memcpy(p->ops.data(), (const char *)blob + h.op_off, h.n_ops * sizeof(BlobOp));
-    p->w_off.assign(h.n_ops, 0);
-    p->aux_off.assign(h.n_ops, 0);
-    p->bn.assign(h.n_ops, 0);
+    if (int rc = parse_net_table(blob, bytes, in_ch, n_cls, p->net)) {
+        delete p;
+        return rc;
+    }
+    const size_t n_ops = p->net.ops.size();
+    p->w_off.assign(n_ops, 0);
+    p->aux_off.assign(n_ops, 0);
+    p->bn.assign(n_ops, 0);
     size_t cur = 0;
-    for (size_t i = 0; i < p->ops.size(); ++i) {
-        const BlobOp &o = p->ops[i];
-        bool ok = o.n_src >= 1 && o.n_src <= (uint32_t)kMaxSrc && o.dst < h.n_tensors;
-        uint32_t cin = 0;
-        for (uint32_t j = 0; ok && j < o.n_src; ++j) {
-            ok = o.src[j].tensor < h.n_tensors && o.src[j].choff + o.src[j].ch <= p->tensors[o.src[j].tensor].channels;
-            cin += o.src[j].ch;
-        }
-        if (!ok) {
-            delete p;
-            return fail(PF_EBLOB, "op %zu is inconsistent with the tensor table", i);
-        }
+    for (size_t i = 0; i < n_ops; ++i) {
+        const BlobOp &o = p->net.ops[i];
         if (o.kind != OP_STEM && o.kind != OP_CONV) continue;
+        uint32_t cin = 0;
+        for (uint32_t j = 0; j < o.n_src; ++j) cin += o.src[j].ch;
         if (cin != o.cin || !((o.k == 3 && (o.stride == 1 || o.stride == 2)) || (o.k == 1 && o.stride == 1))) {
             delete p;
             return fail(PF_EUNSUPPORTED, "op %zu: training supports 3x3 (stride 1/2) and 1x1 convs", i);
@@ -476,8 +433,8 @@ extern "C" int pf_train_param_count(const pf_train *p, size_t *n_floats) {
 }
 
 extern "C" int pf_train_param_layout(const pf_train *p, int op_index, size_t *w_off, size_t *aux_off, int *has_bn) {
-    if (!p || op_index < 0 || (size_t)op_index >= p->ops.size() || !w_off || !aux_off || !has_bn) return fail(PF_EINVAL, "pf_train_param_layout: bad argument");
-    const BlobOp &o = p->ops[op_index];
+    if (!p || op_index < 0 || (size_t)op_index >= p->net.ops.size() || !w_off || !aux_off || !has_bn) return fail(PF_EINVAL, "pf_train_param_layout: bad argument");
+    const BlobOp &o = p->net.ops[op_index];
     if (o.kind != OP_STEM && o.kind != OP_CONV) return fail(PF_EINVAL, "op %d is not a convolution", op_index);
     *w_off = p->w_off[op_index];
     *aux_off = p->aux_off[op_index];
@@ -487,8 +444,8 @@ extern "C" int pf_train_param_layout(const pf_train *p, int op_index, size_t *w_
 
 extern "C" int pf_train_workspace(const pf_train *p, int B, int H, int W, int out_h, int out_w, size_t *bytes) {
     if (!p || !bytes || B <= 0 || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0) return fail(PF_EINVAL, "pf_train_workspace: bad argument");
-    std::vector<TDims> d;
-    int rc = t_propagate(p, H, W, d);
+    std::vector<Dims> d;
+    int rc = propagate_dims(p->net, H, W, d);
     if (rc) return rc;
     *bytes = t_layout(p, B, d, out_h, out_w).total;
     return PF_OK;
@@ -497,15 +454,15 @@ extern "C" int pf_train_workspace(const pf_train *p, int B, int H, int W, int ou
 extern "C" int pf_train_tensor_view(const pf_train *p, const char *name, int want_grad, int B, int H, int W, int out_h, int out_w,
                                     size_t *ws_offset, int *channels, int *h, int *w) {
     if (!p || !name || !ws_offset || !channels || !h || !w) return fail(PF_EINVAL, "pf_train_tensor_view: null");
-    std::vector<TDims> d;
-    int rc = t_propagate(p, H, W, d);
+    std::vector<Dims> d;
+    int rc = propagate_dims(p->net, H, W, d);
     if (rc) return rc;
     const TLayout L = t_layout(p, B, d, out_h, out_w);
-    for (size_t t = 0; t < p->tensors.size(); ++t)
-        if (strncmp(p->tensors[t].name, name, sizeof(p->tensors[t].name)) == 0) {
+    for (size_t t = 0; t < p->net.tensors.size(); ++t)
+        if (strncmp(p->net.tensors[t].name, name, sizeof(p->net.tensors[t].name)) == 0) {
             const size_t off = want_grad ? L.grad[t] : L.act[t];
             if (off == (size_t)-1) return fail(PF_EINVAL, "tensor '%s' has no %s buffer", name, want_grad ? "gradient" : "activation");
-            *ws_offset = off; *channels = (int)p->tensors[t].channels; *h = d[t].h; *w = d[t].w;
+            *ws_offset = off; *channels = (int)p->net.tensors[t].channels; *h = d[t].h; *w = d[t].w;
             return PF_OK;
         }
     return fail(PF_EINVAL, "no tensor named '%s'", name);
@@ -536,7 +493,7 @@ struct TOneHotArgs { const void *seg; int seg_i64; const float *depth; const uin
 struct TPackArgs { const float *theta; float *arena; const void *jobs; int n; };   // PackJob / S4WJob list
 struct TZeroChArgs { float *t; int ctotal, c0, n; long long hw; };
 struct TUnpadArgs { const float *src; int C, H, W, Wp; float *dst; int ctotal, choff, accum; };
-struct TUnpadMultiArgs { const float *src; int C, H, W, Wp, n; float *dst[kMaxSrc]; int ctotal[kMaxSrc], choff[kMaxSrc], ch[kMaxSrc], overwrite[kMaxSrc]; };
+struct TUnpadMultiArgs { const float *src; int C, H, W, Wp, n; float *dst[kConvMaxSrc]; int ctotal[kConvMaxSrc], choff[kConvMaxSrc], ch[kConvMaxSrc], overwrite[kConvMaxSrc]; };
 struct TBnFwdArgs {
     const float *y; int C, H, W; float eps, momentum; const float *gamma, *beta; float *rmean, *rvar, *mean, *invstd; double *part;
     float *dst; int dst_ctotal, dst_choff, relu, y_pitch;
@@ -619,18 +576,18 @@ ConvArgs over_buffer(ConvArgs c, const float *x, int cin, int win, int wout) {
 // the call's theta, gradient and workspace.  Kernel choices are made here, through predicates: a geometry without a kernel
 // fails before anything is enqueued.  measuring: the autotune pass - a conv_dma geometry this plan has not measured is measured
 // at enqueue time (T_CONV_DMA_MEASURE)
-int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<TDims> &d, const TLayout &L, const GradFirst &gfirst,
+int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<Dims> &d, const TLayout &L, const GradFirst &gfirst,
                          bool measuring, std::vector<TStep> &steps) {
     // the options read per call
-    const int kacc = g_opt_train_kacc, use_tuned = g_opt_use_tuned, table_batch = g_opt_train_table_batch;
+    const int kacc = g_opt_train_kacc, use_tuned = g_plan_opt.use_tuned_table, table_batch = g_opt_train_table_batch;
     const bool tagged = prof_enabled();
     const int B = k.B;
     char *wsb = (char *)k.ws;
     auto buf = [&](size_t off) { return reinterpret_cast<float *>(wsb + off); };
     auto act = [&](uint32_t t) { return buf(L.act[t]); };
     auto gradt = [&](uint32_t t) { return buf(L.grad[t]); };
-    const uint32_t input = p->ops[0].src[0].tensor;
-    const int in_ch = (int)p->tensors[input].channels, n_cls = (int)p->hdr.n_cls;
+    const uint32_t input = p->net.ops[0].src[0].tensor;
+    const int in_ch = (int)p->net.tensors[input].channels, n_cls = (int)p->net.hdr.n_cls;
     float *dy_slot[pf_train::kDySlots];
     for (int j = 0; j < pf_train::kDySlots; ++j) dy_slot[j] = buf(p->side && j ? L.dy_more[j] : L.dy);
     float *wpk_arena = buf(L.wpk_arena), *pad_in = buf(L.pad_in), *pad_out = buf(L.pad_out), *dfull = buf(L.dfull);
@@ -643,14 +600,14 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<TD
         st.kind = kind; st.stats = stats; st.side = side; st.slot = slot;
         return st;
     };
-    auto conv_args = [&](const BlobOp &o, const TDims &in, const TDims &out) {
+    auto conv_args = [&](const BlobOp &o, const Dims &in, const Dims &out) {
         ConvArgs a;
         memset(&a, 0, sizeof(a));
         a.n_src = (int)o.n_src;
         int c0 = 0;
         for (int j = 0; j < a.n_src; ++j) {
             a.src[j] = act(o.src[j].tensor);
-            a.src_ctotal[j] = (int)p->tensors[o.src[j].tensor].channels;
+            a.src_ctotal[j] = (int)p->net.tensors[o.src[j].tensor].channels;
             a.src_choff[j] = (int)o.src[j].choff;
             a.src_cstart[j] = c0;
             c0 += (int)o.src[j].ch;
@@ -729,10 +686,10 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<TD
     // the packed-pair shadow of channels [c0, c1) of tensor t, for the convolutions that read it through conv_s4
     // (a slice that starts or ends in the middle of a 4-channel group also zero-fills the group's other half while no producer has
     //  written it in this pass: a reader of this slice multiplies those channels by zero weights, and 0 x a stale NaN pattern is NaN)
-    std::vector<std::vector<char>> s4_written(p->tensors.size());
+    std::vector<std::vector<char>> s4_written(p->net.tensors.size());
     auto shadow = [&](uint32_t t, int c0, int c1) {
         if (L.s4act[t] == (size_t)-1) return;
-        const int ct = (int)p->tensors[t].channels;
+        const int ct = (int)p->net.tensors[t].channels;
         std::vector<char> &wr = s4_written[t];
         if (wr.empty()) wr.assign((size_t)ct + 4, 0);
         const int fill_lo = (c0 & 2) && !wr[c0 - 2], fill_up = (c1 & 3) == 2 && c1 < ct && !wr[c1];
@@ -751,21 +708,21 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<TD
     add(T_PACK_TILED).u.pack = {k.theta, wpk_arena, L.jobs.data(), (int)L.jobs.size()};
     if (!L.s4jobs.empty()) add(T_PACK_S4).u.pack = {k.theta, buf(L.s4w_arena), L.s4jobs.data(), (int)L.s4jobs.size()};
     for (const auto &c : gfirst.clear)     // (no cleared gradient arena: first writers store)
-        add(T_ZERO_CHANNELS).u.zch = {gradt((uint32_t)c[0]), (int)p->tensors[c[0]].channels, c[1], c[2], (long long)d[c[0]].h * d[c[0]].w};
+        add(T_ZERO_CHANNELS).u.zch = {gradt((uint32_t)c[0]), (int)p->net.tensors[c[0]].channels, c[1], c[2], (long long)d[c[0]].h * d[c[0]].w};
     if (!k.accumulate_grads) add(T_ZERO_FILL).u.copy = {k.grad, nullptr, p->n_params * sizeof(float)};
 
     // ================================================================ forward (training mode)
-    for (size_t i = 0; i < p->ops.size(); ++i) {
-        const BlobOp &o = p->ops[i];
-        const TDims in = d[o.src[0].tensor];
-        const TDims out = o.kind == OP_HEAD ? in : d[o.dst];
+    for (size_t i = 0; i < p->net.ops.size(); ++i) {
+        const BlobOp &o = p->net.ops[i];
+        const Dims in = d[o.src[0].tensor];
+        const Dims out = o.kind == OP_HEAD ? in : d[o.dst];
         if (o.kind == OP_STEM || o.kind == OP_CONV) {
             ConvArgs a = conv_args(o, in, out);
             float *gather = L.odd[i] ? buf(L.xpad[i]) : pad_in;     // (an odd op keeps its copy for the weight gradient)
             const int Wp = (in.w + 3) / 4 * 4;
             if (!p->bn[i]) {
                 a.bias = k.theta + p->aux_off[i];
-                a.dst = act(o.dst); a.dst_ctotal = (int)p->tensors[o.dst].channels; a.dst_choff = (int)o.dst_choff; a.relu = (int)o.relu;
+                a.dst = act(o.dst); a.dst_ctotal = (int)p->net.tensors[o.dst].channels; a.dst_choff = (int)o.dst_choff; a.relu = (int)o.relu;
                 if ((rc = conv(a, (int)o.k, (int)o.stride, L.fwd_job[i], gather, false))) return rc;
                 shadow(o.dst, (int)o.dst_choff, (int)o.dst_choff + (int)o.cout);
                 continue;
@@ -808,15 +765,15 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<TD
             float *aux = k.theta + p->aux_off[i], *stat = buf(L.stat[i]);
             add(T_BN_FWD).u.bnf = {y, (int)o.cout, out.h, out.w, k.bn_eps, k.bn_momentum, aux, aux + o.cout,
                                    k.update_running_stats ? aux + 2 * o.cout : nullptr, k.update_running_stats ? aux + 3 * o.cout : nullptr,
-                                   stat, stat + o.cout, bnpart, act(o.dst), (int)p->tensors[o.dst].channels, (int)o.dst_choff, (int)o.relu,
+                                   stat, stat + o.cout, bnpart, act(o.dst), (int)p->net.tensors[o.dst].channels, (int)o.dst_choff, (int)o.relu,
                                    L.odd[i] ? (out.w + 3) / 4 * 4 : 0};
             shadow(o.dst, (int)o.dst_choff, (int)o.dst_choff + (int)o.cout);
         } else if (o.kind == OP_POOL) {
             add(T_POOL).u.plain = {act(o.src[0].tensor), act(o.dst), B * (int)o.cin, in.h, in.w, 0, 0, 0};
-            shadow(o.dst, 0, (int)p->tensors[o.dst].channels);
+            shadow(o.dst, 0, (int)p->net.tensors[o.dst].channels);
         } else if (o.kind == OP_UPSAMPLE) {
             add(T_UPSAMPLE).u.plain = {act(o.src[0].tensor), act(o.dst), B * (int)o.cin, in.h, in.w, out.h, out.w, 0};
-            shadow(o.dst, 0, (int)p->tensors[o.dst].channels);
+            shadow(o.dst, 0, (int)p->net.tensors[o.dst].channels);
         } else if (o.kind == OP_HEAD) {
             add(T_CE).u.ce = {act(o.src[0].tensor), (int)o.cin, in.h, in.w, k.labels, k.labels_i64, k.out_h, k.out_w, k.ignore_index, dfull, cepart, loss3};
             add(T_COPY).u.copy = {k.out3, loss3, 3 * sizeof(double)};
@@ -828,10 +785,10 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<TD
     // copy of x) reads it on side stream n % kSideStreams while the caller's stream goes on to the input gradients and the next
     // layers; before it overwrites a slot it waits for the weight gradient of layer n - kDySlots that last read it.
     int n_conv = 0;
-    for (size_t ii = p->ops.size(); ii-- > 0;) {
-        const BlobOp &o = p->ops[ii];
-        const TDims in = d[o.src[0].tensor];
-        const TDims out = o.kind == OP_HEAD ? in : d[o.dst];
+    for (size_t ii = p->net.ops.size(); ii-- > 0;) {
+        const BlobOp &o = p->net.ops[ii];
+        const Dims in = d[o.src[0].tensor];
+        const Dims out = o.kind == OP_HEAD ? in : d[o.dst];
         const int store = gfirst.store[ii][0];
         if (o.kind == OP_HEAD) {
             // d loss / d logits = bilinear^T (softmax - onehot) * loss_scale / n_valid   (mean over the valid pixels, bg_model.py:81)
@@ -842,7 +799,7 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<TD
             add(T_UPSAMPLE_BWD).u.upb = {gradt(o.dst), B * (int)o.cin, in.h, in.w, out.h, out.w, nullptr, 1.f, !store, gradt(o.src[0].tensor), up_tmp};
         } else if (o.kind == OP_STEM || o.kind == OP_CONV) {
             if (!p->bn[ii] && o.relu) return fail(PF_EUNSUPPORTED, "training: ReLU without BatchNorm (op %zu)", ii);
-            const int t_ctotal = (int)p->tensors[o.dst].channels;
+            const int t_ctotal = (int)p->net.tensors[o.dst].channels;
             float *aux = k.theta + p->aux_off[ii], *gaux = k.grad + p->aux_off[ii];
             const int slot = n_conv % pf_train::kDySlots, sidx = n_conv % pf_train::kSideStreams;
             float *dy = dy_slot[slot];
@@ -889,7 +846,7 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<TD
                 m = {pad_out, (int)o.cin, in.h, in.w, Wp, (int)o.n_src, {}, {}, {}, {}, {}};
                 for (uint32_t j = 0; j < o.n_src; ++j) {
                     m.dst[j] = o.src[j].tensor != input ? gradt(o.src[j].tensor) : nullptr;
-                    m.ctotal[j] = (int)p->tensors[o.src[j].tensor].channels;
+                    m.ctotal[j] = (int)p->net.tensors[o.src[j].tensor].channels;
                     m.choff[j] = (int)o.src[j].choff;
                     m.ch[j] = (int)o.src[j].ch;
                     m.overwrite[j] = gfirst.store[ii][j];
@@ -899,7 +856,7 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<TD
             for (uint32_t j = 0; j < o.n_src; ++j) {
                 const uint32_t t = o.src[j].tensor;
                 if (t == input) continue;
-                const ConvArgs b = bwd_data_args(dsrc, (int)o.cout, (int)o.src[j].ch, in.h, in.w, gradt(t), (int)p->tensors[t].channels,
+                const ConvArgs b = bwd_data_args(dsrc, (int)o.cout, (int)o.src[j].ch, in.h, in.w, gradt(t), (int)p->net.tensors[t].channels,
                                                  (int)o.src[j].choff, gfirst.store[ii][j] ? 0 : 1);
                 if ((rc = conv(b, (int)o.k, 1, L.bwd_job[ii][j], pad_in, false))) return rc;
             }
@@ -914,8 +871,8 @@ int train_pass(const pf_train *p, TCall k, bool measuring) {
     if (!p || !k.theta || !k.grad || !k.labels || !k.out3 || !k.ws) return fail(PF_EINVAL, "pf_train_forward_backward: null pointer argument");
     if (!k.x_dense && (!k.seg || !k.depth || !k.depth_mask)) return fail(PF_EINVAL, "pf_train_forward_backward: pass seg+depth+depth_mask or x_dense");
     if (k.B <= 0 || k.H <= 0 || k.W <= 0 || k.out_h <= 0 || k.out_w <= 0) return fail(PF_EINVAL, "pf_train_forward_backward: bad dims");
-    std::vector<TDims> d;
-    int rc = t_propagate(p, k.H, k.W, d);
+    std::vector<Dims> d;
+    int rc = propagate_dims(p->net, k.H, k.W, d);
     if (rc) return rc;
     const TLayout L = t_layout(p, k.B, d, k.out_h, k.out_w);
     if (k.ws_bytes < L.total) return fail(PF_EWORKSPACE, "workspace %zu B < required %zu B", k.ws_bytes, L.total);

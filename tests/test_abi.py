@@ -51,7 +51,7 @@ def test_version_and_argument_errors_without_a_gpu():
 
 def test_every_documented_option_name_is_accepted():
     """include/pfhip.h documents the names pf_set_option takes: each is accepted (set to its documented default, so the process
-    keeps the library's behaviour), an unknown name is refused - the comment block and hardnet_plan.hip's table cannot drift apart."""
+    keeps the library's behaviour), an unknown name is refused - the comment block and plan_create.hip's table cannot drift apart."""
     import re
     text = open(os.path.join(ROOT, 'include', 'pfhip.h')).read()
     block = text[:text.index('int pf_set_option(const char *name, int value);')]

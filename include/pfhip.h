@@ -435,7 +435,12 @@ int pf_profile_get(int i, char *label, size_t label_cap, int *launches, double *
  * {1,2,4}, p1 = NT); 2 = conv_wave (p0 = rows per tile in {1,2,4}, p1 = NT in {1,2}, p2 = K-split waves in
  * {2,4,8,16}); 3 = conv_valu (3x3 only, p0 = rows per wave in {1,2}); 4 = conv_split (3x3 only, p0 = NT in {1,2,3},
  * p1 = 1 for 8x64-pixel tiles).  Shapes that are not built fall back to the automatic choice.  Process-wide, not
- * thread-safe. */
+ * thread-safe.
+ * The training step honours kind 1 only: while pf_debug_force_conv(1, wm, nt, 0) is set, every forward and backward-data
+ * convolution of pf_train_forward_backward (stride 2 included) runs conv_dma with wm pixel waves and min(nt, the layer's cout
+ * tiles) cout tiles per workgroup (wm = 1: at most 2; nt = 0: the cost model's count) instead of the shape of csrc/train_tuned.inc,
+ * the cost model or pf_train_autotune, and pf_train_path_stats counts it in none of stats[0..2] (tests: every built shape of the
+ * training convolutions against a reference). */
 int pf_debug_force_conv(int kind, int p0, int p1, int p2);
 /* Instrumented builds only (make libpfhip_probe.so, env PF_PROBE=1): the 64 in-kernel timestamps (shader clock)
  * written by workgroup 0 / wave 0 of the last conv_wave launch; PF_EINVAL when nothing was recorded. */

@@ -831,12 +831,7 @@ int launch_wgrad(const ConvArgs &a, int ks, int stride, const float *dy, int B, 
     const bool tiled = wgrad_tiled_ok(a.Win, a.Wout);
     if (wgrad_taps_wanted(g_opt_wgrad_taps, ks, stride, a.Cin, a.Cout, a.Hin, a.Win, a.Hout, a.Wout)) {
         const int co_pad = (a.Cout + 31) / 32 * 32, ci_pad = (a.Cin + 15) / 16 * 16;      // (what wgrad_partial_floats sized the buffer for)
-        const double flops = 2.0 * B * a.Hout * a.Wout * (double)a.Cout * a.Cin * ks * ks;
-        {
-            ProfScope ps(s, "wgrad_taps_kernel", flops, 4.0 * B * ((double)a.Cout * a.Hout * a.Wout + (double)a.Cin * a.Hin * a.Win));
-            int rc = launch_wgrad_taps(a, dy, B, slabs, co_pad, ci_pad, partial, &slabs, s);
-            if (rc) return rc;
-        }
+        if (int rc = launch_wgrad_taps(a, dy, B, slabs, co_pad, ci_pad, partial, &slabs, s)) return rc;      // (its profile scope carries the instantiation)
         const long long total = (long long)a.Cout * a.Cin * ks * ks;
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, partial, slabs, co_pad, ci_pad, ks * ks, a.Cout, a.Cin, dw);
         PF_LAUNCH_CHECK("wgrad_reduce_kernel");
@@ -850,8 +845,10 @@ int launch_wgrad(const ConvArgs &a, int ks, int stride, const float *dy, int B, 
     const dim3 grid(tiled ? (a.Cout + 31) / 32 : (a.Cout + 15) / 16, (a.Cin + 15) / 16, slabs);
     const double flops = 2.0 * B * a.Hout * a.Wout * (double)a.Cout * a.Cin * ks * ks;
     {
-        ProfScope ps(s, tiled ? "wgrad_tiled_kernel" : "wgrad_partial_kernel", flops,
-                     4.0 * B * ((double)a.Cout * a.Hout * a.Wout + (double)a.Cin * a.Hin * a.Win));
+        char label[48];      // the instantiation, as the conv_dma labels name theirs: <KS, STRIDE, R> / <KS, STRIDE>
+        if (tiled) snprintf(label, sizeof(label), "wgrad_tiled_kernel<%d, %d, %d>", ks, stride, two_rows ? 2 : 1);
+        else snprintf(label, sizeof(label), "wgrad_partial_kernel<%d, %d>", ks, stride);
+        ProfScope ps(s, label, flops, 4.0 * B * ((double)a.Cout * a.Hout * a.Wout + (double)a.Cin * a.Hin * a.Win));
         if (tiled) {
             if (ks == 3 && stride == 1) hipLaunchKernelGGL((wgrad_tiled_kernel<3, 1, 2>), grid, dim3(256), 0, s, a, dy, B, slabs, partial);
             else if (ks == 3 && stride == 2) hipLaunchKernelGGL((wgrad_tiled_kernel<3, 2, 1>), grid, dim3(256), 0, s, a, dy, B, slabs, partial);
@@ -983,6 +980,7 @@ __global__ __launch_bounds__(256) void zero_stuff_kernel(const float *dy, int Ho
     up[(long long)bc * Hin * Win + i] = v;
 }
 int launch_zero_stuff(const float *dy, int planes, int Hout, int Wout, int Hin, int Win, float *up, hipStream_t s) {
+    ProfScope ps(s, "zero_stuff_kernel", 0.0, 4.0 * planes * ((double)Hout * Wout + (double)Hin * Win));
     hipLaunchKernelGGL(zero_stuff_kernel, dim3((unsigned)(((long long)Hin * Win + 255) / 256), planes), dim3(256), 0, s, dy, Hout, Wout, Hin, Win, up);
     PF_LAUNCH_CHECK("zero_stuff_kernel");
     return PF_OK;
@@ -1183,6 +1181,9 @@ int launch_ce_fwd_bwd(const float *logits, int B, int C, int Hi, int Wi, const v
                       float *dfull, double *partial, double *out3, hipStream_t s) {
     const float sh = Ho > 1 ? (float)(Hi - 1) / (float)(Ho - 1) : 0.f, sw = Wo > 1 ? (float)(Wi - 1) / (float)(Wo - 1) : 0.f;
     const dim3 grid((unsigned)(((long long)Ho * Wo + 255) / 256), B);
+    char label[32];
+    snprintf(label, sizeof(label), "ce_fwd_bwd_kernel<%d>", C);
+    ProfScope ps(s, label, 0.0, 4.0 * B * C * ((double)Hi * Wi + (double)Ho * Wo));
     if (C == 11) hipLaunchKernelGGL((ce_fwd_bwd_kernel<11>), grid, dim3(256), 0, s, logits, Hi, Wi, labels, lab_i64, Ho, Wo, ignore, sh, sw, dfull, partial);
     else if (C == 19) hipLaunchKernelGGL((ce_fwd_bwd_kernel<19>), grid, dim3(256), 0, s, logits, Hi, Wi, labels, lab_i64, Ho, Wo, ignore, sh, sw, dfull, partial);
     else return fail(PF_EUNSUPPORTED, "cross entropy kernels are built for 11 or 19 classes, got %d", C);

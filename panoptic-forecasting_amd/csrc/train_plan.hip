@@ -643,7 +643,11 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<Di
         const std::array<int, 8> key = tune_key(c, ks, stride, B);
         int wm = 0, nt = 0, src = 1;
         const auto it = p->autotune ? p->tuned.find(key) : p->tuned.end();
-        if (it != p->tuned.end()) {
+        if (g_conv_force.kind == 1 && g_conv_force.p0 > 0) {
+            // pf_debug_force_conv(1, wm, nt, 0): every conv_dma step of the schedule with that shape (conv_dma_supported clamps nt to
+            // the layer's cout tiles); counted in none of the path statistics' table / cost-model / measured slots
+            wm = g_conv_force.p0, nt = g_conv_force.p1, src = 3;
+        } else if (it != p->tuned.end()) {
             wm = it->second.first, nt = it->second.second, src = 2;
         } else if (measuring) {
             src = 2;
@@ -658,7 +662,7 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<Di
                     break;
                 }
         }
-        TStep &st = add(src == 2 && it == p->tuned.end() ? T_CONV_DMA_MEASURE : T_CONV_DMA, stats | (uint8_t)(1u << src));
+        TStep &st = add(src == 2 && it == p->tuned.end() ? T_CONV_DMA_MEASURE : T_CONV_DMA, stats | (uint8_t)(src < 3 ? 1u << src : 0u));
         st.a = c; st.ks = ks; st.stride = stride;
         if (st.kind == T_CONV_DMA && !conv_dma_supported(c, ks, stride, B, wm, nt, 0, &st.wm, &st.nt))
             return fail(PF_EUNSUPPORTED, "training: conv_dma has no kernel for ks=%d stride=%d wm=%d nt=%d", ks, stride, st.wm, st.nt);
@@ -842,14 +846,23 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<Di
             if (odd) {
                 const ConvArgs b = bwd_data_args(dy, (int)o.cout, (int)o.cin, in.h, Wp, pad_out, (int)o.cin, 0, 0);
                 if ((rc = dma(b, (int)o.k, 1, L.bwd_all_job[ii], 0x20))) return rc;
-                TUnpadMultiArgs &m = add(T_UNPAD_MULTI).u.unpadm;
-                m = {pad_out, (int)o.cin, in.h, in.w, Wp, (int)o.n_src, {}, {}, {}, {}, {}};
-                for (uint32_t j = 0; j < o.n_src; ++j) {
-                    m.dst[j] = o.src[j].tensor != input ? gradt(o.src[j].tensor) : nullptr;
-                    m.ctotal[j] = (int)p->net.tensors[o.src[j].tensor].channels;
-                    m.choff[j] = (int)o.src[j].choff;
-                    m.ch[j] = (int)o.src[j].ch;
-                    m.overwrite[j] = gfirst.store[ii][j];
+                // one scatter launch for all ranges - unless two of them overlap in one tensor (an earlier range stores what a
+                // later one adds to: they must not share a launch): then one launch per range, in range order
+                bool overlap = false;
+                for (uint32_t j = 0; j < o.n_src; ++j)
+                    for (uint32_t j2 = 0; j2 < j; ++j2)
+                        overlap = overlap || (o.src[j].tensor == o.src[j2].tensor && o.src[j].choff < o.src[j2].choff + o.src[j2].ch &&
+                                              o.src[j2].choff < o.src[j].choff + o.src[j].ch);
+                for (uint32_t only = 0; only < (overlap ? o.n_src : 1u); ++only) {
+                    TUnpadMultiArgs &m = add(T_UNPAD_MULTI).u.unpadm;
+                    m = {pad_out, (int)o.cin, in.h, in.w, Wp, (int)o.n_src, {}, {}, {}, {}, {}};
+                    for (uint32_t j = 0; j < o.n_src; ++j) {
+                        m.dst[j] = o.src[j].tensor != input && (!overlap || j == only) ? gradt(o.src[j].tensor) : nullptr;
+                        m.ctotal[j] = (int)p->net.tensors[o.src[j].tensor].channels;
+                        m.choff[j] = (int)o.src[j].choff;
+                        m.ch[j] = (int)o.src[j].ch;
+                        m.overwrite[j] = gfirst.store[ii][j];
+                    }
                 }
                 continue;
             }

@@ -196,6 +196,9 @@ int launch_taps_cfg(const ConvArgs &a, const float *dy, int B, int slabs, int ch
         attr_set = true;
     }
     const dim3 grid(chunks, (a.Cin + 16 * NC - 1) / (16 * NC), slabs);
+    char label[48];
+    snprintf(label, sizeof(label), "wgrad_taps_kernel<%d, %d, %d, %d>", T, NC, TW, R);
+    ProfScope ps(s, label, 2.0 * B * a.Hout * a.Wout * (double)a.Cout * a.Cin * 9, 4.0 * B * ((double)a.Cout * a.Hout * a.Wout + (double)a.Cin * a.Hin * a.Win));
     hipLaunchKernelGGL((wgrad_taps_kernel<T, NC, TW, R>), grid, dim3(C::NTHR), bytes, s, a, dy, B, slabs, cob, co_pad, ci_pad, partial);
     return PF_OK;
 }

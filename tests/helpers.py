@@ -1,5 +1,8 @@
 """Test-only helpers: tiny custom op tables run through the C ABI (pf_hardnet_forward_dense)."""
 import ctypes
+import functools
+import json
+import os
 
 import torch
 
@@ -173,5 +176,216 @@ class MiniTrain:
         n = b * c.value * th.value * tw.value
         return self.ws[off.value:off.value + 4 * n].view(torch.float32).view(b, c.value, th.value, tw.value)
 
+    def path_stats(self):
+        """pf_train_path_stats of the last step (include/pfhip.h: [0] table, [1] cost model, [2] measured, ..., [7] packed pairs)"""
+        buf, n = (ctypes.c_int * 8)(), ctypes.c_int()
+        _lib.check(_lib.load().pf_train_path_stats(self.t, buf, 8, ctypes.byref(n)), 'pf_train_path_stats')
+        return list(buf)
+
     def close(self):
         _lib.load().pf_train_destroy(self.t)
+
+
+def mini_torch(sp, params, x, labels, dtype=torch.float64, pre=None):
+    """The same op table through torch autograd on the CPU, with gradients of every tensor retained: in float64 the checker, in
+    float32 (ATen) the yardstick of what fp32 rounding alone does.  ``pre``: a dict that receives every conv's output before
+    BatchNorm / ReLU (retained: ``.grad`` is the gradient the weight gradient is formed from)."""
+    import torch.nn.functional as F
+    leaves = {n: {k: v.to(dtype).clone().requires_grad_(k in ('w', 'gamma', 'beta', 'b')) for k, v in pr.items()} for n, pr in params.items()}
+    parts = {}           # tensor index -> {choff: produced slice}
+    whole = {0: x.to(dtype)}
+    kept = {}
+
+    def get(src):
+        if src.tensor in whole:
+            return whole[src.tensor][:, src.choff:src.choff + src.ch]
+        pr = parts[src.tensor]
+        if src.choff in pr and pr[src.choff].shape[1] == src.ch and sum(p.shape[1] for p in pr.values()) < sp.tensors[src.tensor].channels:
+            return pr[src.choff]                       # a slice read while the tensor is still being filled
+        t = torch.cat([pr[k] for k in sorted(pr)], 1)
+        assert t.shape[1] == sp.tensors[src.tensor].channels
+        whole[src.tensor] = t
+        return t[:, src.choff:src.choff + src.ch]
+
+    logits = None
+    for op in sp.ops:
+        if op.kind in (arch.OP_STEM, arch.OP_CONV):
+            xin = torch.cat([get(s) for s in op.srcs], 1)
+            pr = leaves[op.name]
+            y = F.conv2d(xin, pr['w'], None if op.bn else pr['b'], stride=op.stride, padding=op.k // 2)
+            if pre is not None:
+                y.retain_grad()
+                pre[op.name] = y
+            if op.bn:
+                y = F.batch_norm(y, pr['mean'], pr['var'], pr['gamma'], pr['beta'], training=True, momentum=0.1, eps=1e-5)
+            if op.relu:
+                y = F.relu(y)
+            if op.cout == sp.tensors[op.dst].channels:
+                y.retain_grad()
+                whole[op.dst] = y
+                kept[sp.tensors[op.dst].name] = y
+            else:
+                y.retain_grad()
+                parts.setdefault(op.dst, {})[op.dst_choff] = y
+                kept['%s@%d' % (sp.tensors[op.dst].name, op.dst_choff)] = y
+        elif op.kind == arch.OP_POOL:
+            whole[op.dst] = F.avg_pool2d(get(op.srcs[0]), 2, 2)
+            whole[op.dst].retain_grad()
+            kept[sp.tensors[op.dst].name] = whole[op.dst]
+        elif op.kind == arch.OP_UPSAMPLE:
+            like = get(op.srcs[1])
+            whole[op.dst] = F.interpolate(get(op.srcs[0]), size=like.shape[-2:], mode='bilinear', align_corners=True)
+            whole[op.dst].retain_grad()
+            kept[sp.tensors[op.dst].name] = whole[op.dst]
+        else:
+            logits = get(op.srcs[0])
+    full = F.interpolate(logits, size=labels.shape[-2:], mode='bilinear', align_corners=True)
+    loss = F.cross_entropy(full, labels.long(), ignore_index=255)
+    loss.backward()
+    return float(loss.detach()), leaves, kept
+
+
+# ---- the single-layer probe: dense input (6 channels) -> a (-> a2) -> L -> fin -> head, one layer L under test at a time.
+#      a / a2: 3x3 stride 1, BatchNorm + ReLU, so that L reads tensors some op produced and their gradients are computed.  L has NO
+#      ReLU: neither dW_L, dgamma_L / dbeta_L nor the gradient arriving at a's output then depends on a ReLU mask that could flip
+#      between fp32 and float64, so every compared quantity is well conditioned (unlike a deeper net's).  fin: 1x1 to n_cls with bias.
+class Probe:
+    """One probe case.  ``srcs``: L's input ranges, [('a' | 'a2', first channel, channels), ...]; ``ca`` / ``ca2``: channels of a / a2
+    (ca2 = 0: no a2); ``slot``: L writes channels [10, 10 + cout) of a wider tensor whose first 10 channels a 1x1 conv + BatchNorm
+    ``side`` over a produces (a's gradient then has a storing and an accumulating writer); ``fin_a`` = (first channel, channels): fin reads that slice of a beside L's
+    output (stride 1), so those channels of a's gradient are written before L's backward pass gets to them; ``size``: L's input size;
+    ``dead``: the labels of image 0 are all ignored."""
+
+    def __init__(self, name, k, stride, srcs, cout, size, ca, ca2=0, bn=True, slot=False, b=2, n_cls=11, u8=False, dead=False, fin_a=None):
+        self.name, self.k, self.stride, self.cout, self.size, self.ca, self.ca2 = name, k, stride, cout, tuple(size), ca, ca2
+        self.srcs = [(t, c0, n) for t, c0, n in srcs]
+        self.bn, self.slot, self.b, self.n_cls, self.u8, self.dead, self.fin_a = bn, slot, b, n_cls, u8, dead, fin_a
+        assert (not slot and not fin_a) or stride == 1
+        for t, c0, n in self.srcs:
+            assert c0 + n <= (ca if t == 'a' else ca2), (name, t, c0, n)
+
+    @property
+    def cin(self):
+        return sum(n for _, _, n in self.srcs)
+
+    def spec(self):
+        sp = MiniSpec(6)
+        S = arch.Src
+        t = {'a': sp.conv('a', [S(0, 0, 6)], self.ca, 3, bn=True)}
+        if self.ca2:
+            t['a2'] = sp.conv('a2', [S(0, 0, 6)], self.ca2, 3, bn=True)
+        srcs = [S(t[n], c0, ch) for n, c0, ch in self.srcs]
+        more = [S(t['a'], *self.fin_a)] if self.fin_a else []
+        if self.slot:
+            wide = sp.tensor('wide', 10 + self.cout)
+            sp.conv('side', [S(t['a'], 0, self.ca)], 10, 1, dst=wide, dst_choff=0, relu=False, bn=True)
+            sp.conv('L', srcs, self.cout, self.k, stride=self.stride, dst=wide, dst_choff=10, relu=False, bn=self.bn)
+            fin = sp.conv('fin', [S(wide, 0, 10 + self.cout)] + more, self.n_cls, 1, relu=False, bn=False)
+        else:
+            lt = sp.conv('L', srcs, self.cout, self.k, stride=self.stride, relu=False, bn=self.bn)
+            fin = sp.conv('fin', [S(lt, 0, self.cout)] + more, self.n_cls, 1, relu=False, bn=False)
+        sp.head(fin)
+        return sp
+
+    def data(self):
+        """(params, x, labels): CPU tensors, a function of the case alone"""
+        sp = self.spec()
+        g = torch.Generator().manual_seed(1000 + sum(ord(c) * (i + 1) for i, c in enumerate(self.name)) % 9973)
+        params = {}
+        for op in sp.conv_ops():
+            pr = {'w': torch.randn(op.cout, op.cin, op.k, op.k, generator=g) * (2.0 / (op.cin * op.k * op.k)) ** 0.5}
+            if op.bn:
+                pr.update(gamma=torch.rand(op.cout, generator=g) + 0.5, beta=torch.randn(op.cout, generator=g) * 0.2,
+                          mean=torch.zeros(op.cout), var=torch.ones(op.cout))
+            else:
+                pr['b'] = torch.randn(op.cout, generator=g) * 0.1
+            params[op.name] = pr
+        h, w = self.size
+        x = torch.randn(self.b, 6, h, w, generator=g)
+        oh, ow = (h + self.stride - 1) // self.stride, (w + self.stride - 1) // self.stride
+        lab = torch.randint(0, self.n_cls + 1, (self.b, 2 * oh - 3, 2 * ow + 1), generator=g)
+        lab[lab == self.n_cls] = 255
+        if self.dead:
+            lab[0] = 255
+        return params, x, (lab.to(torch.uint8) if self.u8 else lab)
+
+    def quantities(self, loss, leaves, kept):
+        """what a case compares, out of mini_torch's result: {name: float64 CPU tensor}"""
+        q = {'loss': torch.tensor([loss], dtype=torch.float64), 'act a': kept['a'].detach(), 'grad a': kept['a'].grad}
+        if self.ca2:
+            q['act a2'], q['grad a2'] = kept['a2'].detach(), kept['a2'].grad
+        q['act L'] = kept['wide@10' if self.slot else 'L'].detach()
+        for nm in ('w', 'gamma', 'beta') if self.bn else ('w', 'b'):
+            q['d%s L' % nm] = leaves['L'][nm].grad
+        return {k: v.double() for k, v in q.items()}
+
+    def quantities_hip(self, net, loss):
+        q = {'loss': torch.tensor([loss], dtype=torch.float64), 'act a': net.tensor('a'), 'grad a': net.tensor('a', grad=True)}
+        if self.ca2:
+            q['act a2'], q['grad a2'] = net.tensor('a2'), net.tensor('a2', grad=True)
+        q['act L'] = net.tensor('wide')[:, 10:10 + self.cout] if self.slot else net.tensor('L')
+        for nm in ('w', 'gamma', 'beta') if self.bn else ('w', 'b'):
+            q['d%s L' % nm] = net.param('L.' + nm, grad=True)
+        return {k: v.detach().cpu().double() for k, v in q.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def _probe_reference(case):
+    params, x, lab = case.data()
+    sp = case.spec()
+    return tuple(case.quantities(*mini_torch(sp, params, x, lab, dtype=dt)) for dt in (torch.float64, torch.float32))
+
+
+def probe_reference(case):
+    """(float64 autograd, fp32 ATen autograd) quantities of a case - computed once per case and process, never modified"""
+    return _probe_reference(case)
+
+
+# the two criteria of the probe.  PROBE_REL: the project's kernel-level bar (relative L2; activations and the loss 1e-5).  The
+# elementwise one: e(X) = max|X - X64| / max|X64| of the subject at most max(M * e of fp32 ATen, floor).  PROBE_M_CAP /
+# PROBE_FLOOR_CAP are the largest values a test may use: with them the bar on dW stays <= 4.5e-5, a fifth of the smallest error one
+# lost pixel of a weight gradient makes (tests/test_train_host.py: the bar bites)
+PROBE_M_CAP, PROBE_FLOOR_CAP = 32.0, 2e-5
+
+
+def probe_rel_bar(name):
+    return 1e-5 if name.startswith('act') or name == 'loss' else 1e-4
+
+
+def probe_distances(got, ref64, ref32):
+    """per quantity: e of the subject, e of fp32 ATen, relative L2 of the subject"""
+    out = {}
+    for k, r in ref64.items():
+        mx = float(r.abs().max()) + 1e-300
+        out[k] = {'e_hip': float((got[k] - r).abs().max()) / mx, 'e_aten': float((ref32[k] - r).abs().max()) / mx,
+                  'rel_hip': float((got[k] - r).norm() / (r.norm() + 1e-300))}
+    return out
+
+
+def probe_failures(dist, m, floor):
+    """[(quantity, which criterion, value, bar)] of a case's distances"""
+    assert 1.0 <= m <= PROBE_M_CAP and 0.0 <= floor <= PROBE_FLOOR_CAP
+    bad = []
+    for k, d in dist.items():
+        if not d['rel_hip'] <= probe_rel_bar(k):
+            bad.append((k, 'rel. L2', d['rel_hip'], probe_rel_bar(k)))
+        bar = max(m * d['e_aten'], floor)
+        if not d['e_hip'] <= bar:
+            bad.append((k, 'elementwise', d['e_hip'], bar))
+    return bad
+
+
+def probe_record(case_id, dist, kernels):
+    """train_layer_probe_dist.json in the scratch directory the suite's other measured reports go to (tests/test_gpu_precision.py:
+    REPORT): e_hip / e_aten (and the relative L2) per case and quantity, and the kernels the case ran.  The run on MI355X is kept
+    as profiles/train_layer_probe_dist.json: M and floor of tests/test_gpu_train_layers.py come from it"""
+    from test_gpu_precision import REPORT
+    path = os.path.join(os.path.dirname(REPORT), 'train_layer_probe_dist.json')
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    data = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            data = json.load(f)
+    data[case_id] = {'e': {k: {n: float('%.4g' % v) for n, v in d.items()} for k, d in dist.items()}, 'kernels': list(kernels)}
+    with open(path, 'w') as f:
+        json.dump(data, f, indent=0, sort_keys=True)

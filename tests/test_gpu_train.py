@@ -439,61 +439,6 @@ def _mini_net():
     return sp
 
 
-def _mini_torch(sp, params, x, labels):
-    """The same op table through torch autograd (float64 checker), with gradients of every tensor retained."""
-    from panoptic_forecasting_amd import hardnet_arch as arch
-    import torch.nn.functional as F
-    leaves = {n: {k: v.double().clone().requires_grad_(k in ('w', 'gamma', 'beta', 'b')) for k, v in pr.items()} for n, pr in params.items()}
-    parts = {}           # tensor index -> {choff: produced slice}
-    whole = {0: x.double()}
-    kept = {}
-
-    def get(src):
-        if src.tensor in whole:
-            return whole[src.tensor][:, src.choff:src.choff + src.ch]
-        pr = parts[src.tensor]
-        if src.choff in pr and pr[src.choff].shape[1] == src.ch and sum(p.shape[1] for p in pr.values()) < sp.tensors[src.tensor].channels:
-            return pr[src.choff]                       # a slice read while the tensor is still being filled
-        t = torch.cat([pr[k] for k in sorted(pr)], 1)
-        assert t.shape[1] == sp.tensors[src.tensor].channels
-        whole[src.tensor] = t
-        return t[:, src.choff:src.choff + src.ch]
-
-    logits = None
-    for op in sp.ops:
-        if op.kind in (arch.OP_STEM, arch.OP_CONV):
-            xin = torch.cat([get(s) for s in op.srcs], 1)
-            pr = leaves[op.name]
-            y = F.conv2d(xin, pr['w'], None if op.bn else pr['b'], stride=op.stride, padding=op.k // 2)
-            if op.bn:
-                y = F.batch_norm(y, pr['mean'], pr['var'], pr['gamma'], pr['beta'], training=True, momentum=0.1, eps=1e-5)
-            if op.relu:
-                y = F.relu(y)
-            if op.cout == sp.tensors[op.dst].channels:
-                y.retain_grad()
-                whole[op.dst] = y
-                kept[sp.tensors[op.dst].name] = y
-            else:
-                y.retain_grad()
-                parts.setdefault(op.dst, {})[op.dst_choff] = y
-                kept['%s@%d' % (sp.tensors[op.dst].name, op.dst_choff)] = y
-        elif op.kind == arch.OP_POOL:
-            whole[op.dst] = F.avg_pool2d(get(op.srcs[0]), 2, 2)
-            whole[op.dst].retain_grad()
-            kept[sp.tensors[op.dst].name] = whole[op.dst]
-        elif op.kind == arch.OP_UPSAMPLE:
-            like = get(op.srcs[1])
-            whole[op.dst] = F.interpolate(get(op.srcs[0]), size=like.shape[-2:], mode='bilinear', align_corners=True)
-            whole[op.dst].retain_grad()
-            kept[sp.tensors[op.dst].name] = whole[op.dst]
-        else:
-            logits = get(op.srcs[0])
-    full = F.interpolate(logits, size=labels.shape[-2:], mode='bilinear', align_corners=True)
-    loss = F.cross_entropy(full, labels.long(), ignore_index=255)
-    loss.backward()
-    return float(loss), leaves, kept
-
-
 @pytest.mark.parametrize('taps', [1, 0, 2])
 @pytest.mark.parametrize('size', [(24, 40), (34, 70)])
 def test_mini_network_training_step_vs_autograd(size, taps):
@@ -551,7 +496,7 @@ def test_forward_on_packed_pairs_is_the_same_step_to_rounding():
 
 
 def _mini_network_step(size):
-    from tests.helpers import MiniTrain
+    from tests.helpers import MiniTrain, mini_torch as _mini_torch
     from panoptic_forecasting_amd import lib as pflib
     h, w = size
     sp = _mini_net()

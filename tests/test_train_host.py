@@ -1,6 +1,7 @@
 """Host side of the training driver (scope row f4): the learning-rate schedule against torch's schedulers as the reference
 builds them (training/train_utils.py:13-24, stepped once per epoch + once before the first, train.py:162-164,228-229), and
-the flat-gradient exchange on two gloo ranks."""
+the flat-gradient exchange on two gloo ranks; and the checker of the per-layer training probe (tests/test_gpu_train_layers.py):
+its elementwise bar catches what the relative-L2 bar lets through."""
 import os
 import subprocess
 import sys
@@ -72,3 +73,53 @@ def test_reference_parameter_order_matches_fixture():
     assert sorted(mine) == sorted(want)
     assert mine != want                      # the op-table order differs (conv1x1_up.i before denseBlocksUp.i) ...
     assert bg_train.reference_parameter_order(mine) == want   # ... the checkpoint order is the reference's
+
+
+def _probe_cases():
+    from tests.helpers import Probe
+    return [Probe('bites 40->28 9x72', 3, 1, [('a', 0, 40)], 28, (9, 72), 40),
+            Probe('bites 50->70 17x136', 3, 1, [('a', 0, 50)], 70, (17, 136), 50),
+            Probe('bites 1x1 90->70 9x72', 1, 1, [('a', 0, 90)], 70, (9, 72), 90),
+            Probe('bites 270->70 17x72', 3, 1, [('a', 0, 270)], 70, (17, 72), 270),
+            Probe('bites 3 ranges 9x70', 3, 1, [('a', 0, 16), ('a2', 2, 10), ('a', 8, 14)], 18, (9, 70), 24, 12),
+            Probe('bites s2 40->24 35x70', 3, 2, [('a', 0, 28), ('a', 12, 12)], 24, (35, 70), 40, bn=False)]
+
+
+@pytest.mark.parametrize('case', _probe_cases(), ids=lambda c: c.name)
+def test_probe_elementwise_bar_bites_where_relative_l2_does_not(case):
+    """Why the per-layer probe has an elementwise criterion, pinned on the CPU.  (1) A second fp32 implementation - ATen's own
+    convolutions with oneDNN switched off - passes both criteria at the caps (M = 32, floor = 2e-5) with fp32 ATen as the
+    yardstick: the caps leave room for what fp32 rounding does.  (2) The float64 weight gradient of L with ONE pixel's
+    contribution removed from ONE element (an edge tile clipped one pixel short; the pixel with the median |contribution| to that
+    element) fails the elementwise criterion at the caps in every case, by 5x or more - while the 1e-4 relative-L2 bar passes it in
+    the three cases with the larger weight tensors (1.4e-5 .. 1.6e-5) and sits within 2x of it, on either side depending on the
+    element, in the other three."""
+    from tests.helpers import (PROBE_FLOOR_CAP, PROBE_M_CAP, mini_torch, probe_distances, probe_failures, probe_reference)
+    r64, r32 = probe_reference(case)
+    params, x, lab = case.data()
+    sp = case.spec()
+    with torch.backends.mkldnn.flags(enabled=False):
+        other = case.quantities(*mini_torch(sp, params, x, lab, dtype=torch.float32))
+    assert probe_failures(probe_distances(other, r64, r32), PROBE_M_CAP, PROBE_FLOOR_CAP) == []
+    # the yardstick itself is where the issue measured it (dW 1.4e-6, input gradients 8.4e-6, the rest below 1e-6): x2
+    d32 = probe_distances(r32, r64, r32)
+    for k, d in d32.items():
+        assert d['e_aten'] <= (2e-5 if k.startswith('grad') else 4e-6), (k, d)
+    pre = {}
+    _, leaves, kept = mini_torch(sp, params, x, lab, pre=pre)
+    dy = pre['L'].grad
+    xin = torch.cat([kept[t][:, c0:c0 + n] for t, c0, n in case.srcs], 1).detach()
+    s, c = case.stride, case.k // 2
+    co, ci = 1, 2
+    contrib = dy[:, co] * xin[:, ci, ::s, ::s][:, :dy.shape[2], :dy.shape[3]]       # the centre tap's terms, pixel by pixel
+    assert abs(float(contrib.sum()) - float(leaves['L']['w'].grad[co, ci, c, c])) <= 1e-12 * float(contrib.abs().sum())
+    nz = contrib[contrib != 0]
+    term = nz[(nz.abs() - nz.abs().median()).abs().argmin()]
+    hurt = {k: v.clone() for k, v in r64.items()}
+    hurt['dw L'][co, ci, c, c] -= term
+    d = probe_distances(hurt, r64, r32)
+    bad = probe_failures(d, PROBE_M_CAP, PROBE_FLOOR_CAP)
+    assert [b[:2] for b in bad if b[1] == 'elementwise'] == [('dw L', 'elementwise')], bad
+    assert d['dw L']['e_hip'] >= 5.0 * max(PROBE_M_CAP * d['dw L']['e_aten'], PROBE_FLOOR_CAP), d['dw L']
+    if case.name in ('bites 50->70 17x136', 'bites 270->70 17x72', 'bites s2 40->24 35x70'):
+        assert d['dw L']['rel_hip'] <= 1e-4, d['dw L']          # ... and the norm-wise bar does not see it

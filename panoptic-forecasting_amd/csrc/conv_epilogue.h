@@ -16,8 +16,11 @@ typedef float epi_f32x4 __attribute__((ext_vector_type(4)));
 typedef float epi_f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) float lds_float;   // explicit LDS pointers: ds_read, not flat loads
 
-// align_corners=True source index (ATen area_pixel_compute_scale / compute_source_index)
+// align_corners=True source index (ATen area_pixel_compute_scale / compute_source_index).  r is the fp32-ROUNDED product, as in
+// ATen: with contraction allowed the compiler forms l1 = fma(scale, o, -i0) from the unrounded product, a weight up to
+// 2^-24 * r away from the contract's (8e-7 * max|tap| at 16 source rows: tests/head_ref64.py measures against the rounded form)
 __device__ __forceinline__ void lin_coord(int o, float scale, int in_size, int &i0, int &i1, float &l0, float &l1) {
+#pragma clang fp contract(off)
     const float r = scale * (float)o;
     i0 = min((int)r, in_size - 1);
     i1 = i0 + (i0 < in_size - 1 ? 1 : 0);

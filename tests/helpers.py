@@ -64,19 +64,39 @@ class MiniNet:
                    'pf_hardnet_plan_create')
         self.spec = spec
 
-    def run(self, x):
+    def _workspace(self, x):
+        """a zeroed workspace for an input of x's shape (kept as self.ws) -> (the library, contiguous x, b, h, w)"""
         L = _lib.load()
         b, _, h, w = x.shape
         need = ctypes.c_size_t()
         _lib.check(L.pf_hardnet_workspace(self.plan, b, h, w, ctypes.byref(need)), 'pf_hardnet_workspace')
         self.ws = torch.zeros(need.value, dtype=torch.uint8, device=x.device)
-        x = x.contiguous()
+        self.bhw = (b, h, w)
+        return L, x.contiguous(), b, h, w
+
+    def run(self, x):
+        L, x, b, h, w = self._workspace(x)
         rc = L.pf_hardnet_forward_dense(self.plan, x.data_ptr(), b, h, w, 0, 0, None, 0, None, None,
                                         self.ws.data_ptr(), self.ws.numel(), _lib.stream_ptr())
         _lib.check(rc, 'pf_hardnet_forward_dense')
         torch.cuda.synchronize()
-        self.bhw = (b, h, w)
         return self
+
+    def run_head(self, x, out_h, out_w, seg_dtype=torch.uint8, want_logits=True):
+        """the forward with the head's outputs requested: (rc, seg [B, out_h, out_w] of ``seg_dtype`` (uint8 / int64), out_logits
+        [B, C, out_h, out_w] or None, out_orig_logits = the head's input as the library copies it out).  The outputs are
+        pre-filled with values no kernel writes (label 250, NaN), so a pixel left out shows"""
+        L, x, b, h, w = self._workspace(x)
+        c = self.spec.n_cls
+        assert seg_dtype in (torch.uint8, torch.int64)
+        seg = torch.full((b, out_h, out_w), 250, dtype=seg_dtype, device=x.device)
+        logits = torch.full((b, c, out_h, out_w), float('nan'), device=x.device) if want_logits else None
+        orig = torch.full((b, c, h, w), float('nan'), device=x.device)
+        rc = L.pf_hardnet_forward_dense(self.plan, x.data_ptr(), b, h, w, out_h, out_w, seg.data_ptr(), int(seg_dtype == torch.int64),
+                                        logits.data_ptr() if want_logits else None, orig.data_ptr(), self.ws.data_ptr(),
+                                        self.ws.numel(), _lib.stream_ptr())
+        torch.cuda.synchronize()
+        return rc, seg, logits, orig
 
     def tensor(self, name):
         return view_tensor(self.plan, self.ws, name, *self.bhw)
@@ -379,13 +399,25 @@ def probe_record(case_id, dist, kernels):
     """train_layer_probe_dist.json in the scratch directory the suite's other measured reports go to (tests/test_gpu_precision.py:
     REPORT): e_hip / e_aten (and the relative L2) per case and quantity, and the kernels the case ran.  The run on MI355X is kept
     as profiles/train_layer_probe_dist.json: M and floor of tests/test_gpu_train_layers.py come from it"""
+    _merge_report('train_layer_probe_dist.json', case_id,
+                  {'e': {k: {n: float('%.4g' % v) for n, v in d.items()} for k, d in dist.items()}, 'kernels': list(kernels)})
+
+
+def _merge_report(name, key, entry):
+    """set ``key`` of the JSON object in file ``name`` of the suite's scratch report directory (tests/test_gpu_precision.py: REPORT)"""
     from test_gpu_precision import REPORT
-    path = os.path.join(os.path.dirname(REPORT), 'train_layer_probe_dist.json')
+    path = os.path.join(os.path.dirname(REPORT), name)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     data = {}
     if os.path.exists(path):
         with open(path) as f:
             data = json.load(f)
-    data[case_id] = {'e': {k: {n: float('%.4g' % v) for n, v in d.items()} for k, d in dist.items()}, 'kernels': list(kernels)}
+    data[key] = entry
     with open(path, 'w') as f:
         json.dump(data, f, indent=0, sort_keys=True)
+
+
+def head_probe_record(case_id, entry):
+    """head_probe_dist.json next to the other measured reports (probe_record above): per case of tests/test_gpu_head.py the worst
+    err / (u*M), the near-tie count and the kernel that ran.  The run on MI355X is kept as profiles/head_probe_dist.json"""
+    _merge_report('head_probe_dist.json', case_id, entry)

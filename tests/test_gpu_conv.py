@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import head_ref64
+
 pytestmark = pytest.mark.gpu
 
 
@@ -90,6 +92,10 @@ def test_pool_and_upsample(h, w):
     up = F.interpolate(pooled, size=(h, w), mode='bilinear', align_corners=True)
     assert (net.tensor('pool').cpu() - pooled).abs().max() <= 1e-6
     assert (net.tensor('up').cpu() - up).abs().max() <= 1e-5
+    # upsample_kernel alone, at the bar its fp32 rounding allows (tests/head_ref64.py: the same lin_coord, 4.5 * 2^-24 * max|tap|):
+    # float64 interpolation, with the contract's fp32 coordinates, of the pooled tensor as the device holds it
+    dev_pooled = net.tensor('pool').cpu()
+    assert (net.tensor('up').cpu().double() - head_ref64.upsample64(dev_pooled, h, w)).abs().max() <= head_ref64.head_bar(dev_pooled)
     net.close()
 
 

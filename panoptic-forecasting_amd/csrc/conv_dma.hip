@@ -17,10 +17,6 @@
 #include "conv_epilogue.h"
 #include "pf_prof.h"
 
-#ifndef PF_ABLATE
-#define PF_ABLATE 0
-#endif
-
 #ifndef PF_PROBE
 #define PF_PROBE 0
 #endif

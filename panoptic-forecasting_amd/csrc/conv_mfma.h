@@ -224,13 +224,10 @@ inline int dma_kc(int ks, int stride) { return dma_kc_ct(ks, stride); }
 int dma_chunks(const int *src_ch, int n_src, int ks, int stride);
 // conv_dma's vector-ALU cout path: the last `rem` (1..16) output channels; accumulators rv in {2,4,8,12,16} >= rem
 inline int dma_rem_rv(int rem) { return rem <= 2 ? 2 : (rem + 3) / 4 * 4; }
-// how many trailing output channels of a 3x3/s1 conv go to the vector ALU (0 = none): the partial tile, or with
-// peel_full a whole 16-wide tile of a conv whose cout is a multiple of 16
-inline int dma_valu_split(int cout, bool peel_full) {
+// how many trailing output channels of a 3x3/s1 conv go to the vector ALU (0 = none): the partial tile
+inline int dma_valu_split(int cout) {
     if (cout < 16) return 0;
-    const int r = cout % 16;
-    if (r == 0) return (peel_full && cout >= 32) ? 16 : 0;
-    return r;
+    return cout % 16;
 }
 void pack_conv_weights_rem(const float *w_oihw, int cin, int cout, int rem, int ks, int kc, const int *src_ch, int n_src, float *out);
 void pack_conv_weights_tiled(const float *w_oihw, int cin, int cout, int ks, int kc, const int *src_ch, int n_src, float *out);

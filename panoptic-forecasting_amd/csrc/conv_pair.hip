@@ -28,10 +28,6 @@
 #include "conv_s4.h"
 #include "pf_prof.h"
 
-#ifndef PAIR_DBG
-#define PAIR_DBG 0
-#endif
-
 namespace pf {
 
 template <int NT, int NTP, int MERGED = 0>
@@ -281,7 +277,7 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(PairArgs pa) {
     for (int m = 0; m < C::MP; ++m) col_h[m] = col_m[m] = zero8;
 
     typedef const volatile __attribute__((address_space(3))) s4_h4 *lds_h4;
-    // a pixel fragment: the 4 channels of two entries x two terms, four plain 8-B reads (conv_s4.hip: S4_FRAG_B64)
+    // a pixel fragment: the 4 channels of two entries x two terms, four plain volatile 8-B reads (conv_s4_kernel.inc: frag)
     auto frag = [&](const unsigned char *p, int ent_stride8, int term_stride8, s4_h8 &h, s4_h8 &md) {
         const lds_h4 q = (lds_h4)(const __attribute__((address_space(3))) unsigned char *)p;
         h = s4_join(q[0], q[ent_stride8]);
@@ -424,16 +420,9 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(PairArgs pa) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-#if PAIR_DBG & 1
-        __syncthreads();
-#endif
     };
     int R = 0;
     for (; R < RS; ++R) round_body(R, std::integral_constant<int, 0>());
-#if PAIR_DBG & 2
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-#endif
     {
         // ---- P's epilogue: bias, ReLU, zero outside the image, split -> LDS planes (+ the tile's own pixels -> memory)
         const int px = lane & 15;
@@ -500,9 +489,7 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(PairArgs pa) {
                 if (inimg && g > 0 && 4 * pg < pa.p_cout + 2) pair_store_px(pd, 4 * pg, (size_t)oy * a.Wout + ox, v);
             }
         }
-#if !(PAIR_DBG & 4)
         range_commit(a.status, pa.p_range_slot, vmax);
-#endif
     }
     for (; R < RD; ++R) round_body(R, std::integral_constant<int, 1>());
     for (; R < nrounds; ++R) round_body(R, std::integral_constant<int, 2>());

@@ -43,31 +43,6 @@
 #define S4_PROBE(i) do { } while (0)
 #endif
 
-// A/B knobs of profiles/r05_experiments.md (defaults = the shipped kernels): cache-policy bits of the activation LDS-DMA (2 = nt),
-// non-temporal epilogue stores of the 3x3 kernel's common path, raised wave priority across the matrix phase of a round
-#ifndef S4_ACT_AUX
-#define S4_ACT_AUX 0
-#endif
-#ifndef S4_STORE_NT
-#define S4_STORE_NT 0
-#endif
-#ifndef S4_SETPRIO
-#define S4_SETPRIO 0
-#endif
-// Pixel fragments of the 3x3 kernel: a B operand is 8 fp16 = the 4 channels of TWO group entries of one pixel, which live in two
-// planes of a stage, 2880 B apart - out of reach of one ds_read2_b64 (255 x 8 B).  Left alone, hipcc pairs the reads of two
-// DIFFERENT M-tiles of one plane into a ds_read2_b64 and then moves the halves into place: 72 v_mov_b32 per round next to 54
-// matrix instructions (and a ds_read2_b64 occupies the LDS for 8 cycles where two ds_read_b64 take 4).  1 = volatile 8-B
-// reads: no pairing, no moves
-#ifndef S4_PREFETCH
-#define S4_PREFETCH 0
-#endif
-#ifndef S4_COL_EARLY
-#define S4_COL_EARLY 0
-#endif
-#ifndef S4_FRAG_B64
-#define S4_FRAG_B64 1
-#endif
 // the DMA parts of the next stage go out after MFMA groups 1, 3, .. of a round (every placement measured within 1 %)
 [[maybe_unused]] constexpr int kS4IssueFirst = 1, kS4IssueStep = 2;
 

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
     auto issue_part = [&](int r, int stage, int j) {
         if ((jb + j) * 64 + lane < C::PIECES)   // the plane holds exactly its pieces: lanes past the last one write nothing
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ars, (s4_lds_ptr_t)(abuf(stage) + w4 * C::PLANE + (jb + j) * 1024), 16,
-                                                     areal ? poff[j] : kS4Oob, asoff, 0, S4_ACT_AUX);
+                                                     areal ? poff[j] : kS4Oob, asoff, 0, 0);
         unsigned char *wdst = wbuf(stage);
         const bool flush = is_flush(r);
 #pragma unroll
@@ -148,31 +148,26 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
         if (more) prepare_round(round + 1);
         S4_PROBE(round * 4 + 2);
         const unsigned char *ab = abuf(round & 1), *wb = wbuf(round & 1);
-#if S4_SETPRIO
-        __builtin_amdgcn_s_setprio(S4_SETPRIO);
-#endif
+        // Pixel fragments: a B operand is 8 fp16 = the 4 channels of TWO group entries of one pixel, which live in two planes of a
+        // stage, 2880 B apart - out of reach of one ds_read2_b64 (255 x 8 B).  Left alone, hipcc pairs the reads of two DIFFERENT
+        // M-tiles of one plane into a ds_read2_b64 and then moves the halves into place: 72 v_mov_b32 per round next to 54 matrix
+        // instructions (and a ds_read2_b64 occupies the LDS for 8 cycles where two ds_read_b64 take 4).  Hence four plain
+        // volatile ds_read_b64, each straight into its half of an operand tuple: no pairing, no moves
         auto frag = [&](const unsigned char *p, s4_h8 &h, s4_h8 &md) {
-            if constexpr (S4_FRAG_B64 == 1 || (S4_FRAG_B64 == 2 && NT != 2)) {
-                // four plain ds_read_b64, each straight into its half of an operand tuple (see S4_FRAG_B64 above)
-                typedef const volatile __attribute__((address_space(3))) s4_h4 *lds_h4;
-                const lds_h4 q = (lds_h4)(const __attribute__((address_space(3))) unsigned char *)p;
-                constexpr int PL = C::PLANE / 8;
-                h = s4_join(q[0], q[PL]);
-                md = s4_join(q[2 * PL], q[3 * PL]);
-            } else {
-                h = s4_join(*reinterpret_cast<const s4_h4 *>(p), *reinterpret_cast<const s4_h4 *>(p + C::PLANE));
-                md = s4_join(*reinterpret_cast<const s4_h4 *>(p + 2 * C::PLANE), *reinterpret_cast<const s4_h4 *>(p + 3 * C::PLANE));
-            }
+            typedef const volatile __attribute__((address_space(3))) s4_h4 *lds_h4;
+            const lds_h4 q = (lds_h4)(const __attribute__((address_space(3))) unsigned char *)p;
+            constexpr int PL = C::PLANE / 8;
+            h = s4_join(q[0], q[PL]);
+            md = s4_join(q[2 * PL], q[3 * PL]);
         };
         auto mtile_off = [&](int mm) {
             return ((mm / C::MTR) * C::IW + (mm % C::MTR) * 16) * 8;
         };
         // the three products of one block of weights with FT M-tiles; `slot0` numbers the MFMA groups for the DMA parts.
-        // FT = 4 M-tiles per batch of fragment reads, or 2 for <2, 32> with the plain 8-B reads: its 126 registers have no
-        // room for 32 fragment registers that are all live at once (the reads are volatile: none may be sunk below a matrix
-        // instruction) - two tiles at a time need 16
-        constexpr bool kB64 = S4_FRAG_B64 == 1 || (S4_FRAG_B64 == 2 && NT != 2);
-        constexpr int FT = (kB64 && NT == 2 && C::MP == 4) ? 2 : 4;
+        // FT = 4 M-tiles per batch of fragment reads, or 2 for <2, 32>: its 126 registers have no room for 32 fragment registers
+        // that are all live at once (the reads are volatile: none may be sunk below a matrix instruction) - two tiles at a time
+        // need 16
+        constexpr int FT = (NT == 2 && C::MP == 4) ? 2 : 4;
         auto mfmas = [&](const s4_h8 (&wh)[NT], const s4_h8 (&wm)[NT], int m0, const auto &fh, const auto &fm, int slot0, bool dma) {
             constexpr int FTn = (int)(sizeof(fh) / sizeof(fh[0]));
 #pragma unroll
@@ -195,46 +190,6 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
             if (dma) issue_slot(round, more, slot0 + 2);
         };
         constexpr int NB = C::MP / FT;      // fragment batches per instruction of a round
-        // S4_COL_EARLY (<2, 32>): the collected-tap weights of a flush round are requested BEFORE the round's DMA parts: loads return in
-        // order, so waiting for them at the flush then does not wait for the next stage's DMA as well (16 registers across the round:
-        // <3, 32> has no room for its 24)
-        constexpr bool kColEarly = S4_COL_EARLY && C::COLREG && NT == 2;
-        s4_h8 cwh[NT], cwm[NT];
-        if (kColEarly && is_flush(round)) {
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                const bool real = tile0 + n < a.ntiles;   // uniform
-                const char *wp = reinterpret_cast<const char *>(a.wpk) +
-                                 ((size_t)(real ? tile0 + n : 0) * nblocks + s4_blocks_before(round) + 2) * C::WBLK + lane * 16;
-                cwh[n] = real ? *reinterpret_cast<const s4_h8 *>(wp) : zero8;
-                cwm[n] = real ? *reinterpret_cast<const s4_h8 *>(wp + 64 * 16) : zero8;
-            }
-        }
-        // S4_PREFETCH (experiment, off): the fragments of batch k + 1 are read while the matrix instructions of batch k run
-        constexpr bool kPrefetch = S4_PREFETCH && kB64 && NT <= 2 && KS_ == 1 && TH_ == 8 && TW_ == 32;
-        if constexpr (kPrefetch) {
-            s4_h8 fh[2][FT], fm[2][FT];
-            auto read_batch = [&](int k, s4_h8 (&h)[FT], s4_h8 (&md)[FT]) {
-#pragma unroll
-                for (int m = 0; m < FT; ++m) frag(ab + aoff[k / NB] + mtile_off((k % NB) * FT + m), h[m], md[m]);
-            };
-            read_batch(0, fh[0], fm[0]);
-            s4_h8 wh[NT], wm[NT];
-#pragma unroll
-            for (int k = 0; k < 2 * NB; ++k) {
-                const int sI = k / NB;
-                if (k % NB == 0) {
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) {
-                        wh[n] = *reinterpret_cast<const s4_h8 *>(wb + (((n * C::BPT + sI) * 2 + 0) * 64 + lane) * 16);
-                        wm[n] = *reinterpret_cast<const s4_h8 *>(wb + (((n * C::BPT + sI) * 2 + 1) * 64 + lane) * 16);
-                    }
-                }
-                if (k + 1 < 2 * NB) read_batch(k + 1, fh[(k + 1) & 1], fm[(k + 1) & 1]);
-                mfmas(wh, wm, (k % NB) * FT, fh[k & 1], fm[k & 1], 3 * k, true);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             s4_h8 wh[NT], wm[NT];
@@ -252,7 +207,6 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 __builtin_amdgcn_sched_barrier(0);   // keep the next unit's fragment reads behind these MFMAs (registers)
             }
         }
-        }
         // the ninth tap of this round's entries: K-slice (round & 3)
         if (g == (round & 3)) {
 #pragma unroll
@@ -261,9 +215,9 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
         if (is_flush(round)) {
             // the collected-tap block of this flush round (third block of the round in the packed stream).  COLREG: global ->
             // registers (L2-resident; the fragment registers of the two full instructions are dead here); else from LDS
+            s4_h8 cwh[NT], cwm[NT];
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
-                if (kColEarly) continue;
                 if (C::COLREG) {
                     const bool real = tile0 + n < a.ntiles;   // uniform
                     const char *wp = reinterpret_cast<const char *>(a.wpk) +
@@ -289,9 +243,6 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
 #pragma unroll
             for (int m = 0; m < C::MP; ++m) col_h[m] = col_m[m] = zero8;
         }
-#if S4_SETPRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
         if constexpr (KACC) {
 #pragma unroll
             for (int m = 0; m < C::MP; ++m)
@@ -357,13 +308,8 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
             char *p = reinterpret_cast<char *>(a.dst) + (size_t)b * 2 * term + pix * 8 + (size_t)(chb >> 2) * hw * 8;
             if (!mis) {
                 if (ok1) {
-#if S4_STORE_NT
-                    __builtin_nontemporal_store(hi, reinterpret_cast<s4_h4 *>(p));
-                    __builtin_nontemporal_store(mid, reinterpret_cast<s4_h4 *>(p + term));
-#else
                     *reinterpret_cast<s4_h4 *>(p) = hi;
                     *reinterpret_cast<s4_h4 *>(p + term) = mid;
-#endif
                 } else if (ok0) {
                     *reinterpret_cast<h2 *>(p) = h2{hi[0], hi[1]};
                     *reinterpret_cast<h2 *>(p + term) = h2{mid[0], mid[1]};

@@ -149,7 +149,6 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
             if (g_conv_force.kind == 1) ch = g_conv_force;
             if (g_conv_force.kind == 4 && cp.split_off && (!need || o.k == 1)) ch = g_conv_force;
             if (ch.kind == 4 && (!cp.split_off || (need && o.k != 1) || !p->opt.split_f16)) ch = ConvChoice{1, 0, 0, 0};
-            if (ch.kind == 3) ch = ConvChoice{1, 0, 0, 0};   // (kind 3 was conv_valu, removed in round 3: selected by no table row)
             // pf_debug_force_conv(5, ..): launches that cannot read S4 (fp32 sources) still have to be able to WRITE it
             if (g_conv_force.kind == 5) ch = ConvChoice{1, 0, 0, 0};
         }
@@ -214,8 +213,6 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
                     p->net.tensors[o.dst].channels != 16 || (uint32_t)(a.T * (a.n_cls + 1)) != o.cin)
                     return fail(PF_EUNSUPPORTED, "fused stem expects a 3x3/s2 conv %d->16, got %u->%u k%u s%u",
                                 a.T * (a.n_cls + 1), o.cin, o.cout, o.k, o.stride);
-                static const int stem_plane_pad = ab_env("PF_DBG_PLANE_PAD") ? atoi(ab_env("PF_DBG_PLANE_PAD")) : 0;
-                a.dbg_plane_pad = stem_plane_pad;
                 push(S_STEM, i).u.sf.stem = a;
                 pin_fp32(o);
                 continue;

@@ -22,7 +22,6 @@ struct StemArgs {
     unsigned *status;      // range guard of the operand split (conv_mfma.h): |output| > 65504 raises PF_STATUS_RANGE; nullable
     unsigned *range_slot;  // ... and max |output| goes to this word of the status block (low side of the guard); nullable
     long long *probe;      // PF_PROBE builds only
-    int dbg_plane_pad;     // timing experiment only (PF_DBG_PLANE_PAD): extra floats between output planes
 };
 
 struct HeadArgs {

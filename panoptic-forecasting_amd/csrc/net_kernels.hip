@@ -855,7 +855,7 @@ static bool stem_fast_div_exact(float mean, float stdv, float dmin, float dmax) 
 // the conditions of the 2 x 2-outputs-per-lane kernel (the only one that writes the packed-pair layout)
 bool stem_writes_s4(const StemArgs &a) {
     return a.T == 3 && a.wdep && a.woh && !a.seg_is_i64 && (a.W & 3) == 0 && (a.H & 3) == 0 && a.Wout * 2 == a.W && a.Hout * 2 == a.H &&
-           (unsigned long long)a.T * a.H * a.W < (1ull << 32) && !ab_env("PF_STEM_GENERIC") && !ab_env("PF_STEM_BATCHED") && !ab_env("PF_STEM_V3");
+           (unsigned long long)a.T * a.H * a.W < (1ull << 32);
 }
 
 int launch_stem(const StemArgs &a, hipStream_t s) {
@@ -864,12 +864,9 @@ int launch_stem(const StemArgs &a, hipStream_t s) {
     if (a.dst_fmt && !stem_writes_s4(a)) return fail(PF_EUNSUPPORTED, "stem: these arguments select a kernel that writes fp32 only");
     const size_t lds = (size_t)a.T * (a.n_cls + 1) * 9 * 16 * sizeof(float);
     const double ipx = (double)a.B * a.T * a.H * a.W, opx = (double)a.B * a.Hout * a.Wout;
-    static const bool generic = ab_env("PF_STEM_GENERIC") != nullptr;   // A/B switch for profiling
-    const bool batched = a.T == 3 && a.wdep && !generic;
-    static const bool no_v3 = ab_env("PF_STEM_BATCHED") != nullptr;       // A/B switch: the previous form
-    const bool v3 = batched && a.woh && !no_v3 && (unsigned long long)a.T * a.H * a.W < (1ull << 32);
-    static const bool no_v4 = ab_env("PF_STEM_V3") != nullptr;            // A/B switch: one output per lane
-    const bool v4 = v3 && !no_v4 && !a.seg_is_i64 && (a.W & 3) == 0 && (a.H & 3) == 0 && a.Wout * 2 == a.W && a.Hout * 2 == a.H;
+    const bool batched = a.T == 3 && a.wdep;
+    const bool v3 = batched && a.woh && (unsigned long long)a.T * a.H * a.W < (1ull << 32);
+    const bool v4 = v3 && !a.seg_is_i64 && (a.W & 3) == 0 && (a.H & 3) == 0 && a.Wout * 2 == a.W && a.Hout * 2 == a.H;
     const char *label = !batched ? "pf::stem_onehot_kernel(pf::StemArgs)"
                         : v4 ? "pf::stem_onehot_v4_kernel(pf::StemArgs, float)"
                         : v3 ? "pf::stem_onehot_v3_kernel(pf::StemArgs)"
@@ -932,8 +929,7 @@ int launch_head(const HeadArgs &a, hipStream_t s) {
     const float sw = a.Wout > 1 ? (float)(a.Win - 1) / (float)(a.Wout - 1) : 0.f;
     const float shh = a.Hout > 1 ? (float)(a.Hin - 1) / (float)(a.Hout - 1) : 0.f;
     const size_t win = ((size_t)(shh * (kHeadCH - 1)) + 3) * ((size_t)(sw * (kHeadCW - 1)) + 3) * 4;   // window bound of one tile, per channel
-    static const bool no_tile = ab_env("PF_HEAD_UNTILED") != nullptr;   // A/B switch
-    const bool tiled = (a.C == 11 || a.C == 19) && a.Hin >= 2 && a.Win >= 2 && win * a.C <= 60 * 1024 && !no_tile;
+    const bool tiled = (a.C == 11 || a.C == 19) && a.Hin >= 2 && a.Win >= 2 && win * a.C <= 60 * 1024;
     const bool quad = !tiled && (a.Wout & 3) == 0 && 3.f * sw < 1.f && a.Win >= 3;   // 4 consecutive outputs span <= 2 source columns
     // the profile record names the kernel that is launched (the symbol rocprofv3 prints)
     const char *label = tiled ? (a.C == 11 ? "void pf::head_col_kernel<11>(pf::HeadArgs)" : "void pf::head_col_kernel<19>(pf::HeadArgs)")

@@ -27,7 +27,7 @@ int fail(int code, const char *fmt, ...);
         if (_e != hipSuccess) return pf::fail(PF_EHIP, "%s: %s", what, hipGetErrorString(_e)); \
     } while (0)
 
-// A/B and debugging switches read from the environment (PF_STEM_V3, PF_SYNC_OPS, PF_PROBE, ...) exist only in libraries
+// A/B and debugging switches read from the environment (PF_SYNC_OPS, PF_PROBE) exist only in libraries
 // built with -DPF_AB=1 (the probe / A-B targets of the Makefile); the shipped libpfhip.so reads no environment variable
 #ifndef PF_AB
 #define PF_AB 0

@@ -217,11 +217,10 @@ void pack_dma(const BlobOp &o, const float *w, const int *src_ch, Arena &a, Conv
     c.tiled_chunks = dma_chunks(src_ch, (int)o.n_src, (int)o.k, (int)o.stride);
     c.tiled_off = a.take((size_t)((o.cout + 15) / 16) * c.tiled_chunks * (kc / 4) * o.k * o.k * 64);
     pack_conv_weights_tiled(w, (int)o.cin, (int)o.cout, (int)o.k, kc, src_ch, (int)o.n_src, a.at(c.tiled_off));
-    // trailing couts that may run on the vector ALU beside the MFMA tiles (conv_dma.hip); env knobs for A/B runs:
-    // PF_VALU_MAX = largest such group (default 8: beyond that the padded MFMA tile measured faster; 0 disables), PF_VALU_PEEL = 1 also peels a full tile of cout % 16 == 0
-    static const int valu_max = ab_env("PF_VALU_MAX") ? atoi(ab_env("PF_VALU_MAX")) : 8;
-    static const bool valu_peel = ab_env("PF_VALU_PEEL") ? atoi(ab_env("PF_VALU_PEEL")) != 0 : false;
-    const int split = (o.k == 3 && o.stride == 1) ? dma_valu_split((int)o.cout, valu_peel) : 0;
+    // trailing couts that may run on the vector ALU beside the MFMA tiles (conv_dma.hip): groups of at most valu_max (beyond
+    // that the padded MFMA tile measured faster)
+    constexpr int valu_max = 8;
+    const int split = (o.k == 3 && o.stride == 1) ? dma_valu_split((int)o.cout) : 0;
     if (split > 0 && split <= valu_max) {
         c.rem_count = split;
         c.rem_off = a.take((size_t)c.tiled_chunks * (kc / 4) * 9 * dma_rem_rv(split) * 4, 4);

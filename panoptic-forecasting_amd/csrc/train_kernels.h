@@ -6,16 +6,8 @@ namespace pf {
 
 int launch_onehot_dense(const void *seg, int seg_i64, const float *depth, const uint8_t *mask, float mean, float stdv, int B, int T,
                         int n_cls, int H, int W, float *x, hipStream_t s);
-// OIHW (device) -> fragment order of the generic MFMA conv (conv_mfma.hip); transpose_flip = 1 packs the backward-data
-// weights of forward input range [c0, c0 + ch)
-int launch_pack_weights(const float *w, int cin_f, int cout_f, const ConvTiling &t, int transpose_flip, int c0, int ch, float *out,
-                        hipStream_t s);
-// ... -> the per-tile order of the LDS-DMA kernels (conv_dma.hip): src_ch[n_src] = the conv's input ranges (forward), or
-// {forward cout} with transpose_flip (backward-data of forward input range [c0, c0 + ch): a ch-output, cout_f-input conv)
+// floats of one conv's weights in the per-tile order of the LDS-DMA kernels (conv_dma.hip); src_ch[n_src] = its input ranges
 size_t tiled_packed_floats(const int *src_ch, int n_src, int cout, int ks, int stride);
-int launch_pack_weights_tiled(const float *w, int cin_f, int cout_f, int ks, int stride, const int *src_ch, int n_src, int transpose_flip,
-                              int c0, int ch, float *out, hipStream_t s);
-// the same packings for a whole training step in ceil(n / kPackBatch) launches: jobs as kernel arguments
 constexpr int kPackBatch = 24;
 struct PackJob {
     long long w_off, out_off, total;   // floats: weights inside theta, packing inside the arena, packed size
@@ -27,8 +19,11 @@ struct PackBatch {
     PackJob job[kPackBatch];
 };
 static_assert(sizeof(PackBatch) <= 3584, "PackBatch travels as kernel arguments");
+// one job: OIHW (device) -> that order.  src_ch[n_src] = the conv's input ranges (forward), or {forward cout} with transpose_flip
+// (backward-data of forward input range [c0, c0 + ch): a ch-output, cout_f-input conv)
 void pack_job_fill(PackJob &q, size_t w_off, int cin_f, int cout_f, int ks, int stride, const int *src_ch, int n_src, int transpose_flip, int c0,
                    int ch, size_t out_off);
+// the packings of a whole training step in ceil(n / kPackBatch) launches: jobs as kernel arguments
 int launch_pack_weights_batch(const float *theta, float *arena, const PackJob *jobs, int n, hipStream_t s);
 size_t bn_partial_doubles(int C);
 int launch_bn_forward(const float *y, int B, int C, int H, int W, float eps, float momentum, const float *gamma, const float *beta,

@@ -58,93 +58,15 @@ int launch_onehot_dense(const void *seg, int seg_i64, const float *depth, const 
 }
 
 // ------------------------------------------------------------------------------------------------ weight packing on the device
-// OIHW -> the fragment order of conv_mfma.hip::pack_conv_weights ([cout_block][chunk][kgroup][tap][nt][64 lanes]).
-// transpose_flip = 0: forward weights.  transpose_flip = 1: the backward-data convolution of input range [c0, c0+ch):
-//   Wd[co_d][ci_d][tap] = W[ci_d][c0 + co_d][ks2-1-tap]   (ci_d runs over the forward cout)
-__global__ __launch_bounds__(256) void pack_weights_kernel(const float *w, int cin_f, int cout_f, int ks2, int kc, int nt, int nchunks,
-                                                           long long total, int transpose_flip, int c0, int ch, float *out) {
-    const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (o >= total) return;
-    long long r = o;
-    const int lane = (int)(r % 64); r /= 64;
-    const int n = (int)(r % nt); r /= nt;
-    const int tap = (int)(r % ks2); r /= ks2;
-    const int kg = (int)(r % (kc / 4)); r /= (kc / 4);
-    const int chunk = (int)(r % nchunks); r /= nchunks;
-    const int cb = (int)r;
-    const int co = (cb * nt + n) * 16 + (lane & 15), ci = chunk * kc + kg * 4 + (lane >> 4);
-    float v = 0.f;
-    if (!transpose_flip) {
-        if (co < cout_f && ci < cin_f) v = w[((long long)co * cin_f + ci) * ks2 + tap];
-    } else {
-        if (co < ch && ci < cout_f) v = w[((long long)ci * cin_f + c0 + co) * ks2 + (ks2 - 1 - tap)];
-    }
-    out[o] = v;
-}
-
-int launch_pack_weights(const float *w, int cin_f, int cout_f, const ConvTiling &t, int transpose_flip, int c0, int ch, float *out,
-                        hipStream_t s) {
-    const long long total = (long long)t.packed_floats();
-    hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, cin_f, cout_f, t.ks * t.ks, t.kc, t.nt,
-                       t.nchunks, total, transpose_flip, c0, ch, out);
-    PF_LAUNCH_CHECK("pack_weights_kernel");
-    return PF_OK;
-}
-
-// OIHW -> the per-tile order of the LDS-DMA kernels (conv_dma.hip::pack_conv_weights_tiled: [cout tile][chunk][kgroup][tap][64 lanes],
-// K order = the input ranges in order, each padded to whole chunks of kc channels).  Same two modes as above; the
-// backward-data convolution has ONE input range (the forward cout channels of dy).
-struct TiledPackArgs {
-    int cstart[kConvMaxSrc + 1];   // first conv input channel of each range ([n_src] = cin)
-    int chunk0[kConvMaxSrc + 1];   // first chunk of each range ([n_src] = nchunks)
-    int n_src;
-};
-__global__ __launch_bounds__(256) void pack_weights_tiled_kernel(const float *w, int cin_f, int cout_f, int ks2, int kc, TiledPackArgs pa,
-                                                                 long long total, int transpose_flip, int c0, int ch, float *out) {
-    const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (o >= total) return;
-    const int nchunks = pa.chunk0[pa.n_src];
-    long long r = o;
-    const int lane = (int)(r % 64); r /= 64;
-    const int tap = (int)(r % ks2); r /= ks2;
-    const int kg = (int)(r % (kc / 4)); r /= (kc / 4);
-    const int chunk = (int)(r % nchunks); r /= nchunks;
-    const int t = (int)r;
-    int j = 0;
-    while (j + 1 < pa.n_src && chunk >= pa.chunk0[j + 1]) ++j;
-    const int cl = (chunk - pa.chunk0[j]) * kc + kg * 4 + (lane >> 4), nch = pa.cstart[j + 1] - pa.cstart[j];
-    const int co = t * 16 + (lane & 15), ci = pa.cstart[j] + cl;
-    float v = 0.f;
-    if (cl < nch) {
-        if (!transpose_flip) {
-            if (co < cout_f) v = w[((long long)co * cin_f + ci) * ks2 + tap];
-        } else {
-            if (co < ch) v = w[((long long)ci * cin_f + c0 + co) * ks2 + (ks2 - 1 - tap)];   // ci runs over the forward cout
-        }
-    }
-    out[o] = v;
-}
 size_t tiled_packed_floats(const int *src_ch, int n_src, int cout, int ks, int stride) {
     return (size_t)((cout + 15) / 16) * dma_chunks(src_ch, n_src, ks, stride) * (dma_kc(ks, stride) / 4) * ks * ks * 64;
 }
-int launch_pack_weights_tiled(const float *w, int cin_f, int cout_f, int ks, int stride, const int *src_ch, int n_src, int transpose_flip,
-                              int c0, int ch, float *out, hipStream_t s) {
-    TiledPackArgs pa;
-    const int kc = dma_kc(ks, stride);
-    pa.n_src = n_src;
-    pa.cstart[0] = 0;
-    pa.chunk0[0] = 0;
-    for (int j = 0; j < kConvMaxSrc; ++j) {
-        pa.cstart[j + 1] = pa.cstart[j] + (j < n_src ? src_ch[j] : 0);
-        pa.chunk0[j + 1] = pa.chunk0[j] + (j < n_src ? (src_ch[j] + kc - 1) / kc : 0);
-    }
-    const long long total = (long long)tiled_packed_floats(src_ch, n_src, transpose_flip ? ch : cout_f, ks, stride);
-    hipLaunchKernelGGL(pack_weights_tiled_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, cin_f, cout_f, ks * ks, kc, pa, total,
-                       transpose_flip, c0, ch, out);
-    PF_LAUNCH_CHECK("pack_weights_tiled_kernel");
-    return PF_OK;
-}
 
+// OIHW -> the per-tile order of the LDS-DMA kernels (conv_dma.hip::pack_conv_weights_tiled: [cout tile][chunk][kgroup][tap][64 lanes],
+// K order = the input ranges in order, each padded to whole chunks of kc channels).
+// transpose_flip = 0: forward weights.  transpose_flip = 1: the backward-data convolution of input range [c0, c0+ch):
+//   Wd[co_d][ci_d][tap] = W[ci_d][c0 + co_d][ks2-1-tap]   (ci_d runs over the forward cout)
+// which has ONE input range (the forward cout channels of dy).
 // All tiled packings of a training step in a handful of launches (train_plan.hip collects the jobs: one per forward conv, one per
 // backward-data conv): a step used to spend 190 launches of ~4.6 us on them (0.87 ms of a 20.7 ms step).  The jobs travel as kernel
 // arguments, kPackBatch per launch; a workgroup finds its job by a scalar walk over the block prefix

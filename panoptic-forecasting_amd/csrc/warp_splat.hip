@@ -48,34 +48,23 @@ long long *probe_buffer();
 
 constexpr unsigned long long kEmpty = ~0ull;
 constexpr int kThreads = 256;
-// raster workgroup shape (A/B builds: -DPF_RASTER_THREADS=256 -DPF_RASTER_FLIGHT=8 -DPF_RASTER_MINWAVES=1 is the round-2 start).
+// raster workgroup shape (256 threads x 8 tiles in flight at 1 wave per SIMD was the round-2 start).
 // The kernel waits on dependent memory round trips (list -> records -> LDS -> gather -> store) at a workgroup count per CU
 // that its 32 KB z-buffer fixes at 4: waves hide that better than loads in flight per wave.  Same box, 16 frames:
 // 256 threads x 8 tiles in flight (4 waves per SIMD, 109 registers) 557 us; 512 x 4 at 4 waves 652; 512 x 4 at 5 waves (66
 // registers) 517; 512 x 2 at 8 waves (64 registers) 460-478; 512 x 3 at 8 waves 470; 512 x 1 at 8 waves 485.
-// invalid-point mark stores of bin_kernel (same-box A/B, 32 frames, profiles/r06_experiments.md): 0 = four unconditional byte stores
-// (rounds 1-5): 1138 / 1119 / 1138 us; 1 = only the distinct bins: 1088 / 1093 / 1095; 2 (shipped) = distinct bins, the two bins of a
-// row as one two-byte store: 1064 / 1071 / 1067 (-6 %).  Bit-exact either way (tests/test_gpu_warp_splat.py, test_gpu_pipeline.py)
-#ifndef PF_MARK_VARIANT
-#define PF_MARK_VARIANT 2
-#endif
-#ifndef PF_RASTER_THREADS
-#define PF_RASTER_THREADS 512
-#endif
-#ifndef PF_RASTER_FLIGHT
-#define PF_RASTER_FLIGHT 2
-#endif
-#ifndef PF_RASTER_MINWAVES
-#define PF_RASTER_MINWAVES 8   // __launch_bounds__' second argument on HIP: waves per SIMD -> 64 registers
-#endif
-constexpr int kRThreads = PF_RASTER_THREADS;   // raster workgroup: kRHalves groups of 256 threads, each group takes its own source tile
+// invalid-point mark stores of bin_kernel (same-box A/B, 32 frames, profiles/r06_experiments.md): four unconditional byte stores
+// (rounds 1-5) took 1138 / 1119 / 1138 us; only the distinct bins 1088 / 1093 / 1095; the shipped form - distinct bins, the two bins
+// of a row as one two-byte store - 1064 / 1071 / 1067 (-6 %).  All three were bit-exact
+constexpr int kRThreads = 512;            // raster workgroup: kRHalves groups of 256 threads, each group takes its own source tile
+constexpr int kRMinWaves = 8;             // __launch_bounds__' second argument on HIP: waves per SIMD -> 64 registers
 constexpr int kRHalves = kRThreads / 256;
 constexpr int kSrcTH = 16, kSrcTW = 64;   // source tile (pixels); 256 threads x 4 consecutive pixels
 constexpr int kDstTH = 32, kDstTW = 128;  // destination tile owned by one raster workgroup (32 KB LDS)
 constexpr int kScan = 256;                // bounding boxes tested per thread-pass (overflow path only)
 constexpr int kScanBatches = 8;           // (the list holds kScan * kScanBatches = 2048 tile ids)
 constexpr int kListCap = 64;              // source-tile ids per destination-tile list written by bin_kernel (typical fill 6-12)
-constexpr int kFlight = PF_RASTER_FLIGHT;  // source tiles whose projections a group of 256 raster threads keeps in flight
+constexpr int kFlight = 2;                // source tiles whose projections a group of 256 raster threads keeps in flight
 constexpr int kIdFrameShift = 20;         // list entry = (frame inside the z-buffer group) << 20 | source tile  (in the raster workgroup's LDS
                                           // copy: | source tile row << 10 | column; both < 1024 as bins have 13 bits)
 constexpr int kZSlots = 64;               // atomicMax slots per z-buffer group (spreads the memory-side atomics)
@@ -409,16 +398,7 @@ __global__ __launch_bounds__(kThreads) void bin_kernel(SplatArgs a) {
                 // the uniform base: N < 2^30 is checked at launch)
                 const unsigned o00 = (unsigned)p.y0 * (unsigned)a.W + (unsigned)p.x0, dxo = (unsigned)(p.x1 - p.x0);
                 const unsigned o10 = (unsigned)p.y1 * (unsigned)a.W + (unsigned)p.x0;
-#if PF_MARK_VARIANT == 1
-                // A/B (profiles/r06_experiments.md): only the DISTINCT bins are marked - a point clamped to the image edge has
-                // x1 == x0 and / or y1 == y0 and stores once or twice instead of four times
-                mark[o00] = 1;
-                if (dxo) mark[o00 + 1] = 1;
-                if (o10 != o00) {
-                    mark[o10] = 1;
-                    if (dxo) mark[o10 + 1] = 1;
-                }
-#elif PF_MARK_VARIANT == 2
+                // only the DISTINCT bins are marked (a point clamped to the image edge has x1 == x0 and / or y1 == y0):
                 // the two bins of a row as ONE two-byte store where they differ (x1 = x0 + 1 <= W - 1: inside the row; the store may be
                 // unaligned - global memory takes that), a byte store where they do not; the second row only if it is another row
                 if (dxo) {
@@ -428,12 +408,6 @@ __global__ __launch_bounds__(kThreads) void bin_kernel(SplatArgs a) {
                     mark[o00] = 1;
                     if (o10 != o00) mark[o10] = 1;
                 }
-#else
-                mark[o00] = 1;
-                mark[o10] = 1;
-                mark[o00 + dxo] = 1;
-                mark[o10 + dxo] = 1;
-#endif
             }
         }
         if ((a.W & 3) == 0) {   // the raster pass re-reads these instead of re-projecting (coalesced 32 B per thread)
@@ -510,7 +484,7 @@ __global__ __launch_bounds__(kThreads) void bin_kernel(SplatArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kRThreads, PF_RASTER_MINWAVES) void raster_kernel(SplatArgs a) {
+__global__ __launch_bounds__(kRThreads, kRMinWaves) void raster_kernel(SplatArgs a) {
     __shared__ unsigned long long zb[kDstTH * kDstTW];   // 16 KB
     __shared__ unsigned short list[kScan * kScanBatches];
     __shared__ unsigned ent[kListCap];
@@ -797,7 +771,7 @@ extern "C" int pf_warp_splat(const float *depth, const uint8_t *depth_mask, cons
     a.stx = L.stx; a.sty = L.sty; a.dtx = L.dtx; a.dty = L.dty;
     a.probe = nullptr;
 #if PF_PROBE
-    static const bool splat_probe = ab_env("PF_PROBE") != nullptr;   // read once, not per call
+    static const bool splat_probe = pf::ab_env("PF_PROBE") != nullptr;   // read once, not per call
     a.probe = splat_probe ? pf::probe_buffer() : nullptr;
 #endif
     hipStream_t s = (hipStream_t)stream;

@@ -319,6 +319,14 @@ int pf_odom_forward(const float *packed, int flags, int B, int T_in, int T_out, 
  *                   cout tile pads with zeros): 1 = where it measured faster (launches of 65k-196k pixels), 0 = never, 2 = wherever
  *                   the kernel exists, 3 = everywhere and never merged, 4 = the merged pairs only (A/B runs, tests); results agree
  *                   with the two launches within 1e-5 (1 + max) (tests/test_gpu_conv.py);
+ *   "share_s"       (default 1) an odd HarDBlock layer's launch also sums its consumer's rows over the input both read (csrc/conv_s4.hip,
+ *                   conv_s4_share_kernel: the odd layer's couts rounded up to 4, then the consumer's, in common cout tiles), and the
+ *                   consumer's launch runs over its other ranges and adds the stored sums before bias and ReLU (conv_s4_add_kernel):
+ *                   the common input is read once and the consumer's padding rows do the work.  1 = where it measured faster
+ *                   (csrc/conv_select.cpp::share_wanted), 0 = never - and a plan CREATED while the process-wide value is 0 packs no
+ *                   weights for it -, 2 = wherever the two forms exist (A/B runs, tests); the workspace grows by one scratch region
+ *                   of the largest such consumer (fp32); results agree with the two plain launches within 1e-5 (1 + max)
+ *                   (tests/test_gpu_share_s.py);
  *   "train_blocked_sum" (default 1; process-wide only) the 3x3 convolutions of a training step add every round of 8 input channels
  *                   into a second accumulator set (blocked summation, like ATen's): forward activations 0.79-0.95 x as far from
  *                   float64 as torch-CPU fp32; 0 = one fp32 chain over all 9 Cin terms;
@@ -442,6 +450,12 @@ int pf_profile_get(int i, char *label, size_t label_cap, int *launches, double *
  * the cost model or pf_train_autotune, and pf_train_path_stats counts it in none of stats[0..2] (tests: every built shape of the
  * training convolutions against a reference). */
 int pf_debug_force_conv(int kind, int p0, int p1, int p2);
+/* Host only, no device involved (tests): the weight arena a plan created now from this blob would upload - every packing of every
+ * convolution under the process-wide options - copied to out when cap >= *n_floats, and per op of the table (table_ops rows of six
+ * numbers, nullable): offset in floats and rounds of its packed-pair packing, offset and cout tiles of its share launch's packing,
+ * offset and rounds of its add launch's ("share_s"; 0 = the op has none). */
+int pf_debug_plan_arena(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                        long long *table, int table_ops);
 /* Instrumented builds only (make libpfhip_probe.so, env PF_PROBE=1): the 64 in-kernel timestamps (shader clock)
  * written by workgroup 0 / wave 0 of the last conv_wave launch; PF_EINVAL when nothing was recorded. */
 int pf_debug_probe_read(long long *host64);

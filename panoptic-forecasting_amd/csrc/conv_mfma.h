@@ -62,6 +62,13 @@ struct ConvArgs {
     int src_gn[kConvMaxSrc];      // number of groups it touches
     int src_ent0[kConvMaxSrc + 1];// first K entry of each range ("group entries": one group of one range; padded per range to
                                   // whole rounds when the conv was packed with pad_sources)
+    // ---- the share / add forms of the 3x3 packed-pair kernel (conv_s4.hip: launch_conv_s4_share / _add; zero for every other launch).
+    //      An odd HarDBlock layer P = conv(S) and its consumer C = conv(P ++ S ++ others): the share launch runs over S with P's rows
+    //      and C's rows over S in common cout tiles, the add launch runs C over its other ranges and adds the stored sums
+    float *share;            // [B][ceil(share_cout / 4)][H][W][4] fp32: C's sums over S times C's acc_scale (no bias, no ReLU)
+    int share_off;           // share form: first matrix row of C's part = P's couts rounded up to 4
+    int share_cout;          // C's output channels
+    float share_scale;       // share form: C's acc_scale (this launch's acc_scale is P's)
 };
 
 // ---- the two-term operand split of conv_split.hip / conv_s4.hip ------------------------------------------------------
@@ -280,6 +287,14 @@ int s4_rounds(const S4Range *r, int n_src, int ks, int pad_sources);
 size_t s4_packed_floats(const S4Range *r, int n_src, int cout, int ks, int pad_sources);
 void pack_conv_weights_s4(const float *w_oihw, int cin, int cout, int ks, const S4Range *r, int n_src, int pad_sources, float *out);
 int launch_conv_s4(const ConvArgs &a, int ks, int nt, int wide, int B, hipStream_t stream);
+// a pair P = conv3x3(S), C = conv3x3(P ++ S ++ others) as two launches that read S once (8 x 32 tiles, nt cout tiles per workgroup;
+// ConvArgs::share ..): `share` = P's launch whose matrix also holds C's rows over S and stores their sums, `add` = C's launch over its
+// other ranges, which adds them.  share_wanted (conv_select.cpp): mode = the plan's share_s option (0 never, 1 the measured rule, 2 wherever
+// the forms exist)
+int launch_conv_s4_share(const ConvArgs &a, int nt, int B, hipStream_t stream);
+int launch_conv_s4_add(const ConvArgs &a, int nt, int B, hipStream_t stream);
+inline int share_row0(int p_cout) { return (p_cout + 3) / 4 * 4; }   // a lane's four couts never straddle the two convs
+bool share_wanted(int p_cin, int p_cout, int c_cin, int c_cout, int h, int w, int B, int mode);
 // the same with an explicit start of every range in the conv's input-channel numbering (cstart[j]; nullptr = the ranges are
 // consecutive): ranges may then be packed in ANOTHER order than the one they are concatenated in (conv_pair.hip)
 void pack_conv_weights_s4_ex(const float *w_oihw, int cin, int cout, int ks, const S4Range *r, const int *cstart, int n_src, int pad_sources, float *out);

@@ -86,19 +86,35 @@ struct S4Cfg {
 // chain over all 9 Cin terms: the forward pass of a training step is then as close to float64 as the fp32 step's
 #define S4_KERNEL_NAME conv_s4_kernel
 #define S4_KERNEL_KACC 0
+#define S4_KERNEL_EPI 0
 #define S4_KERNEL_WAVES (KS_ == 4 ? 1 : (TH_ == 16 || KS_ == 2) ? 2 : (TW_ == 32 && NT <= 2) ? 4 : (TW_ == 32 && NT == 3) ? 3 : 2)
 #include "conv_s4_kernel.inc"
 #undef S4_KERNEL_NAME
+// the share / add forms (an odd HarDBlock layer's launch also sums its consumer's rows over their common source; the consumer's launch
+// adds them: launch_conv_s4_share / _add below), instantiated for 8 x 32 tiles without a K split at the plain form's launch bounds
+#undef S4_KERNEL_EPI
+#define S4_KERNEL_NAME conv_s4_share_kernel
+#define S4_KERNEL_EPI 1
+#include "conv_s4_kernel.inc"
+#undef S4_KERNEL_NAME
+#undef S4_KERNEL_EPI
+#define S4_KERNEL_NAME conv_s4_add_kernel
+#define S4_KERNEL_EPI 2
+#include "conv_s4_kernel.inc"
+#undef S4_KERNEL_NAME
+#undef S4_KERNEL_EPI
 #undef S4_KERNEL_KACC
 #undef S4_KERNEL_WAVES
 // the blocked-sum form (instantiated for 8 x 32 tiles without a K split): one workgroup per CU fewer than the plain form where the
 // second accumulator set needs the registers
 #define S4_KERNEL_NAME conv_s4_blocked_kernel
 #define S4_KERNEL_KACC 1
+#define S4_KERNEL_EPI 0
 #define S4_KERNEL_WAVES (NT == 1 ? 4 : (NT == 2 ? 3 : 2))
 #include "conv_s4_kernel.inc"
 #undef S4_KERNEL_NAME
 #undef S4_KERNEL_KACC
+#undef S4_KERNEL_EPI
 #undef S4_KERNEL_WAVES
 
 template <int NT, int TW_, int TH_ = 8, int KS_ = 1>
@@ -142,6 +158,62 @@ static int launch_s4_blocked_cfg(const ConvArgs &a0, int B, hipStream_t s) {
     PF_LAUNCH_CHECK("conv_s4_blocked_kernel");
     return PF_OK;
 }
+
+// the share (ADD = false) / add form on 8 x 32 tiles, NT cout tiles per workgroup
+template <int NT, bool ADD>
+static int launch_s4_share_cfg(const ConvArgs &a0, int B, hipStream_t s) {
+    using C = S4Cfg<NT, 32, 8, 1>;
+    ConvArgs a = a0;
+    a.tilesX = (a.Wout + C::TW - 1) / C::TW;
+    a.tilesY = (a.Hout + C::TH - 1) / C::TH;
+    const void *fn = ADD ? reinterpret_cast<const void *>(&conv_s4_add_kernel<NT, 32, 8, 1>) : reinterpret_cast<const void *>(&conv_s4_share_kernel<NT, 32, 8, 1>);
+    static bool attr_set = false;
+    if (!attr_set) {
+        PF_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
+        attr_set = true;
+    }
+    char label[96];
+    snprintf(label, sizeof(label), "void pf::conv_s4_%s_kernel<%d, 32, 8, 1>(pf::ConvArgs)", ADD ? "add" : "share", NT);
+    const double px = (double)B * a.Hout * a.Wout;
+    const int rows = ADD ? a.Cout : a.Cout + a.share_cout;   // output channels the matrix instructions produce
+    ProfScope ps(s, label, 2.0 * px * rows * a.Cin * 9,
+                 4.0 * ((double)B * a.Cin * a.Hin * a.Win + px * (a.Cout + (double)(a.share_cout + 3) / 4 * 4) + (double)rows * a.Cin * 9));
+    const dim3 grid(a.tilesX * a.tilesY, (a.ntiles + NT - 1) / NT, B);
+    if (ADD) hipLaunchKernelGGL((conv_s4_add_kernel<NT, 32, 8, 1>), grid, dim3(C::NTHR), C::LDS_BYTES, s, a);
+    else hipLaunchKernelGGL((conv_s4_share_kernel<NT, 32, 8, 1>), grid, dim3(C::NTHR), C::LDS_BYTES, s, a);
+    PF_LAUNCH_CHECK(ADD ? "conv_s4_add_kernel" : "conv_s4_share_kernel");
+    return PF_OK;
+}
+
+// a pair P = conv3x3(S), C = conv3x3(P ++ S ++ others) as two launches that read S once:
+// share: a = P's launch with a.wpk = pack of [P's rows; zero rows up to a.share_off; C's rows over the columns of S] (a.ntiles tiles of
+//        that matrix), a.share / share_off / share_cout / share_scale filled; P's slice is stored as by the plain kernel
+// add:   a = C's launch without the range S (weights packed without its columns), a.share / share_cout filled
+static int check_share(const ConvArgs &a, const char *who) {
+    if (!a.src_fmt || !a.dst_fmt) return fail(PF_EINVAL, "%s: sources and destination in the S4 layout only", who);
+    if ((a.Wout & 3) != 0 || a.Hin != a.Hout || a.Win != a.Wout) return fail(PF_EUNSUPPORTED, "%s: stride 1, width %% 4 == 0 only", who);
+    if (a.pool || a.res || a.no_bias || a.kacc) return fail(PF_EUNSUPPORTED, "%s: no fused epilogue stages", who);
+    if (a.chunk_begin != 0 || a.chunk_end != a.nchunks) return fail(PF_EUNSUPPORTED, "%s: whole K range only", who);
+    if (!a.share || a.share_cout < 1 || (reinterpret_cast<uintptr_t>(a.share) & 15) != 0) return fail(PF_EINVAL, "%s: no scratch tensor", who);
+    return PF_OK;
+}
+#define PF_S4_SHARE(ADD_) \
+    nt = nt < 1 ? 1 : (nt > a.ntiles ? a.ntiles : nt); \
+    if (nt == 1) return launch_s4_share_cfg<1, ADD_>(a, B, s); \
+    if (nt == 2) return launch_s4_share_cfg<2, ADD_>(a, B, s); \
+    return launch_s4_share_cfg<3, ADD_>(a, B, s);
+int launch_conv_s4_share(const ConvArgs &a, int nt, int B, hipStream_t s) {
+    if (int rc = check_share(a, "conv_s4 share")) return rc;
+    if ((a.share_off & 3) != 0 || a.share_off < a.Cout || a.share_off + a.share_cout > a.ntiles * 16)
+        return fail(PF_EINVAL, "conv_s4 share: rows %d + %d in %d tiles", a.share_off, a.share_cout, a.ntiles);
+    PF_S4_SHARE(false)
+}
+int launch_conv_s4_add(const ConvArgs &a, int nt, int B, hipStream_t s) {
+    if (int rc = check_share(a, "conv_s4 add")) return rc;
+    if (a.share_cout != a.Cout) return fail(PF_EINVAL, "conv_s4 add: stored sums of %d channels for %d", a.share_cout, a.Cout);
+    PF_S4_SHARE(true)
+}
+#undef PF_S4_SHARE
 
 // ------------------------------------------------------------------------------------------------
 // 1x1: a streaming kernel (these layers are bound by their bytes: 2*Cin*Cout flops per pixel against 4*(Cin+Cout) bytes).

@@ -3,9 +3,13 @@
 //   S4_KERNEL_NAME   conv_s4_kernel | conv_s4_blocked_kernel
 //   S4_KERNEL_KACC   0 | 1: every round's products summed on their own and added to a second accumulator set (training)
 //   S4_KERNEL_WAVES  waves per SIMD of __launch_bounds__
+//   S4_KERNEL_EPI    0 | 1 "share" | 2 "add": the epilogue (DESIGN.md 4; ConvArgs::share ..).  share: matrix rows from a.share_off on are
+//                    ANOTHER conv's sums over this launch's source, stored as fp32 units of four channels (acc * a.share_scale; no bias,
+//                    no ReLU, no range report); the rows below it take the plain epilogue.  add: v = fma(acc, acc_scale, stored) + bias
 template <int NT, int TW_, int TH_, int KS_>
 __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAME(ConvArgs a) {
     [[maybe_unused]] constexpr int KACC = S4_KERNEL_KACC;
+    [[maybe_unused]] constexpr int EPI = S4_KERNEL_EPI;
 #if defined(__HIP_DEVICE_COMPILE__)
     using C = S4Cfg<NT, TW_, TH_, KS_>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
@@ -80,7 +84,9 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
     if (wave_all == 0 && lane < NT * 16) {
         const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void *)a.bias, 0, 0x7FFFFFFF, 0x00020000);
         const int co = tile0 * 16 + lane;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, (s4_lds_ptr_t)bias_lds, 4, co < a.ntiles * 16 ? (unsigned)co * 4u : kS4Oob, 0, 0, 0);
+        // (share: the bias array is the odd layer's, padded to ITS tiles)
+        const int nbias = EPI == 1 ? (a.Cout + 15) / 16 * 16 : a.ntiles * 16;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, (s4_lds_ptr_t)bias_lds, 4, co < nbias ? (unsigned)co * 4u : kS4Oob, 0, 0, 0);
     }
 
     const int nrounds = a.nchunks;   // 3x3 launches always run the whole K range (the collected tap spans 4 rounds)
@@ -291,6 +297,26 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
         // loaded before the loop - got an s_waitcnt vmcnt(0) in EVERY iteration of that loop, and on gfx950 stores count in
         // vmcnt: each unit then sat through the store round trips of the unit before it (tools/asm_store_waits.py lists the
         // kernels that wait for their own stores).  One wait the pass can see, here:
+        // (add: the lane's units of the stored sums are loaded in front of that wait - the main-loop state is dead, they take its registers)
+        [[maybe_unused]] s4_f32x4 part[EPI == 2 ? C::MP : 1][EPI == 2 ? NT : 1];
+        [[maybe_unused]] const size_t su_frame = EPI ? (size_t)((a.share_cout + 3) >> 2) * a.Hout * a.Wout : 0;   // 16-B units per frame of a.share
+        if constexpr (EPI == 2) {
+#pragma unroll
+            for (int m = 0; m < C::MP; ++m) {
+                const int mt = wave * C::MP + m;
+                const int oy = tileY * C::TH + mt / C::MTR;
+                const int ox = tileX * C::TW + (mt % C::MTR) * 16 + (lane & 15);
+                const bool in = oy < a.Hout && ox < a.Wout;
+#pragma unroll
+                for (int n = 0; n < NT; ++n) {
+                    const int co = (tile0 + n) * 16 + 4 * (lane >> 4);
+                    part[m][n] = s4_f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (in && co < a.share_cout)
+                        part[m][n] = reinterpret_cast<const s4_f32x4 *>(a.share)[(size_t)b * su_frame + (size_t)(co >> 2) * a.Hout * a.Wout +
+                                                                                 (size_t)oy * a.Wout + ox];
+                }
+            }
+        }
         __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0), expcnt / lgkmcnt untouched
         const int g = lane >> 4, px = lane & 15;
         const size_t hw = (size_t)a.Hout * a.Wout;
@@ -335,11 +361,28 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
                 const int co = (tile0 + n) * 16 + 4 * g;
+                if constexpr (EPI == 1) {
+                    // the consumer's rows: channels cs .. cs + 3 of its sums over this source, one fp32 unit (rows past its couts
+                    // inside the last unit multiplied zero weights).  Not stored values of any tensor: no range_acc
+                    const int cs = co - a.share_off;
+                    if (cs >= 0) {
+                        if (cs < a.share_cout) {
+                            s4_f32x4 u = acc[m][n];
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) u[r] *= a.share_scale;   // 2^-k: exact
+                            reinterpret_cast<s4_f32x4 *>(a.share)[(size_t)b * su_frame + (size_t)(cs >> 2) * hw + pix] = u;
+                        }
+                        continue;
+                    }
+                }
                 if (co >= a.Cout + 2) continue;
                 s4_f32x4 v = acc[m][n];
                 const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(bias_lds + n * 16 + 4 * g);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r] * a.acc_scale + b4[r], relu_lo);   // relu_lo = 0 or -inf: one max, no select
+                for (int r = 0; r < 4; ++r) {
+                    if constexpr (EPI == 2) v[r] = fmaxf(__builtin_fmaf(v[r], a.acc_scale, part[m][n][r]) + b4[r], relu_lo);
+                    else v[r] = fmaxf(v[r] * a.acc_scale + b4[r], relu_lo);   // relu_lo = 0 or -inf: one max, no select
+                }
                 vmax = range_acc(vmax, v[0], v[1], v[2], v[3]);
                 if (a.dst_fmt) {
                     store_px(co, pix, v);

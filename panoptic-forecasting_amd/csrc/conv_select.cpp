@@ -93,6 +93,22 @@ bool pair_wanted(int p_cin, int p_cout, int c_cin, int c_cout, int h, int w, int
     return c_cout <= 32 && p_cout <= 16 && px >= 65536 && px <= 196608;
 }
 
+// conv_s4.hip share / add instead of the two plain launches of a pair?  mode = plan option share_s: 0 never, 2 wherever the forms exist
+// (tests, A/B runs), 1 (default): where the packed rows (P's couts rounded up to 4, then C's) need fewer cout tiles than the two launches
+// together, outside the window in which pair_wanted selects conv_pair, and only for the pairs whose share + add launches MEASURED faster
+// than the two plain ones in every run (MI355X, 1024x2048 network, B = 32 per launch, same box: profiles/r07_experiments.md)
+bool share_wanted(int p_cin, int p_cout, int c_cin, int c_cout, int h, int w, int B, int mode) {
+    if (mode >= 2) return true;
+    if (mode <= 0) return false;
+    const int packed = (share_row0(p_cout) + c_cout + 15) / 16, apart = (p_cout + 15) / 16 + (c_cout + 15) / 16;
+    if (packed >= apart || pair_wanted(p_cin, p_cout, c_cin, c_cout, h, w, B, 1)) return false;
+    // the measured winners: 48 -> 10 -> 18 (635-637 -> 534-547 us) and 63 -> 10 -> 18 (772-775 -> 605-623 us) at 256x512, B = 32: launches
+    // of 4 M pixels, S of 48 channels or more.  The two (24, 40) pairs of the 32x64 level (four tiles instead of five) gained 3-5 us of 45
+    // each in every run, 0.06 % of a step and a fifth of the headline's own spread: they stay as they are; every other pair of the
+    // network packs no tile away or measured slower
+    return p_cout == 10 && c_cout == 18 && p_cin >= 48 && (long)B * h * w >= 4194304;
+}
+
 ConvChoice choose_conv(int ks, int stride, int cin, int cout, int hout, int wout, int B, int need, int use_tuned) {
     if (stride != 1) return ConvChoice{1, 0, 0, 0};           // conv_dma, shape by its cost model
     // The table was measured at B = 1, 2, 4, 8, 16 and (round 5, the strict-fp32 model at the headline's sub-batch) 32; a layer

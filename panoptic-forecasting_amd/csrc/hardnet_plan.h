@@ -34,6 +34,10 @@ struct ConvPlan {
     size_t pair_c_off = 0, pair_two_off = 0, pair_nine_off = 0;
     int pair_rounds = 0;
     bool pair_merged = false;              // pair_c_off carries P's weights in C's padding rows (conv_mfma.h: PairArgs::merged)
+    // the share / add launches of the same pair (conv_s4.hip), kept on the consumer too and packed only by plans created with share_s != 0:
+    // [P's rows; C's rows over the columns of S] over S (share_a_tiles cout tiles), and C without the columns of S (share_b_rounds rounds)
+    size_t share_a_off = 0, share_b_off = 0;
+    int share_a_tiles = 0, share_b_rounds = 0;
 };
 
 // The switches a plan carries (include/pfhip.h documents each), with their defaults.  g_plan_opt is the process-wide set
@@ -48,6 +52,8 @@ struct PlanOptions {
     int normalize_ranges = 1;  // per-channel power-of-two scaling of the stored activations, fixed at plan creation; process-wide only
     int profile_tag_ops = 0;   // pf_profile_* records carry one label per op of the table (tools/)
     int fuse_pairs = 1;        // conv_pair.hip: an odd HarDBlock layer runs inside its consumer where both read / write packed pairs (0 = two launches)
+    int share_s = 1;           // conv_s4.hip share / add: an odd HarDBlock layer's launch also sums its consumer's rows over their common source
+                               // (0 = off, and a plan created with 0 packs nothing for it; 1 = conv_select.cpp::share_wanted; 2 = wherever built)
 };
 
 struct pf_plan {
@@ -83,8 +89,9 @@ constexpr size_t kStatusBytes = PF_WS_STATUS_BYTES;
 constexpr int kStickyWord = PF_WS_STICKY_OFFSET / 4, kLiveWord = 2, kSlot0 = 16, kMaxSlots = ((int)(kStatusBytes / 4) - kSlot0) / 2;
 
 // the plan's geometry for a batch of B inputs of H x W: every tensor's size and workspace offset ((size_t)-1: not stored), and
-// the workspace size (plan_access.hip)
-int layout(const pf_plan *p, int B, int H, int W, std::vector<Dims> &d, std::vector<size_t> &off, size_t &total);
+// the workspace size (plan_access.hip).  share_off (nullable): offset of the scratch region of the share / add launches - one region,
+// sized for the largest pair the plan has packings for, reused by all of them; (size_t)-1 when the plan has none
+int layout(const pf_plan *p, int B, int H, int W, std::vector<Dims> &d, std::vector<size_t> &off, size_t &total, size_t *share_off = nullptr);
 
 // ops i (P) and i + 1 (C) form a pair conv_pair.hip can run as one launch (plan_create.hip)
 bool is_conv_pair(const NetTable &t, size_t i);

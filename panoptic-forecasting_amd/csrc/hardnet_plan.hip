@@ -17,7 +17,7 @@ namespace {
 // ---- A forward = build_schedule (host code only: every launch with all its arguments, each naming exactly one kernel) + the
 //      enqueue loop of run_net.  S_CONV: inside build_schedule only, a convolution whose kernel is picked once the formats are known
 enum StepKind : uint8_t {
-    S_RANGE_CHECK, S_STEM, S_STEM_FRONT, S_PAIR, S_CONV, S_CONV_S4, S_CONV_GENERIC, S_CONV_SPLIT, S_CONV_SPLIT1, S_CONV_WAVE, S_CONV_DMA,
+    S_RANGE_CHECK, S_STEM, S_STEM_FRONT, S_PAIR, S_CONV, S_CONV_S4, S_CONV_S4_SHARE, S_CONV_S4_ADD, S_CONV_GENERIC, S_CONV_SPLIT, S_CONV_SPLIT1, S_CONV_WAVE, S_CONV_DMA,
     S_POOL, S_UPSAMPLE, S_HEAD };
 struct PlainArgs { const float *src; float *dst; int planes, hin, win, hout, wout; size_t n; unsigned *status, *slot; };   // pool, upsample, range check
 struct Step {
@@ -46,7 +46,8 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
     std::vector<Dims> d;
     std::vector<size_t> off;
     size_t ws_need = 0;
-    int rc = layout(p, B, H, W, d, off, ws_need);
+    size_t share_off = (size_t)-1;
+    int rc = layout(p, B, H, W, d, off, ws_need, &share_off);
     if (rc) return rc;
     if (ws_bytes < ws_need) return fail(PF_EWORKSPACE, "workspace %zu B < required %zu B", ws_bytes, ws_need);
     const uint32_t input = p->net.ops[0].src[0].tensor;
@@ -420,16 +421,51 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
     }
 
     // ---- 5. an odd HarDBlock layer inside its consumer (conv_pair.hip): two adjacent steps P = op i, C = op i + 1 that both read
-    //      and write packed pairs become one
+    //      and write packed pairs become one; or (conv_s4.hip share / add) stay two launches that read their common source S once: P's
+    //      launch also sums C's rows over S, C's launch runs over its other ranges and adds them
     size_t w = 0;
     for (size_t k = 0; k < steps.size(); ++k, ++w) {
         const size_t i = (size_t)steps[k].op;
         // (reading S4 implies a width % 4 == 0 and no forced kernel but conv_s4)
-        const bool pair = p->opt.fuse_pairs && k + 1 < steps.size() && steps[k].kind == S_CONV_S4 && steps[k + 1].kind == S_CONV_S4 &&
-                          steps[k + 1].op == (int)i + 1 && is_conv_pair(p->net, i) && p->conv[i + 1].pair_c_off && steps[k].u.c.dst_fmt && steps[k + 1].u.c.dst_fmt;
+        const bool adjacent = k + 1 < steps.size() && steps[k].kind == S_CONV_S4 && steps[k + 1].kind == S_CONV_S4 && steps[k + 1].op == (int)i + 1 &&
+                              is_conv_pair(p->net, i) && steps[k].u.c.dst_fmt && steps[k + 1].u.c.dst_fmt;
+        const bool pair = p->opt.fuse_pairs && adjacent && p->conv[i + 1].pair_c_off;
         const BlobOp &o = p->net.ops[i];
         if (!pair || !pair_wanted((int)o.cin, (int)o.cout, (int)p->net.ops[i + 1].cin, (int)p->net.ops[i + 1].cout, d[o.dst].h, d[o.dst].w, Bt,
                                   p->opt.fuse_pairs)) {
+            // share / add: 8 x 32 tiles without a K split for both launches, packings made at plan creation
+            if (adjacent && p->opt.share_s && p->conv[i + 1].share_a_off && share_off != (size_t)-1 && steps[k].wide == 0 && steps[k + 1].wide == 0 &&
+                share_wanted((int)o.cin, (int)o.cout, (int)p->net.ops[i + 1].cin, (int)p->net.ops[i + 1].cout, d[o.dst].h, d[o.dst].w, Bt, p->opt.share_s)) {
+                const ConvPlan &cc = p->conv[i + 1];
+                Step sa = steps[k], sb = steps[k + 1];
+                float *const sums = reinterpret_cast<float *>((char *)ws + share_off);
+                ConvArgs &a = sa.u.c, &c = sb.u.c;
+                sa.kind = S_CONV_S4_SHARE;
+                a.wpk = p->dev_weights + cc.share_a_off; a.ntiles = cc.share_a_tiles;
+                a.share = sums; a.share_off = share_row0((int)o.cout); a.share_cout = c.Cout; a.share_scale = cc.split_acc_scale;
+                sa.nt = cc.share_a_tiles <= 3 ? cc.share_a_tiles : 2;
+                // the consumer without its second range S
+                sb.kind = S_CONV_S4_ADD;
+                c.Cin -= c.src_cstart[2] - c.src_cstart[1];
+                for (int j = 1; j + 1 < c.n_src; ++j) {
+                    c.src[j] = c.src[j + 1]; c.src_ctotal[j] = c.src_ctotal[j + 1]; c.src_choff[j] = c.src_choff[j + 1];
+                    c.src_c4[j] = c.src_c4[j + 1]; c.src_g0[j] = c.src_g0[j + 1]; c.src_gn[j] = c.src_gn[j + 1];
+                }
+                --c.n_src;
+                int e = 0;
+                for (int j = 0; j <= kConvMaxSrc; ++j) {
+                    c.src_ent0[j] = e;
+                    if (j < c.n_src) e += c.src_gn[j];
+                }
+                c.src_end = c.n_src;
+                c.wpk = p->dev_weights + cc.share_b_off; c.nchunks = cc.share_b_rounds;
+                c.chunk_begin = 0; c.chunk_end = c.nchunks;
+                c.share = sums; c.share_cout = c.Cout;
+                steps[w] = sa;
+                steps[++w] = sb;
+                ++k;
+                continue;
+            }
             if (w != k) steps[w] = steps[k];
             continue;
         }
@@ -506,6 +542,8 @@ int run_net(const pf_plan *p, const StemArgs *stem, const float *dense_x, int B,
                 st.u.sf.front.probe = probe; rc = launch_conv_front(st.u.sf.front, B, s); break;
             case S_PAIR: st.u.pair.c.probe = probe; rc = launch_conv_pair(st.u.pair, B, s); break;
             case S_CONV_S4: rc = launch_conv_s4(a, (int)o.k, st.nt, st.wide, B, s); break;
+            case S_CONV_S4_SHARE: rc = launch_conv_s4_share(a, st.nt, B, s); break;
+            case S_CONV_S4_ADD: rc = launch_conv_s4_add(a, st.nt, B, s); break;
             case S_CONV_GENERIC: rc = launch_conv(a, p->conv[st.ci].tiling, B, s); break;
             case S_CONV_SPLIT: rc = launch_conv_split(a, st.ch.p0, st.ch.p1, B, s); break;
             case S_CONV_SPLIT1: rc = launch_conv_split1(a, st.ch.p0, B, s); break;

@@ -35,6 +35,7 @@ const Option kOptions[] = {
     {"range_guard", nullptr, &PlanOptions::range_guard, nullptr, true, true, false},
     {"fuse_front", nullptr, &PlanOptions::fuse_front, nullptr, true, true, false},   // (0: stem -> conv_split -> conv_dma stride 2, three kernels)
     {"fuse_pairs", nullptr, &PlanOptions::fuse_pairs, nullptr, true, true, false},
+    {"share_s", nullptr, &PlanOptions::share_s, nullptr, true, true, false},
     {"profile_tag_ops", nullptr, &PlanOptions::profile_tag_ops, nullptr, true, true, false},
     {"table_batch", nullptr, &PlanOptions::table_batch, nullptr, false, true, true},
     {"normalize_ranges", nullptr, &PlanOptions::normalize_ranges, nullptr, true, false, false},
@@ -298,6 +299,34 @@ void pack_pair(const BlobOp &P, const float *wP, const BlobOp &o, const float *w
     pack_conv_weights_pair_p(wp.data(), (int)P.cin, (int)P.cout, rs, a.at(c.pair_two_off), a.at(c.pair_nine_off));
 }
 
+// conv_s4.hip share / add: o is the consumer C of a pair, P its producer.  The share launch's matrix over S: P's rows (scaled by P's own
+// 2^k), zero rows up to share_row0, C's rows restricted to the columns of S (C's 2^k); the add launch's: C over [P's output, others..]
+void pack_share(const BlobOp &P, const float *wP, const BlobOp &o, const float *ws, Arena &a, ConvPlan &c) {
+    const int n = (int)o.n_src, row0 = share_row0((int)P.cout), rows = row0 + (int)o.cout, cS = (int)o.src[0].ch;
+    std::vector<float> wp, wa((size_t)rows * P.cin * 9, 0.f);
+    scale_weights(wP, (size_t)P.cout * P.cin * 9, wp);
+    std::copy(wp.begin(), wp.end(), wa.begin());
+    for (int co = 0; co < (int)o.cout; ++co)
+        for (int ci = 0; ci < (int)P.cin; ++ci)
+            for (int t = 0; t < 9; ++t) wa[((size_t)(row0 + co) * P.cin + ci) * 9 + t] = ws[((size_t)co * o.cin + cS + ci) * 9 + t];
+    const S4Range rs{(int)P.src[0].choff, (int)P.src[0].ch};
+    c.share_a_tiles = (rows + 15) / 16;
+    c.share_a_off = a.take(s4_packed_floats(&rs, 1, rows, 3, 0), 16);
+    pack_conv_weights_s4(wa.data(), (int)P.cin, rows, 3, &rs, 1, 0, a.at(c.share_a_off));
+    S4Range rg[kConvMaxSrc];
+    int cstart[kConvMaxSrc], c0 = 0;
+    for (int j = 0, k = 0; j < n; ++j) {
+        if (j != 1) {
+            rg[k] = S4Range{(int)o.src[j].choff, (int)o.src[j].ch};
+            cstart[k++] = c0;
+        }
+        c0 += (int)o.src[j].ch;
+    }
+    c.share_b_rounds = s4_rounds(rg, n - 1, 3, 0);
+    c.share_b_off = a.take(s4_packed_floats(rg, n - 1, (int)o.cout, 3, 0), 16);
+    pack_conv_weights_s4_ex(ws, (int)o.cin, (int)o.cout, 3, rg, cstart, n - 1, 0, a.at(c.share_b_off));
+}
+
 void pack_front(const BlobOp &o, const float *ws, Arena &a, ConvPlan &c) {   // 3x3 stride 2, one range
     const S4Range rg{(int)o.src[0].choff, (int)o.src[0].ch};
     c.front_off = a.take(s4_packed_floats(&rg, 1, (int)o.cout, 3, 0), 16);
@@ -355,6 +384,7 @@ int build_plan_weights(pf_plan &p, const float *wts, std::vector<float> &host) {
         if (o.stride == 1) pack_split(o, ws, src_ch, a, c);
         if (o.stride == 1 && o.kind == OP_CONV) pack_s4(o, ws, a, c);
         if (i > 0 && is_conv_pair(p.net, i - 1)) pack_pair(ops[i - 1], wts + ops[i - 1].w_off, o, ws, a, c);
+        if (i > 0 && p.opt.share_s && is_conv_pair(p.net, i - 1)) pack_share(ops[i - 1], wts + ops[i - 1].w_off, o, ws, a, c);
         if (o.k == 3 && o.stride == 2 && o.kind == OP_CONV && o.n_src == 1 && (o.src[0].choff & 3) == 0 && o.cout <= 32) pack_front(o, ws, a, c);
         if (o.stride == 1) pack_wave(o, w, src_ch, a, c);
         if (o.kind == OP_STEM) pack_stem(o, w, (int)p.net.hdr.n_cls, a, c);
@@ -428,6 +458,32 @@ extern "C" int pf_hardnet_plan_create(const void *blob, size_t bytes, int in_ch,
         return fail(PF_EHIP, "plan upload: %s", hipGetErrorString(e));
     }
     *out = p;
+    return PF_OK;
+}
+
+// Host only, no device involved (tests): the weight arena a plan created now from this blob would upload (every packing of every
+// convolution under the process-wide options), and per op of the table six numbers: offset (floats) and rounds of its packed-pair
+// packing, offset and cout tiles of the share launch's, offset and rounds of the add launch's (0 = the op has none)
+extern "C" int pf_debug_plan_arena(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                                   long long *table, int table_ops) {
+    if (!blob || !n_floats) return fail(PF_EINVAL, "pf_debug_plan_arena: null argument");
+    pf_plan p;
+    p.opt = g_plan_opt;
+    int rc = parse_net_table(blob, bytes, in_ch, n_cls, p.net);
+    const size_t n_w = rc ? 0 : (bytes - p.net.hdr.weights_off) / sizeof(float);
+    if (!rc) rc = check_plan_ops(p.net, n_w);
+    if (rc) return rc;
+    const float *w0 = reinterpret_cast<const float *>((const char *)blob + p.net.hdr.weights_off);
+    std::vector<float> wnorm(w0, w0 + n_w), host;
+    normalize_ranges(&p, wnorm);
+    if ((rc = build_plan_weights(p, wnorm.data(), host))) return rc;
+    *n_floats = host.size();
+    if (out && cap >= host.size()) memcpy(out, host.data(), host.size() * sizeof(float));
+    for (int i = 0; table && i < table_ops && i < (int)p.conv.size(); ++i) {
+        const ConvPlan &c = p.conv[i];
+        const long long row[6] = {(long long)c.s4_off, c.s4_rounds, (long long)c.share_a_off, c.share_a_tiles, (long long)c.share_b_off, c.share_b_rounds};
+        memcpy(table + 6 * i, row, sizeof(row));
+    }
     return PF_OK;
 }
 

@@ -52,10 +52,13 @@ __global__ __launch_bounds__(256) void stem_onehot_kernel(StemArgs a) {
             for (int t = 0; t < a.T; ++t) {
                 const size_t idx = ((size_t)b * a.T + t) * N + pix;
                 // label -> one-hot column (labels >= n_cls contribute nothing, bg_model.py:54-57)
-                int cls = a.seg_is_i64 ? (int)reinterpret_cast<const long long *>(a.seg)[idx]
-                                       : (int)reinterpret_cast<const uint8_t *>(a.seg)[idx];
-                if (a.hop & PF_HOP_TRAINID_LUT) cls = lut[cls & 255];
-                if (cls >= 0 && cls < a.n_cls) {
+                // (an int64 label is compared in 64 bits: 2^32 + 3 is no class; the LUT, which the reference applies to u8 files
+                //  only, reads its low byte)
+                long long lab = a.seg_is_i64 ? reinterpret_cast<const long long *>(a.seg)[idx]
+                                             : (long long)reinterpret_cast<const uint8_t *>(a.seg)[idx];
+                if (a.hop & PF_HOP_TRAINID_LUT) lab = lut[lab & 255];
+                if (lab >= 0 && lab < a.n_cls) {
+                    const int cls = (int)lab;
                     const f32x4v *row = reinterpret_cast<const f32x4v *>(wl + (tap * in_ch + t * a.n_cls + cls) * 16);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -100,111 +103,17 @@ __global__ __launch_bounds__(256) void stem_onehot_kernel(StemArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Stem, latency-organised (T compile-time): the generic kernel above walks its 9*T taps one dependent
-// load -> LUT -> weight-row chain at a time (54 serial HBM round trips per wave; profiles/r01_e: 193 us at B=4 for
-// 65 us of traffic).  Here every lane first issues ALL its 9*T label and depth loads (clamped addresses, no branches
-// in between, so they are in flight together), and only then consumes them; the depth-channel weights are uniform
-// per (tap, t) and come through the scalar cache (a.wdep, [tap][t][16]) instead of LDS, which halves the LDS reads.
-template <int T, bool SEG64>
-__global__ __launch_bounds__(256) void stem_onehot_batched_kernel(StemArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float wl[];   // [tap][ch][16]
-    __shared__ uint8_t lut[256];
-    const int in_ch = T * (a.n_cls + 1);
-    for (int e = threadIdx.x; e < 9 * in_ch * 16; e += 256) {
-        const int co = e & 15, ch = (e >> 4) % in_ch, tap = (e >> 4) / in_ch;
-        wl[e] = a.w[((size_t)co * in_ch + ch) * 9 + tap];
-    }
-    lut[threadIdx.x] = (a.hop & PF_HOP_TRAINID_LUT) ? a.lut[threadIdx.x] : (uint8_t)threadIdx.x;
-    __syncthreads();
-
-    const int ox = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int oy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int b = blockIdx.z;
-    if (ox >= a.Wout || oy >= a.Hout) return;
-    const size_t N = (size_t)a.H * a.W;
-    const bool hop_d = (a.hop & PF_HOP_DEPTH_U16) != 0;
-
-    // ---- phase 1: all loads
-    int lab[9 * T];
-    float dep[9 * T];
-    uint8_t msk[9 * T];
-    unsigned okbits = 0;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-        const int iy = oy * 2 - 1 + tap / 3, ix = ox * 2 - 1 + tap % 3;
-        const bool ok = iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-        okbits |= ok ? (1u << tap) : 0u;
-        const size_t pix = (size_t)(ok ? iy : 0) * a.W + (ok ? ix : 0);
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const size_t idx = ((size_t)b * T + t) * N + pix;
-            lab[tap * T + t] = SEG64 ? (int)reinterpret_cast<const long long *>(a.seg)[idx]
-                                     : (int)reinterpret_cast<const uint8_t *>(a.seg)[idx];
-            dep[tap * T + t] = a.depth[idx];
-            msk[tap * T + t] = hop_d ? (uint8_t)0 : a.mask[idx];
-        }
-    }
-
-    // ---- phase 2
-    float acc[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = a.bias[i];
-    const float mean_ = a.depth_mean, std_ = a.depth_std;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-        const bool ok = (okbits >> tap) & 1u;
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            int cls = lab[tap * T + t];
-            if (a.hop & PF_HOP_TRAINID_LUT) cls = lut[cls & 255];
-            if (ok && cls >= 0 && cls < a.n_cls) {     // labels >= n_cls contribute nothing (bg_model.py:54-57)
-                const f32x4v *row = reinterpret_cast<const f32x4v *>(wl + (tap * in_ch + t * a.n_cls + cls) * 16);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4v r = row[q];
-                    acc[q * 4 + 0] += r[0]; acc[q * 4 + 1] += r[1]; acc[q * 4 + 2] += r[2]; acc[q * 4 + 3] += r[3];
-                }
-            }
-            float d = dep[tap * T + t], m;
-            if (hop_d) {
-                const float q = rintf(fminf(fmaxf(d + 1.f, 0.f), 255.f) * 256.f);  // export :119-124
-                d = q / 256.f - 1.f;                                                // load bg_dataset.py:225
-                const bool mk = d > 0.f;
-                d = mk ? fminf(fmaxf(d, a.min_depth), a.max_depth) : -1.f;           // :227-228,:166-170
-                m = mk ? 1.f : 0.f;
-            } else {
-                m = msk[tap * T + t] ? 1.f : 0.f;
-            }
-            const float dn = ok ? ((d - mean_) / std_) * m : 0.f;                    // (bg_model.py:50-51,66-67)
-            const float *wd = a.wdep + (tap * T + t) * 16;                           // uniform: scalar loads
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] += wd[i] * dn;
-        }
-    }
-    const size_t op = (size_t)a.Hout * a.Wout;
-    float *o = a.dst + (size_t)b * 16 * op + (size_t)oy * a.Wout + ox;
-    float vmax = 0.f;   // the output is >= 0 after the ReLU: range guard of the operand split (conv_mfma.h)
-    bool nan = false;   // a NaN input propagates like in the reference's fp32 conv, but max() would drop it: flag it
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        o[i * op] = fmaxf(acc[i], 0.f);
-        vmax = fmaxf(vmax, acc[i]);
-        nan = nan || acc[i] != acc[i];
-    }
-    range_commit(a.status, a.range_slot, nan ? __builtin_inff() : vmax);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Stem, third form.  The batched kernel above was bound by the vector ALU (SQ counters, profiles/r02_a_pmc.json: 2270
-// instructions per output pixel, 300 M wave-instructions per 16 frames = 485 us of issue time in a 573 us kernel), and a
-// third of those instructions were not arithmetic: 64-bit address arithmetic for each of the 54 loads of a lane, a divergent
-// branch per (tap, frame) around the one-hot row, and every workgroup re-gathering its 20 KB of weights from the OIHW array
-// 4 bytes at a time.  Here
+// Stem, T = 3 compile-time.  The generic kernel above walks its 9*T taps one dependent load -> LUT -> weight-row chain at a
+// time (54 serial HBM round trips per wave; profiles/r01_e: 193 us at B=4 for 65 us of traffic), computes a 64-bit address
+// for each of the 54 loads of a lane, branches per (tap, frame) around the one-hot row, and every workgroup gathers its 20 KB
+// of weights from the OIHW array 4 bytes at a time.  Here
 //   * the one-hot rows arrive pre-packed [tap][t][n_cls + 1][16] (plan creation; the last row of each group is zero) and are
 //     copied to LDS with 16-B loads; a label outside 0..n_cls-1 (or a tap outside the image) selects the zero row: no branch;
-//   * loads use one uniform base per tensor + a 32-bit lane offset;
+//   * the depth-channel weights are uniform per (tap, t) and come through the scalar cache (a.wdep, [tap][t][16]);
+//   * loads use one uniform base per tensor + a 32-bit lane offset (T*H*W >= 2^32 goes to the generic kernel, which indexes
+//     with size_t);
 //   * accumulation is on register pairs (v_pk_add_f32 for the one-hot rows, v_pk_fma_f32 with scalar weight pairs for depth).
-// Same operations on the same values in the same order as the kernels above: outputs are bit-identical.
+// Same operations on the same values in the same order as the generic kernel: outputs are bit-identical.
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 constexpr int kStemRow = 16;   // floats per one-hot weight row in LDS (20 = conflict-free for any label mix; measured no faster: warped label maps are coherent)
 template <int T, bool SEG64, bool HOP_D, bool HOP_LUT>
@@ -244,7 +153,14 @@ __global__ __launch_bounds__(256) void stem_onehot_v3_kernel(StemArgs a) {
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             const unsigned idx = (unsigned)t * N + pix;
-            p.lab[t] = SEG64 ? (int)seg64[idx] : (int)seg8[idx];
+            if (SEG64) {
+                // compared in 64 bits before narrowing (2^32 + 3 is no class): n_cls stands for every label outside
+                // 0..n_cls-1; the LUT, which the reference applies to u8 files only, reads the low byte
+                const long long v = seg64[idx];
+                p.lab[t] = HOP_LUT ? (int)(v & 255) : ((unsigned long long)v < (unsigned long long)a.n_cls ? (int)v : a.n_cls);
+            } else {
+                p.lab[t] = (int)seg8[idx];
+            }
             p.dep[t] = depth[idx];
             p.msk[t] = hop_d ? (uint8_t)0 : mask[idx];
         }
@@ -864,42 +780,42 @@ int launch_stem(const StemArgs &a, hipStream_t s) {
     if (a.dst_fmt && !stem_writes_s4(a)) return fail(PF_EUNSUPPORTED, "stem: these arguments select a kernel that writes fp32 only");
     const size_t lds = (size_t)a.T * (a.n_cls + 1) * 9 * 16 * sizeof(float);
     const double ipx = (double)a.B * a.T * a.H * a.W, opx = (double)a.B * a.Hout * a.Wout;
-    const bool batched = a.T == 3 && a.wdep;
-    const bool v3 = batched && a.woh && (unsigned long long)a.T * a.H * a.W < (1ull << 32);
+    // T = 3 with the plan's re-packed weights and 32-bit lane offsets: v3, or v4 (2 x 2 outputs per lane) for u8 labels on an
+    // image of whole 4 x 4 blocks; everything else (T != 3, T*H*W >= 2^32) runs the generic kernel, which indexes with size_t
+    const bool v3 = a.T == 3 && a.wdep && a.woh && (unsigned long long)a.T * a.H * a.W < (1ull << 32);
     const bool v4 = v3 && !a.seg_is_i64 && (a.W & 3) == 0 && (a.H & 3) == 0 && a.Wout * 2 == a.W && a.Hout * 2 == a.H;
-    const char *label = !batched ? "pf::stem_onehot_kernel(pf::StemArgs)"
-                        : v4 ? "pf::stem_onehot_v4_kernel(pf::StemArgs, float)"
-                        : v3 ? "pf::stem_onehot_v3_kernel(pf::StemArgs)"
-                        : a.seg_is_i64 ? "void pf::stem_onehot_batched_kernel<3, true>(pf::StemArgs)"
-                                       : "void pf::stem_onehot_batched_kernel<3, false>(pf::StemArgs)";
-    ProfScope ps(s, label, 2.0 * opx * 16 * a.T * (a.n_cls + 1) * 9,
-                 ipx * ((a.seg_is_i64 ? 8 : 1) + 4 + ((a.hop & PF_HOP_DEPTH_U16) ? 0 : 1)) + opx * 16 * 4);
+    const bool hd = (a.hop & PF_HOP_DEPTH_U16) != 0, hl = (a.hop & PF_HOP_TRAINID_LUT) != 0;
+    // the reciprocal form of the division is exact only on the value set of the hop (proven per parameter set)
+    const bool fast = v4 && hd && stem_fast_div_exact(a.depth_mean, a.depth_std, a.min_depth, a.max_depth);
+    const int variant = v4 ? (hd ? 4 : 0) | (hl ? 2 : 0) | (fast ? 1 : 0) : (a.seg_is_i64 ? 4 : 0) | (hd ? 2 : 0) | (hl ? 1 : 0);
+    const double flops = 2.0 * opx * 16 * a.T * (a.n_cls + 1) * 9;
+    const double bytes = ipx * ((a.seg_is_i64 ? 8 : 1) + 4 + (hd ? 0 : 1)) + opx * 16 * 4;
     const dim3 grid((a.Wout + 63) / 64, (a.Hout + 3) / 4, a.B);
+    // the profile label of a launch is the instantiation's name, built from the template arguments of the launch itself
     if (v4) {
         const size_t lds4 = (size_t)9 * a.T * (a.n_cls + 1) * 16 * sizeof(float);
-        const bool hd = (a.hop & PF_HOP_DEPTH_U16) != 0, hl = (a.hop & PF_HOP_TRAINID_LUT) != 0;
-        // the reciprocal form of the division is exact only on the value set of the hop (proven per parameter set)
-        const bool fast = hd && stem_fast_div_exact(a.depth_mean, a.depth_std, a.min_depth, a.max_depth);
         const float inv_std = 1.0f / a.depth_std;
         const dim3 grid4((a.Wout + 127) / 128, (a.Hout + 7) / 8, a.B);
-        const int variant = (hd ? 4 : 0) | (hl ? 2 : 0) | (fast ? 1 : 0);
 #define PF_STEM4(V, HD, HL, FD) \
-        if (variant == V) hipLaunchKernelGGL((stem_onehot_v4_kernel<3, HD, HL, FD>), grid4, dim3(256), lds4, s, a, inv_std);
+        if (variant == V) { \
+            ProfScope ps(s, "void pf::stem_onehot_v4_kernel<3, " #HD ", " #HL ", " #FD ">(pf::StemArgs, float)", flops, bytes); \
+            hipLaunchKernelGGL((stem_onehot_v4_kernel<3, HD, HL, FD>), grid4, dim3(256), lds4, s, a, inv_std); \
+        }
         PF_STEM4(0, false, false, false) PF_STEM4(2, false, true, false)
         PF_STEM4(4, true, false, false) PF_STEM4(5, true, false, true) PF_STEM4(6, true, true, false) PF_STEM4(7, true, true, true)
 #undef PF_STEM4
     } else if (v3) {
         const size_t lds3 = (size_t)9 * a.T * (a.n_cls + 1) * kStemRow * sizeof(float);
-        const int variant = (a.seg_is_i64 ? 4 : 0) | ((a.hop & PF_HOP_DEPTH_U16) ? 2 : 0) | ((a.hop & PF_HOP_TRAINID_LUT) ? 1 : 0);
 #define PF_STEM3(V, S64, HD, HL) \
-        if (variant == V) hipLaunchKernelGGL((stem_onehot_v3_kernel<3, S64, HD, HL>), grid, dim3(256), lds3, s, a);
+        if (variant == V) { \
+            ProfScope ps(s, "void pf::stem_onehot_v3_kernel<3, " #S64 ", " #HD ", " #HL ">(pf::StemArgs)", flops, bytes); \
+            hipLaunchKernelGGL((stem_onehot_v3_kernel<3, S64, HD, HL>), grid, dim3(256), lds3, s, a); \
+        }
         PF_STEM3(0, false, false, false) PF_STEM3(1, false, false, true) PF_STEM3(2, false, true, false) PF_STEM3(3, false, true, true)
         PF_STEM3(4, true, false, false) PF_STEM3(5, true, false, true) PF_STEM3(6, true, true, false) PF_STEM3(7, true, true, true)
 #undef PF_STEM3
-    } else if (batched) {
-        if (a.seg_is_i64) hipLaunchKernelGGL((stem_onehot_batched_kernel<3, true>), grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((stem_onehot_batched_kernel<3, false>), grid, dim3(256), lds, s, a);
     } else {
+        ProfScope ps(s, "pf::stem_onehot_kernel(pf::StemArgs)", flops, bytes);
         hipLaunchKernelGGL(stem_onehot_kernel, grid, dim3(256), lds, s, a);
     }
     PF_LAUNCH_CHECK("stem_onehot_kernel");

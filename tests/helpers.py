@@ -31,6 +31,16 @@ class MiniSpec:
         self.ops.append(arch.Op(arch.OP_CONV, name, srcs, dst, dst_choff, cin, cout, k, stride, relu, bn=bn))
         return dst
 
+    def stem(self, name, T, n_cls):
+        """the fused one-hot stem (pf_bg_forward): 3x3 stride 2 + ReLU over the T*(n_cls+1) input channels the kernels never build,
+        into a 16-channel tensor of its own"""
+        cin = T * (n_cls + 1)
+        assert cin == self.in_ch and not self.ops
+        self.n_cls = n_cls
+        dst = self.tensor(name, 16)
+        self.ops.append(arch.Op(arch.OP_STEM, name, [arch.Src(0, 0, cin)], dst, 0, cin, 16, 3, 2, True, bn=False))
+        return dst
+
     def head(self, logits_t):
         ch = self.tensors[logits_t].channels
         self.n_cls = ch
@@ -98,8 +108,51 @@ class MiniNet:
         torch.cuda.synchronize()
         return rc, seg, logits, orig
 
+    def run_bg(self, seg, depth, mask, mean, std, hop_flags, min_depth, max_depth, out_h, out_w):
+        """pf_bg_forward on seg [B, T, H, W] (uint8 / int64), depth (fp32) and mask (uint8; None under PF_HOP_DEPTH_U16) -> rc.  The
+        outputs are pre-filled as in run_head and kept as self.out = (seg, out_logits, out_orig_logits)"""
+        L, seg, b, h, w = self._workspace(seg)
+        t, c = seg.shape[1], self.spec.n_cls
+        assert seg.dtype in (torch.uint8, torch.int64) and depth.dtype == torch.float32 and (mask is None or mask.dtype == torch.uint8)
+        depth = depth.contiguous()
+        mask = None if mask is None else mask.contiguous()
+        oh, ow = (h + 1) // 2, (w + 1) // 2
+        for op in self.spec.ops[1:]:
+            if op.kind == arch.OP_CONV and op.stride == 2:
+                oh, ow = (oh + 1) // 2, (ow + 1) // 2
+        out_seg = torch.full((b, out_h, out_w), 250, dtype=torch.uint8, device=seg.device)
+        logits = torch.full((b, c, out_h, out_w), float('nan'), device=seg.device)
+        orig = torch.full((b, c, oh, ow), float('nan'), device=seg.device)
+        rc = L.pf_bg_forward(self.plan, seg.data_ptr(), int(seg.dtype == torch.int64), depth.data_ptr(),
+                             None if mask is None else mask.data_ptr(), float(mean), float(std), int(hop_flags), float(min_depth),
+                             float(max_depth), b, t, h, w, out_h, out_w, out_seg.data_ptr(), 0, logits.data_ptr(), orig.data_ptr(),
+                             self.ws.data_ptr(), self.ws.numel(), _lib.stream_ptr())
+        torch.cuda.synchronize()
+        self.out = (out_seg, logits, orig)
+        return rc
+
     def tensor(self, name):
         return view_tensor(self.plan, self.ws, name, *self.bhw)
+
+    def stored_tensor(self, name):
+        """the tensor as the last forward stored it, if that was fp32 NCHW: in the plan's own units (times its per-channel powers
+        of two), where tensor() hands out the caller's"""
+        L = _lib.load()
+        b, h, w = self.bhw
+        off, c, th, tw = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _lib.check(L.pf_hardnet_tensor_view(self.plan, name.encode(), b, h, w, ctypes.byref(off), ctypes.byref(c), ctypes.byref(th),
+                                            ctypes.byref(tw)), 'pf_hardnet_tensor_view')
+        n = b * c.value * th.value * tw.value
+        stored = self.ws[off.value:off.value + 4 * n].view(torch.float32).view(b, c.value, th.value, tw.value).clone()
+        # the guard: what pf_hardnet_tensor_read hands out is this times one power of two per channel - true of fp32 NCHW storage,
+        # not of the packed-pair bytes of the same region read as floats
+        x = self.tensor(name)
+        assert torch.equal(x == 0, stored == 0), 'tensor %s is not stored as fp32 NCHW' % name
+        for ch in range(c.value):
+            nz = stored[:, ch] != 0
+            r = (x[:, ch][nz] / stored[:, ch][nz]).unique()
+            assert len(r) <= 1 and bool((torch.frexp(r)[0] == 0.5).all()), 'tensor %s is not stored as fp32 NCHW' % name
+        return stored
 
     def set_option(self, name, value):
         _lib.check(_lib.load().pf_hardnet_plan_set_option(self.plan, name.encode(), int(value)), 'pf_hardnet_plan_set_option')
@@ -421,3 +474,9 @@ def head_probe_record(case_id, entry):
     """head_probe_dist.json next to the other measured reports (probe_record above): per case of tests/test_gpu_head.py the worst
     err / (u*M), the near-tie count and the kernel that ran.  The run on MI355X is kept as profiles/head_probe_dist.json"""
     _merge_report('head_probe_dist.json', case_id, entry)
+
+
+def stem_probe_record(case_id, entry):
+    """stem_probe_dist.json next to the other measured reports: per case of tests/test_gpu_stem.py the worst err / bar of every
+    run (hop flags, parameter set) and the kernels that ran"""
+    _merge_report('stem_probe_dist.json', case_id, entry)

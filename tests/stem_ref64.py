@@ -1,0 +1,223 @@
+"""The float64 checker of the fused one-hot stem (csrc/net_kernels.hip: launch_stem), plain torch / NumPy on the CPU, and the
+cases tests/test_gpu_stem.py runs (tests/test_stem_host.py pins the checker itself without a GPU).
+
+stem_inputs() forms the [B, T*(n_cls+1), H, W] fp32 tensor the reference network feeds its first convolution (bg_model.py:53-69
+behind the on-disk hop of oracle/hop.py): every step of it is exact in fp32 or one IEEE operation, so it is what the kernels are
+specified to compute bit for bit.  stem64() is the convolution + ReLU in float64.
+
+The bar.  A kernel starts an accumulator at the bias and, for the 9 taps and T frames in the order ky, kx, t, adds one row of
+one-hot weights (a rounded addition) and then one depth weight times the normalised depth (a fused multiply-add: one rounding):
+18*T rounded operations, 18*T + 1 terms.  The standard bound of a sequential fp32 sum of n terms is (n - 1) u sum|term_i| (1 +
+O(n u)) with u = 2^-24; stem_bar() uses n u with 1 % on top, 1.01 * (18*T + 1) * 2^-24 * conv2d(|x|, |w|, |b|) per element.  The
+ReLU is 1-Lipschitz, so the bar holds behind it.  Nothing in the bar is measured.
+"""
+import functools
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from oracle import hop as ohop
+
+PF_HOP_TRAINID_LUT, PF_HOP_DEPTH_U16 = 1, 2
+HOPS = (0, PF_HOP_DEPTH_U16, PF_HOP_TRAINID_LUT, PF_HOP_TRAINID_LUT | PF_HOP_DEPTH_U16)
+# (mean, std, min_depth, max_depth): the project's, and a second set (the reciprocal form of the division is chosen per set)
+PARAM_SETS = ((20.0, 15.0, 0.1, 200.0), (11.3, 3.7, 0.5, 80.0))
+# a set whose std is not finite: launch_stem's proof that the reciprocal form of the division is exact refuses it, so the v4 kernels
+# with the IEEE division run under the depth hop; every normalised depth is +-0 (run where a test asks for it, not in StemCase.runs)
+ALL_SETS = PARAM_SETS + ((20.0, float('inf'), 0.1, 200.0),)
+INF_STD_SET = 2
+U = 2.0 ** -24
+
+
+def _f32(v):
+    return torch.tensor(v, dtype=torch.float32)
+
+
+def hop_depth(depth, min_depth, max_depth):
+    """export :119-124 and bg_dataset.py:224-230,166-170 on fp32 values -> (depth, mask); every step is exact in fp32"""
+    q = torch.round((depth + _f32(1.0)).clamp(0.0, 255.0) * _f32(256.0))     # (round half to even, like rintf)
+    d = q / _f32(256.0) - _f32(1.0)
+    mask = d > 0
+    d = torch.where(mask, d.clamp(float(_f32(min_depth)), float(_f32(max_depth))), _f32(-1.0))
+    return d, mask
+
+
+def stem_inputs(seg, depth, mask, T, n_cls, mean, std, hop_flags, min_depth, max_depth):
+    """seg [B, T, H, W] (uint8 / int64), depth fp32, mask (bool / uint8; ignored under PF_HOP_DEPTH_U16) -> x [B, T*(n_cls+1), H, W]
+    fp32: T*n_cls one-hot channels (frame-major), then T normalised depth channels"""
+    b, t, h, w = seg.shape
+    assert t == T and depth.dtype == torch.float32
+    seg = seg.long()
+    if hop_flags & PF_HOP_TRAINID_LUT:
+        assert int(seg.min()) >= 0 and int(seg.max()) <= 255            # (the reference applies the table to u8 files only)
+        seg = torch.from_numpy(ohop.id2trainid_lut().astype(np.int64))[seg]
+    ok = (seg >= 0) & (seg < n_cls)                                     # a label outside 0..n_cls-1: the zero vector
+    oh = F.one_hot(torch.where(ok, seg, torch.zeros_like(seg)), n_cls) * ok.unsqueeze(-1)
+    x = oh.permute(0, 1, 4, 2, 3).float().reshape(b, T * n_cls, h, w)
+    if hop_flags & PF_HOP_DEPTH_U16:
+        depth, mask = hop_depth(depth, min_depth, max_depth)
+    dn = ((depth - _f32(mean)) / _f32(std)) * mask.to(torch.float32)    # fp32, IEEE division
+    assert dn.dtype == torch.float32
+    return torch.cat([x, dn], 1)
+
+
+def stem64(x, w, b):
+    return F.relu(F.conv2d(x.double(), w.double(), b.double(), stride=2, padding=1))
+
+
+def stem_bar(x, w, b, T):
+    return 1.01 * (18 * T + 1) * U * F.conv2d(x.double().abs(), w.double().abs(), b.double().abs(), stride=2, padding=1)
+
+
+def emulate_fp32(x, w, b, T, n_cls):
+    """the kernels' arithmetic in NumPy fp32: accumulator = bias; ky, kx, t ascending: + the one-hot row of the label (one rounded
+    addition; nothing for the zero vector), then the depth weight times the normalised depth as a multiply-add in float64 rounded
+    to fp32.  x: stem_inputs() -> [B, 16, Hout, Wout] fp32 after the ReLU"""
+    x, w, b = x.numpy(), w.numpy(), b.numpy()
+    B, C, H, W = x.shape
+    ho, wo = (H + 1) // 2, (W + 1) // 2
+    xp = np.zeros((B, C, 2 * ho + 1, 2 * wo + 1), np.float32)
+    xp[:, :, 1:H + 1, 1:W + 1] = x
+    acc = np.broadcast_to(b.astype(np.float32)[None, :, None, None], (B, 16, ho, wo)).copy()
+    for ky in range(3):
+        for kx in range(3):
+            win = xp[:, :, ky:ky + 2 * ho:2, kx:kx + 2 * wo:2]                  # [B, C, ho, wo]
+            for t in range(T):
+                oh = win[:, t * n_cls:(t + 1) * n_cls]                           # at most one 1 per pixel
+                row = np.einsum('bchw,oc->bohw', oh, w[:, t * n_cls:(t + 1) * n_cls, ky, kx]).astype(np.float32)   # exact: one term
+                acc = (acc + row).astype(np.float32)
+                dn = win[:, T * n_cls + t][:, None].astype(np.float64)
+                wd = w[:, T * n_cls + t, ky, kx].astype(np.float64)[None, :, None, None]
+                acc = (wd * dn + acc.astype(np.float64)).astype(np.float32)
+    return torch.from_numpy(np.maximum(acc, np.float32(0)))
+
+
+# ------------------------------------------------------------------------------------------------ the cases
+class StemCase:
+    """One plan (weights, bias) and one set of label / depth / mask planes; a case is run with every hop-flag combination and both
+    parameter sets (``runs``).  ``family``: the kernel launch_stem selects: 'v4' (u8 labels, T = 3, whole 4 x 4 blocks), 'v3'
+    (T = 3 otherwise), 'generic' (T != 3)"""
+
+    def __init__(self, family, h, w, b=1, T=3, n_cls=11, i64=False, note=''):
+        self.family, self.h, self.w, self.b, self.T, self.n_cls, self.i64, self.note = family, h, w, b, T, n_cls, i64, note
+        self.name = '%s %s T%d C%d %dx%d B%d' % (family, 'i64' if i64 else 'u8', T, n_cls, h, w, b)
+        v4 = T == 3 and not i64 and h % 4 == 0 and w % 4 == 0
+        assert family == ('generic' if T != 3 else 'v4' if v4 else 'v3'), self.name
+        self.seed = 5000 + sum(ord(c) * (i + 1) for i, c in enumerate(self.name)) % 9973
+
+    @property
+    def cin(self):
+        return self.T * (self.n_cls + 1)
+
+    @property
+    def runs(self):
+        return [(hop, ps) for hop in HOPS for ps in range(len(PARAM_SETS))]
+
+    def kernel(self, hop):
+        """the profile label launch_stem gives the launch, without 'void pf::' and the argument list; for v4 under the depth hop
+        either division variant (the last template argument) may serve: a tuple of the two"""
+        tf = lambda v: 'true' if v else 'false'
+        hd, hl = bool(hop & PF_HOP_DEPTH_U16), bool(hop & PF_HOP_TRAINID_LUT)
+        if self.family == 'generic':
+            return ('stem_onehot_kernel',)
+        if self.family == 'v3':
+            return ('stem_onehot_v3_kernel<3, %s, %s, %s>' % (tf(self.i64), tf(hd), tf(hl)),)
+        return tuple('stem_onehot_v4_kernel<3, %s, %s, %s>' % (tf(hd), tf(hl), tf(fd)) for fd in ((False, True) if hd else (False,)))
+
+
+def depth_edges(min_depth, max_depth):
+    """the values at which the hop chain changes behaviour"""
+    return [-1.0, -1.0 + 2.0 ** -9,                   # code 0; the tie at code 0.5 (-> 0)
+            300.5 / 256 - 1, 301.5 / 256 - 1,         # ties at an even and an odd code (-> 300, 302)
+            254.0, 254.0001, 1e9,                     # code 65280 = the clamp at 255
+            min_depth / 2, max_depth + 1,             # the min_depth / max_depth clamps
+            0.0, -0.0,                                # result 0: clears the mask
+            -5.0, 255.5 / 256 - 1, 256.5 / 256 - 1]   # d + 1 < 0; the ties around result 0 (-> code 256: masked)
+
+
+BIG_LABELS = (256 + 3, 2 ** 32 + 3, 2 ** 40)          # int64 labels whose low 8 / 32 bits are a class
+
+
+@functools.lru_cache(maxsize=None)
+def _planes(case):
+    """(seg for runs without the LUT, seg for runs with it, raw depth, mask of the runs without the depth hop): CPU tensors, a
+    function of the case alone, never modified.  Labels: uniform over 0..n_cls-1, about 10 % from {n_cls, 254, 255}; runs with the
+    LUT: half of the pixels carry the Cityscapes id of a class instead (ids 0..255 only); int64 runs without it: a few BIG_LABELS.
+    Depth: uniform in [-20, 280] with the hop's edges (both parameter sets') at random places"""
+    g = torch.Generator().manual_seed(case.seed)
+    shape = (case.b, case.T, case.h, case.w)
+    n = case.b * case.T * case.h * case.w
+    seg = torch.randint(0, case.n_cls, shape, generator=g)
+    odd = torch.tensor([case.n_cls, 254, 255])[torch.randint(0, 3, shape, generator=g)]
+    seg = torch.where(torch.rand(shape, generator=g) < 0.1, odd, seg)
+    from panoptic_forecasting_amd import synth
+    ids = torch.from_numpy(synth.TRAINID2ID.astype(np.int64))[seg.clamp(max=18)]
+    seg_lut = torch.where(torch.rand(shape, generator=g) < 0.5, ids, seg)
+    seg_raw = seg.clone()
+    if case.i64:
+        k = min(n // 2, max(3, n // 30))
+        at = torch.randperm(n, generator=g)[:k]
+        seg_raw.view(-1)[at] = torch.tensor(BIG_LABELS)[torch.arange(k) % 3]
+    depth = torch.rand(shape, generator=g) * 300 - 20
+    edges = torch.tensor([v for ps in PARAM_SETS for v in depth_edges(ps[2], ps[3])], dtype=torch.float32)
+    k = min(n // 2, max(len(edges), n // 8))
+    at = torch.randperm(n, generator=g)[:k]
+    depth.view(-1)[at] = edges[torch.arange(k) % len(edges)]
+    mask = (torch.rand(shape, generator=g) < 0.7) & (depth < 1e6)     # (1e9 unmasked and unclamped would only test the range guard)
+    dt = torch.int64 if case.i64 else torch.uint8
+    return seg_raw.to(dt), seg_lut.to(dt), depth, mask.to(torch.uint8)
+
+
+def planes(case, hop):
+    """(seg, depth, mask) of one run; mask is None under PF_HOP_DEPTH_U16"""
+    seg_raw, seg_lut, depth, mask = _planes(case)
+    return (seg_lut if hop & PF_HOP_TRAINID_LUT else seg_raw), depth, (None if hop & PF_HOP_DEPTH_U16 else mask)
+
+
+def inputs(case, hop, ps):
+    seg, depth, mask = planes(case, hop)
+    mean, std, dmin, dmax = ALL_SETS[ps]
+    return stem_inputs(seg, depth, mask, case.T, case.n_cls, mean, std, hop, dmin, dmax)
+
+
+@functools.lru_cache(maxsize=None)
+def params(case):
+    """(w [16, cin, 3, 3], b [16]): weights 3 * randn / sqrt(9 * cin); the bias of a channel puts at least 85 % of its float64
+    pre-activations above zero in EVERY run of the case (85 % quantile of the most negative run), so that the ReLU hides at most
+    a fifth of the outputs of any run (positive_share(), asserted on the host)"""
+    g = torch.Generator().manual_seed(case.seed + 1)
+    w = 3 * torch.randn(16, case.cin, 3, 3, generator=g) / (9 * case.cin) ** 0.5
+    lo = []
+    for hop, ps in case.runs:
+        pre = F.conv2d(inputs(case, hop, ps).double(), w.double(), None, stride=2, padding=1)
+        lo.append(torch.quantile(pre.transpose(0, 1).reshape(16, -1), 0.15, dim=1, interpolation='lower'))
+    b = (0.05 - torch.stack(lo).min(0).values).float()
+    return w, b
+
+
+@functools.lru_cache(maxsize=None)
+def reference(case, hop, ps):
+    """(x, float64 output, bar) of one run - computed once per process, never modified"""
+    w, b = params(case)
+    x = inputs(case, hop, ps)
+    return x, stem64(x, w, b), stem_bar(x, w, b, case.T)
+
+
+def positive_share(case, hop, ps):
+    w, b = params(case)
+    pre = F.conv2d(inputs(case, hop, ps).double(), w.double(), b.double(), stride=2, padding=1)
+    return float((pre > 0).double().mean())
+
+
+V4_SIZES = ((4, 4, 1, 'one lane, all four borders'), (16, 256, 2, 'exactly one tile'), (20, 264, 1, 'partial tile in both directions'),
+            (36, 520, 3, 'several tiles'))
+V4_CASES = [StemCase('v4', h, w, b, n_cls=c, note=note) for h, w, b, note in V4_SIZES for c in (11, 19, 3)]
+V3_I64_CASES = [StemCase('v3', h, w, b, i64=True, note=note) for h, w, b, note in (
+    (1, 1, 2, 'smallest image'), (3, 4, 1, ''), (7, 9, 2, 'odd in both directions: bottom and right padding'),
+    (5, 130, 1, 'Wout = 65: second, partial strip'), (9, 128, 1, 'odd height'), (20, 264, 1, 'the i64 twin of a v4 case'))]
+V3_U8_CASES = [StemCase('v3', h, w, b, note=note) for h, w, b, note in (
+    (10, 6, 1, 'H % 4 == 2'), (8, 10, 2, 'W % 4 == 2'), (7, 9, 1, 'odd in both directions'))]
+GENERIC_CASES = [StemCase('generic', h, w, 1 + (h == 7), T=T, n_cls=c, i64=i64)
+                 for T, c in ((1, 19), (2, 3), (4, 11), (5, 19)) for h, w in ((7, 9), (5, 130), (20, 264)) for i64 in (False, True)]
+CASES = V4_CASES + V3_I64_CASES + V3_U8_CASES + GENERIC_CASES

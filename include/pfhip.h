@@ -278,6 +278,29 @@ int pf_odom_pack(const float *raw, float *packed, int flags, void *stream);
 int pf_odom_forward(const float *packed, int flags, int B, int T_in, int T_out, const float *inps, float *out,
                     float *out_norm, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * odometry forecaster, training - OdomModel.loss (odom_model.py:104-115) differentiates the forward above; the loss
+ * arithmetic on [B,T_out,2] stays with the caller.  csrc/odom_train.hip.
+ *   pf_odom_train_workspace: bytes of the buffer both calls below share (what the forward keeps per step, sequence and
+ *              hidden unit - h, r, z, n, W_hn h + b_hn - plus the weight-gradient partials); grows with B and with
+ *              T_in - 1 + T_out.  0 for B = 0.
+ *   pf_odom_train_forward: pf_odom_forward's out / out_norm bit for bit, and the saved state in ws.
+ *   pf_odom_backward: grad_out, grad_out_norm [B,T_out,2] f32 = the gradients of a scalar with respect to out / out_norm
+ *              (either may be null = zero); ws = the workspace the matching pf_odom_train_forward filled (the call
+ *              consumes it: one backward per forward).  grad_raw [50 950] f32 in the raw layout of pf_odom_weights_size
+ *              is overwritten (never accumulated); the odom_mean / odom_std slots are written as zero.  No gradient
+ *              is produced for inps.
+ *   Three kernel launches (reverse sweep, weight gradients per range of (step, sequence) rows, fixed-order sum of the
+ *   ranges), no atomics: two runs give the same bits.  Dimensions, null buffers and ws_bytes are checked before any
+ *   device work as in pf_odom_forward.  B = 0: the forward enqueues nothing, the backward only the zero fill of grad_raw.
+ */
+int pf_odom_train_workspace(int B, int T_in, int T_out, int flags, size_t *bytes);
+int pf_odom_train_forward(const float *packed, int flags, int B, int T_in, int T_out, const float *inps, float *out,
+                          float *out_norm, void *ws, size_t ws_bytes, void *stream);
+int pf_odom_backward(const float *packed, int flags, int B, int T_in, int T_out, const float *inps, const float *out_norm,
+                     const float *grad_out, const float *grad_out_norm, void *ws, size_t ws_bytes, float *grad_raw,
+                     void *stream);
+
 /* Process-wide execution options (not thread-safe; set before launching work):
  *   "fuse_pool"     (default 1) a 1x1 conv followed by AvgPool2d(2,2) (hardnet.py:296) pools in the conv epilogue;
  *   "fuse_upsample" (default 1) TransitionUp + 1x1 conv over cat([up(x), skip]) (hardnet.py:248-258,365-368) is

@@ -14,31 +14,11 @@
 // the 8 wave partials in LDS.  Every step of a sequence sees the same instructions in the same order whatever M and
 // wherever the sequence sits in its tile: MFMA rows never mix, so a sequence's outputs do not depend on the batch.
 // Kernel nodes only (no memset / memcpy), no atomics: pf_odom_forward can be captured into a graph.
-#include "pf_common.h"
+#include "odom_net.h"
 #include "pf_prof.h"
 
 namespace pf {
 namespace odom {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int H = 128;       // rnn_hidden
-constexpr int G3 = 3 * H;    // gate rows r, z, n
-constexpr int WAVES = 8;     // 8 x 16 units
-constexpr int THREADS = WAVES * 64;
-constexpr int KS = H / 4;    // k-steps of the 16x16x4 MFMA
-constexpr int HP = H + 4;    // LDS row stride of h (floats)
-constexpr int T_MAX = 64;    // T_in and T_out limits
-constexpr int M_MAX = 3;     // 16-row sub-tiles per workgroup (M = 4 would spill: 256 VGPRs + scratch)
-
-// the 8 state_dict tensors in the reference's order (= the raw buffer handed to pf_odom_pack)
-// odom_mean [1,2], odom_std [1,2], rnn.weight_ih_l0 [384,2], rnn.weight_hh_l0 [384,128], rnn.bias_ih_l0, rnn.bias_hh_l0 [384],
-// out.0.weight [2,128], out.0.bias [2]: 50 950 floats
-constexpr int O_MEAN = 0, O_STD = 2, O_WIH = 4, O_WHH = O_WIH + G3 * 2, O_BIH = O_WHH + G3 * H, O_BHH = O_BIH + G3,
-              O_OUTW = O_BHH + G3, O_OUTB = O_OUTW + 2 * H, RAW_TOTAL = O_OUTB + 2;
-constexpr int PACKED_WHH = (RAW_TOTAL + 63) / 64 * 64;          // the re-tiled W_hh follows the raw copy
-constexpr int PACKED_TOTAL = PACKED_WHH + WAVES * KS * 3 * 64;
-static_assert(RAW_TOTAL == 50950, "odom state_dict size");
 
 // packed[((w*KS + ks)*3 + g)*64 + lane] = B operand of k-step ks, gate g, wave w:  W_hh[g*128 + w*16 + (lane&15)][k] with
 // k = (ks>>2)*16 + (lane>>4)*4 + (ks&3), so that one ds_read_b128 of h[row][j*16 + (lane>>4)*4 ..] feeds k-steps 4j..4j+3
@@ -51,30 +31,10 @@ __global__ __launch_bounds__(256) void pack_whh_kernel(const float *__restrict__
     out[i] = whh[row * H + k];
 }
 
-// one DPP butterfly over the 16 lanes of a row: every lane ends with the same sum (each stage adds a commuted pair)
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-    v = dpp_add<0xB1>(v);     // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);     // quad_perm [2,3,0,1]
-    v = dpp_add<0x141>(v);    // row_half_mirror: quad 0 <-> quad 1
-    v = dpp_add<0x140>(v);    // row_mirror: lanes 0-7 <-> 8-15
-    return v;
-}
-
 __device__ __forceinline__ float sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
-struct Args {
-    const float *raw;          // raw state_dict copy inside the packed buffer
-    const float *whh;          // packed W_hh
-    const float *inps;         // [B][T_in][2]
-    float *out, *out_norm;     // [B][T_out][2]
-    int B, T_in, T_out, offset;
-};
-
-template <int M>
+// SAVE (training, odom_train.hip): the same instructions in the same order plus the stores of what the backward reads
+template <int M, bool SAVE>
 __global__ __launch_bounds__(THREADS) void odom_forward_kernel(Args a) {
 #pragma clang fp contract(off)
     constexpr int R = 16 * M;
@@ -161,6 +121,11 @@ __global__ __launch_bounds__(THREADS) void odom_forward_kernel(Args a) {
                 const float hn = (1.f - zg) * ng + zg * hold[mt][r];
                 hold[mt][r] = hn;
                 hnext[row * HP + unit] = hn;
+                if (SAVE && b0 + row < a.B) {
+                    const size_t at = ((size_t)s * a.B + (size_t)(b0 + row)) * H + unit;
+                    a.sv.h[at] = hn, a.sv.r[at] = rg, a.sv.z[at] = zg, a.sv.n[at] = ng, a.sv.q[at] = acc[mt][2][r];
+                    if (wave == 0 && col < 2) a.sv.x[((size_t)s * a.B + (size_t)(b0 + row)) * 2 + col] = col ? x1 : x0;
+                }
                 y0[mt][r] = wo0 * hn;
                 y1[mt][r] = wo1 * hn;
             }
@@ -201,7 +166,7 @@ __global__ __launch_bounds__(THREADS) void odom_forward_kernel(Args a) {
     }
 }
 
-static int check_dims(int B, int T_in, int T_out, int flags) {
+int check_dims(int B, int T_in, int T_out, int flags) {
     if (flags & ~1) return fail(PF_EUNSUPPORTED, "pf_odom: unsupported flags 0x%x (bit 0 = predict_type offset)", flags);
     if (B < 0 || T_in < 2 || T_in > T_MAX || T_out < 1 || T_out > T_MAX)
         return fail(PF_EINVAL, "pf_odom: bad dims B=%d T_in=%d T_out=%d (B >= 0, 2 <= T_in <= %d, 1 <= T_out <= %d)", B, T_in,
@@ -209,7 +174,7 @@ static int check_dims(int B, int T_in, int T_out, int flags) {
     return 0;
 }
 
-static int cu_count(int *cus) {
+int cu_count(int *cus) {
     int dev = 0;
     PF_HIP_CHECK(hipGetDevice(&dev));
     PF_HIP_CHECK(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -223,9 +188,28 @@ static int launch(const Args &a, hipStream_t s) {
     const double steps = a.T_in - 1 + a.T_out;
     ProfScope ps(s, "pf::odom::odom_forward_kernel", 2.0 * a.B * steps * (G3 * (H + 2)) + 2.0 * a.B * a.T_out * 2 * H,
                  4.0 * a.B * (a.T_in + 4 * a.T_out) + 4.0 * tiles * G3 * H);
-    hipLaunchKernelGGL((odom_forward_kernel<M>), dim3(tiles), dim3(THREADS), 0, s, a);
+    hipLaunchKernelGGL((odom_forward_kernel<M, false>), dim3(tiles), dim3(THREADS), 0, s, a);
     PF_LAUNCH_CHECK("odom_forward_kernel");
     return 0;
+}
+
+template <int M>
+static int launch_save(const Args &a, hipStream_t s) {
+    const int tiles = (a.B + 16 * M - 1) / (16 * M);
+    const double steps = a.T_in - 1 + a.T_out;
+    ProfScope ps(s, "pf::odom::odom_train_forward_kernel", 2.0 * a.B * steps * (G3 * (H + 2)) + 2.0 * a.B * a.T_out * 2 * H,
+                 4.0 * a.B * (a.T_in + 4 * a.T_out) + 4.0 * tiles * G3 * H + 4.0 * a.B * steps * (5 * H + 2));
+    hipLaunchKernelGGL((odom_forward_kernel<M, true>), dim3(tiles), dim3(THREADS), 0, s, a);
+    PF_LAUNCH_CHECK("odom_train_forward_kernel");
+    return 0;
+}
+
+int launch_train_forward(const Args &a, int m, hipStream_t s) {
+    switch (m) {
+        case 1: return launch_save<1>(a, s);
+        case 2: return launch_save<2>(a, s);
+        default: return launch_save<3>(a, s);
+    }
 }
 
 }  // namespace odom
@@ -265,12 +249,9 @@ extern "C" int pf_odom_forward(const float *packed, int flags, int B, int T_in, 
     a.whh = packed + PACKED_WHH;
     a.inps = inps, a.out = out, a.out_norm = out_norm;
     a.B = B, a.T_in = T_in, a.T_out = T_out, a.offset = flags & 1;
-    // M sub-tiles per workgroup: the fewest that keep the grid at or below one workgroup per CU (at most M_MAX; past
-    // 16 * M_MAX * CUs sequences the grid simply grows)
-    const long long per = 16LL * cus;
-    const int m = (int)((B + per - 1) / per);
+    a.sv = Saved{};
     hipStream_t s = (hipStream_t)stream;
-    switch (m < 1 ? 1 : (m > M_MAX ? M_MAX : m)) {
+    switch (pick_m(B, cus)) {
         case 1: return launch<1>(a, s);
         case 2: return launch<2>(a, s);
         default: return launch<3>(a, s);

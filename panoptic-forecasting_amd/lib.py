@@ -66,6 +66,9 @@ SIGNATURES = {
     'pf_odom_weights_size': (_i, [_i, _c.POINTER(_sz), _c.POINTER(_sz)]),
     'pf_odom_pack': (_i, [_vp, _vp, _i, _vp]),
     'pf_odom_forward': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'pf_odom_train_workspace': (_i, [_i, _i, _i, _i, _c.POINTER(_sz)]),
+    'pf_odom_train_forward': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pf_odom_backward': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'pf_set_option': (_i, [_c.c_char_p, _i]),
     'pf_hardnet_plan_set_option': (_i, [_vp, _c.c_char_p, _i]),
     'pf_debug_force_conv': (_i, [_i, _i, _i, _i]),

@@ -76,18 +76,20 @@ SNIPPET_LEN = 30            # rows of ``odometry`` per snippet in ``{split}_3d_i
 WINDOW_ROWS = 18            # odom_dataset.py:76 (``np.arange(18)``, independent of input_len / output_len)
 
 
-def odom_windows(odometry, input_len=9, output_len=9):
-    """The odometry forecaster's test-mode windows of one snippet (``OdomDataset(test=True)``, odom_dataset.py:73-83,94-121).
+def odom_windows(odometry, input_len=9, output_len=9, test=True):
+    """The odometry forecaster's windows of one snippet (``OdomDataset``, odom_dataset.py:73-83,94-121).
 
     ``odometry`` [30, >= 2] (columns ``[:, :2]`` = speed, yaw_rate are used).  Returns ``(inputs [N, input_len, 2],
     labels [N, output_len, 2], start_frames [N])`` as float32 / float32 / int64 in the dataset's order: ``start_ind`` 0 ..
-    30 - input_len (rows ``start_ind + arange(18)`` clipped at 29; inputs = the first input_len rows, labels = the rest),
-    then the two padded windows ``start_ind`` -1 and -2 (first row repeated; labels = the last output_len rows of
-    ``arange(18)[:-k]``).  ``start_frames`` = snippet index of the last input row = the export key's last field.
+    30 - input_len with ``test`` (the export's windows; rows ``start_ind + arange(18)`` clipped at 29; inputs = the first
+    input_len rows, labels = the rest) or 0 .. 30 - input_len - output_len without (the training windows, :73-81: every
+    label row is a measured one), then the two padded windows ``start_ind`` -1 and -2 (first row repeated; labels = the
+    last output_len rows of ``arange(18)[:-k]``).  ``start_frames`` = snippet index of the last input row = the export
+    key's last field.
     """
     odom = np.asarray(odometry)[:, :2].astype(np.float32)
     inds = np.arange(WINDOW_ROWS)
-    wins = [(s, (s + inds).clip(max=SNIPPET_LEN - 1)) for s in range(SNIPPET_LEN - input_len + 1)]
+    wins = [(s, (s + inds).clip(max=SNIPPET_LEN - 1)) for s in range(SNIPPET_LEN - input_len + 1 - (0 if test else output_len))]
     wins += [(-1, inds[:-1]), (-2, inds[:-2])]
     inputs, labels, starts = [], [], []
     for start, cur in wins:

@@ -131,7 +131,7 @@ struct GemmArgs {
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
 
 template <int TAPS, int EPI>
-__global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
+__global__ __launch_bounds__(256, TAPS == 9 ? 4 : 1) void gemm_kernel(GemmArgs a) {
     constexpr int KC = TAPS == 9 ? 8 : 32;      // channels per LDS round
     constexpr int KR = KC * TAPS;               // k per round (72 / 32)
     __shared__ float xs[KC * PS];
@@ -178,19 +178,58 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
         const float4 *wsrc = reinterpret_cast<const float4 *>(wt + (size_t)c0 * TAPS * 64);
         for (int i = tid; i < KR * 16; i += 256) reinterpret_cast<float4 *>(ws)[i] = wsrc[i];
         __syncthreads();
+        if (TAPS == 9) {
+            // blocked sum: the 18 matrix steps of a round go into a partial of their own, added to acc once per round - one chain
+            // over the whole K (up to 1188 steps on one accumulator) is 4x further from float64 than a blocked fp32 sum.
+            // Two M-tiles at a time keep the partials at 32 registers (the weight fragments are read once per pair).  The
+            // scheduling barrier, the un-unrolled step loop and the occupancy bound of 4 waves per SIMD (128 registers) keep the
+            // compiler from holding both pairs' partials and several steps' fragments at once: 178 ... 227 registers and 2 waves
+            // per SIMD without them, +38 % at N = 512; as written +5 % (N = 512) ... +8 % (N = 32) against the single chain
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                f32x4 part[2][4];
+                auto step = [&](int ks, bool first) {
+                    const int k = ks * 4 + (lane >> 4);
+                    const int ko = koff[k];
+                    float bf[4];
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) bf[g] = ws[k * 64 + g * 16 + (lane & 15)];
+#pragma unroll
+                    for (int mm = 0; mm < 2; ++mm) {
+                        if (wave + 4 * (2 * half + mm) < 13) {
+                            const float af = xs[pb[2 * half + mm] + ko];
+#pragma unroll
+                            for (int g = 0; g < 4; ++g)
+                                part[mm][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(af, bf[g], first ? f32x4{0.f, 0.f, 0.f, 0.f} : part[mm][g], 0, 0, 0);
+                        }
+                    }
+                };
+                step(0, true);
+#pragma unroll 1
+                for (int ks = 1; ks < KR / 4; ++ks) step(ks, false);
+#pragma unroll
+                for (int mm = 0; mm < 2; ++mm) {
+                    if (wave + 4 * (2 * half + mm) >= 13) continue;
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) acc[2 * half + mm][g] += part[mm][g];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
 #pragma unroll 2
-        for (int ks = 0; ks < KR / 4; ++ks) {
-            const int k = ks * 4 + (lane >> 4);
-            const int ko = koff[k];
-            float bf[4];
+            for (int ks = 0; ks < KR / 4; ++ks) {
+                const int k = ks * 4 + (lane >> 4);
+                const int ko = koff[k];
+                float bf[4];
 #pragma unroll
-            for (int g = 0; g < 4; ++g) bf[g] = ws[k * 64 + g * 16 + (lane & 15)];
+                for (int g = 0; g < 4; ++g) bf[g] = ws[k * 64 + g * 16 + (lane & 15)];
 #pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                if (wave + 4 * m < 13) {
-                    const float af = xs[pb[m] + ko];
+                for (int m = 0; m < 4; ++m) {
+                    if (wave + 4 * m < 13) {
+                        const float af = xs[pb[m] + ko];
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) acc[m][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(af, bf[g], acc[m][g], 0, 0, 0);
+                        for (int g = 0; g < 4; ++g) acc[m][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(af, bf[g], acc[m][g], 0, 0, 0);
+                    }
                 }
             }
         }

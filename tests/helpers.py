@@ -480,3 +480,9 @@ def stem_probe_record(case_id, entry):
     """stem_probe_dist.json next to the other measured reports: per case of tests/test_gpu_stem.py the worst err / bar of every
     run (hop flags, parameter set) and the kernels that ran"""
     _merge_report('stem_probe_dist.json', case_id, entry)
+
+
+def fg_probe_record(case_id, entry):
+    """fg_probe_dist.json next to the other measured reports: per case of tests/test_gpu_fg_stages.py the worst err / bar and
+    the terms the bar was made of.  The run on MI355X is kept as profiles/fg_probe_dist.json"""
+    _merge_report('fg_probe_dist.json', case_id, entry)

@@ -170,6 +170,29 @@ int pf_hop_load(const uint16_t *depth_u16, size_t n, float min_depth, float max_
                 uint8_t *out_mask, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training-time augmentation of BGDataset (data/transforms.py:183-293: joint random scale / pad / crop / nearest resize /
+ * flip) fused with the depth decode of the load hop - ONE launch per batch, enqueue only, no workspace.  Every step of the
+ * transform acts on one axis, so a sample's transform is four index tables built on the host (bg_augment.py):
+ *     out[y][x] = src[y_tab[y]][x_tab[x]],   entry j = source row / column of output row / column j.
+ *
+ *   seg_src   [B,T,Hs,Ws] u8        label_src [B,Hs,Ws] u8 or NULL       depth_src [B,T,Hs,Ws] u16 codes or NULL
+ *   y_map [B,oh], x_map [B,ow] i32  tables of the label maps (seg_src, label_src)
+ *   y_arr [B,oh], x_arr [B,ow] i32  tables of the depth arrays (may be NULL when depth_src is NULL)
+ *   out_seg [B,T,oh,ow] u8, out_label [B,oh,ow] u8, out_depth [B,T,oh,ow] f32, out_mask [B,T,oh,ow] u8 (0/1): the layout
+ *   pf_train_forward_backward takes (seg_is_i64 = 0, labels_are_i64 = 0); outputs of a NULL input are not written.
+ *
+ * A table entry outside [0,Hs) resp. [0,Ws) is padding and is never followed as an address: padding gives pad_label (0..255)
+ * in seg and label, and depth code 0, which decodes to -1 with mask 0.  Depth codes decode exactly as in pf_hop_load.
+ * With ow % 4 == 0, out_depth 16-byte and the u8 outputs 4-byte aligned the stores are 16 / 4 bytes per lane; any other
+ * width or alignment (out_depth at least 4-byte, depth_src 2-byte, tables 4-byte) takes scalar stores.  ow <= 8192 (the x
+ * tables are staged in LDS), else PF_EUNSUPPORTED.  B = 0 launches nothing.
+ */
+int pf_bg_augment(const uint8_t *seg_src, const uint8_t *label_src, const uint16_t *depth_src, int B, int T, int Hs, int Ws,
+                  const int *y_map, const int *x_map, const int *y_arr, const int *x_arr, int oh, int ow, int pad_label,
+                  float min_depth, float max_depth, uint8_t *out_seg, uint8_t *out_label, float *out_depth,
+                  uint8_t *out_mask, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * fg -> panoptic merge — replaces the pasting loops of FGModel.predict_panoptic
  * (models/fg/fg_model.py:548-588; panoptic_ids=1, clear_things=1) and FGModel.predict_semantics (:455-480; panoptic_ids=0,
  * clear_things=0) together with model_utils.paste_mask (models/fg/model_utils.py:30-57).

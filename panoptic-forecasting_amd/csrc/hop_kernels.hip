@@ -15,6 +15,7 @@
 // (scripts/bg/run_export_bg_val.sh -> data/bg/* -> task bg) runs on the device up to the PNG encoder, with 3 B per
 // pixel crossing PCIe instead of 5, and so that tests can prove "in-register hop == file hop" bit for bit.
 // One lane = 4 consecutive pixels (16-B depth loads, 8-B u16 stores, 4-B label stores).
+#include "hop_decode.h"
 #include "pf_common.h"
 #include "pf_prof.h"
 
@@ -90,16 +91,6 @@ struct HopLoadArgs {
     size_t n;
     float min_depth, max_depth;
 };
-
-__device__ __forceinline__ float hop_decode(uint16_t q, float lo, float hi, uint8_t &m) {
-    float d = (float)q / 256.f - 1.f;
-    const bool mk = d > 0.f;
-    m = mk ? 1 : 0;
-    if (!mk) return -1.f;
-    d = d > hi ? hi : d;    // _clamp_depths order: upper bound first, then lower (bg_dataset.py:166-170)
-    d = d < lo ? lo : d;
-    return d;
-}
 
 __global__ __launch_bounds__(256) void hop_load_kernel(HopLoadArgs a) {
     const size_t n4 = a.n >> 2;

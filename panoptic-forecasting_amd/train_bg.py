@@ -15,7 +15,10 @@ call per micro-batch for forward + loss + backward, one for clip + SGD (``bg_tra
 ONE all-reduce of the flat gradient per update instead of DDP buckets.
 
 Datasets are outside the hot path: with the reference package importable, ``--dataset reference`` builds
-``BGDataset`` through its own ``build_dataset``; ``--synthetic N`` trains on N synthetic Cityscapes-shaped crops per epoch.
+``BGDataset`` through its own ``build_dataset``; ``--dataset native`` reads the same exported files with ``bg_dataset.py`` (no
+reference package, ``cv2``, ``h5py`` or ``torchvision`` needed: PNG decode on a thread pool, the joint scale / crop / resize / flip
+and the depth decode in one ``pf_bg_augment`` launch per batch); ``--synthetic N`` trains on N synthetic Cityscapes-shaped crops
+per epoch.
 """
 import os
 import random
@@ -38,7 +41,8 @@ from . import synth                # noqa: E402
 
 EXTRA_FLAGS = (
     ('--synthetic', dict(type=int, default=0, help='train on N synthetic crops per epoch instead of a dataset')),
-    ('--dataset', dict(default='reference', choices=['reference'])),
+    ('--dataset', dict(default='reference', choices=['reference', 'native'],
+                       help="'native': bg_dataset.py (PNG decode on the host, augmentation on the device), no reference package")),
 )
 
 
@@ -179,11 +183,16 @@ def main(argv=None):
         crop = crop if isinstance(crop, int) else int(crop[-1])
         loader = SyntheticCrops(int(params['synthetic']), crop, int(tr.get('batch_size', 8)), data['num_classes'], rank, world)
         val_loader = None
+    elif params.get('dataset') == 'native':
+        from . import bg_dataset
+        datasets = bg_dataset.build_dataset(params)    # injects data.num_classes / depth_norm_params like the reference's
+        loader = bg_dataset.NativeBatches(datasets['train'], params, rank, world, train=True)
+        val_loader = bg_dataset.NativeBatches(datasets['val'], params, rank, world, train=False) if 'val' in datasets else None
     else:
         try:
             from panoptic_forecasting.data import build_dataset
         except ImportError as e:
-            raise SystemExit('the reference package is not importable (%s): pass --synthetic N' % e)
+            raise SystemExit('the reference package is not importable (%s): pass --dataset native or --synthetic N' % e)
         datasets = build_dataset(params)       # injects data.num_classes / depth_norm_params / collate_fn (bg_dataset.py:62-66)
         loader = DatasetBatches(datasets['train'], params, rank, world, train=True)
         val_loader = DatasetBatches(datasets['val'], params, rank, world, train=False) if 'val' in datasets else None

@@ -484,11 +484,13 @@ int pf_profile_collect(void);
 int pf_profile_get(int i, char *label, size_t label_cap, int *launches, double *total_ms, double *flops,
                    double *bytes);
 
-/* Tuning/diagnostic hook (tools/tune_convs.py, tests): force the convolution kernel and tile shape of every
- * stride-1 conv the library launches from now on.  kind 0 = automatic (default); 1 = conv_dma (p0 = WM in
- * {1,2,4}, p1 = NT); 2 = conv_wave (p0 = rows per tile in {1,2,4}, p1 = NT in {1,2}, p2 = K-split waves in
- * {2,4,8,16}); 3 = conv_valu (3x3 only, p0 = rows per wave in {1,2}); 4 = conv_split (3x3 only, p0 = NT in {1,2,3},
- * p1 = 1 for 8x64-pixel tiles).  Shapes that are not built fall back to the automatic choice.  Process-wide, not
+/* Tuning/diagnostic hook (tools/tune_convs.py, tools/tune_s4.py, tests): force the convolution kernel and tile shape of every
+ * stride-1 conv the library launches from now on.  kind (csrc/conv_mfma.h: ConvKind) 0 = CONV_AUTO, automatic (default);
+ * 1 = CONV_DMA, conv_dma (p0 = WM in {1,2,4}, p1 = NT; 0 = by its cost model); 2 = CONV_WAVE, conv_wave (p0 = rows per tile in
+ * {1,2,4}, p1 = NT in {1,2}, p2 = K-split waves in {2,4,8,16}); 3 = retired (was conv_valu); 4 = CONV_SPLIT, conv_split (p0 = NT in
+ * {1,2,3}, p1 = 1 for 8x64-pixel tiles); 5 = CONV_S4, conv_s4 on packed-pair sources wherever the plan can provide them, conv_dma
+ * elsewhere (p0 = NT, p1 = the 3x3 pixel tile, S4Tile: 0 = S4_8x32, 1 = S4_8x64, 2 = S4_16x32, 3 = S4_8x32_K2, 4 = S4_8x32_K4 - 8x32
+ * with 2 / 4 wave groups splitting the K rounds).  Shapes that are not built fall back to the automatic choice.  Process-wide, not
  * thread-safe.
  * The training step honours kind 1 only: while pf_debug_force_conv(1, wm, nt, 0) is set, every forward and backward-data
  * convolution of pf_train_forward_backward (stride 2 included) runs conv_dma with wm pixel waves and min(nt, the layer's cout
@@ -496,6 +498,14 @@ int pf_profile_get(int i, char *label, size_t label_cap, int *launches, double *
  * the cost model or pf_train_autotune, and pf_train_path_stats counts it in none of stats[0..2] (tests: every built shape of the
  * training convolutions against a reference). */
 int pf_debug_force_conv(int kind, int p0, int p1, int p2);
+/* Host only, no device involved, nothing enqueued (tests): what the schedules decide for one convolution (csrc/conv_select.cpp:
+ * decide_conv) under the current pf_debug_force_conv.  B = the batch the choice is made for, need: bit 1 = pooling epilogue, bit 2 =
+ * another fused stage; flags: 1 = input width % 4 != 0 (generic kernel), 2 / 4 = the plan has the conv_split / conv_s4 packing of the
+ * conv, 8 = option use_tuned_table, 16 = option split_f16, 32 = blocked sums (training); rounds = K rounds of the conv_s4 packing.
+ * out[0..10] (cap >= 11) = kind, p0, p1, p2 of the fp32-source kernel, whether the conv wants packed-pair sources, the conv_s4 NT and
+ * tile it then asks for, and NT, TW, TH, KS of the conv_s4 instantiation that request runs (s4_resolve). */
+int pf_debug_conv_decision(int ks, int stride, int cin, int cout, int hout, int wout, int B, int need, int flags, int rounds,
+                           int *out, int cap);
 /* Host only, no device involved (tests): the weight arena a plan created now from this blob would upload - every packing of every
  * convolution under the process-wide options - copied to out when cap >= *n_floats, and per op of the table (table_ops rows of six
  * numbers, nullable): offset in floats and rounds of its packed-pair packing, offset and cout tiles of its share launch's packing,

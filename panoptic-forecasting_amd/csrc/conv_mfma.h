@@ -286,7 +286,15 @@ int s4_entries(const S4Range *r, int n_src, int ks, int pad_sources);
 int s4_rounds(const S4Range *r, int n_src, int ks, int pad_sources);
 size_t s4_packed_floats(const S4Range *r, int n_src, int cout, int ks, int pad_sources);
 void pack_conv_weights_s4(const float *w_oihw, int cin, int cout, int ks, const S4Range *r, int n_src, int pad_sources, float *out);
-int launch_conv_s4(const ConvArgs &a, int ks, int nt, int wide, int B, hipStream_t stream);
+// the pixel tile a 3x3 launch is asked for: 8x32, 8x64, 16x32 on 8 waves, 8x32 with 2 / 4 wave groups splitting the rounds.  The values
+// are the ABI of pf_debug_force_conv(5, nt, tile, 0) and the contents of conv_s4_tuned.inc
+enum S4Tile : int { S4_8x32 = 0, S4_8x64 = 1, S4_16x32 = 2, S4_8x32_K2 = 3, S4_8x32_K4 = 4 };
+// The instantiation that runs a request of nt cout tiles per workgroup on `tile` for a conv of ntiles cout tiles and `rounds` K rounds
+// (conv_select.cpp; 1x1 and kacc - the blocked sums of training - know 8x32 only): conv_s4[_blocked]_kernel<NT, TW, TH, KS>,
+// conv_s4_1x1_kernel<NT, *>.  The schedules resolve when they make the step; launch_conv_s4 dispatches on the result
+struct S4Shape { int NT, TW, TH, KS; };
+S4Shape s4_resolve(int ks, int nt, int tile, int ntiles, int rounds, bool kacc);
+int launch_conv_s4(const ConvArgs &a, int ks, const S4Shape &shape, int B, hipStream_t stream);
 // a pair P = conv3x3(S), C = conv3x3(P ++ S ++ others) as two launches that read S once (8 x 32 tiles, nt cout tiles per workgroup;
 // ConvArgs::share ..): `share` = P's launch whose matrix also holds C's rows over S and stores their sums, `add` = C's launch over its
 // other ranges, which adds them.  share_wanted (conv_select.cpp): mode = the plan's share_s option (0 never, 1 the measured rule, 2 wherever
@@ -358,17 +366,59 @@ struct FrontArgs {
 bool conv_front_supports(int c0, int c1, int c2, int h1, int w1, int dst_ctotal);
 int launch_conv_front(const FrontArgs &a, int B, hipStream_t s);
 
-// Kernel/shape choice for one stride-1 conv (conv_select.cpp): kind 1 = conv_dma (p0 = WM, p1 = NT),
-// kind 2 = conv_wave (p0 = MH, p1 = NT, p2 = WK), (kind 3 was conv_valu: the whole 3x3 conv on v_pk_fma_f32, measured and removed - DESIGN.md 3.2),
-// kind 4 = conv_split (p0 = NT, p1 = 1: 8x64-pixel tiles), kind 5 = conv_s4 (same parameters; S4 sources).
+// Kernel / shape choice for one stride-1 conv (conv_select.cpp).  The values are the ABI of pf_debug_force_conv and the contents of
+// conv_tuned.inc / conv_s4_tuned.inc (3 was conv_valu: the whole 3x3 conv on v_pk_fma_f32, measured and removed - DESIGN.md 3.2)
+enum ConvKind : int { CONV_AUTO = 0, CONV_DMA = 1, CONV_WAVE = 2, CONV_SPLIT = 4, CONV_S4 = 5 };
+// four ints (the table rows aggregate-initialise it); what p0..p2 mean per kind is said by the makers and readers only
 struct ConvChoice {
     int kind, p0, p1, p2;
+    static ConvChoice dma(int wm = 0, int nt = 0) { return {CONV_DMA, wm, nt, 0}; }   // 0: by conv_dma's cost model
+    static ConvChoice wave(int mh, int nt, int wk) { return {CONV_WAVE, mh, nt, wk}; }
+    static ConvChoice split(int nt, int wide) { return {CONV_SPLIT, nt, wide, 0}; }   // wide = 1: 8x64-pixel tiles
+    bool is(ConvKind k) const { return kind == k; }   // (CONV_S4: S4 sources, NT and S4Tile; table rows and the forced choice only)
+    int dma_wm() const { return p0; }
+    int dma_nt() const { return p1; }
+    int wave_mh() const { return p0; }
+    int wave_nt() const { return p1; }
+    int wave_wk() const { return p2; }
+    int split_nt() const { return p0; }
+    int split_wide() const { return p1; }
+    int s4_nt() const { return p0; }
+    int s4_tile() const { return p1; }
 };
 // need: bit 1 = even tile rows if conv_wave is chosen (pooling epilogue)
 ConvChoice choose_conv(int ks, int stride, int cin, int cout, int hout, int wout, int B, int need = 0, int use_tuned = 1);
-bool choose_s4(int ks, int cin, int cout, int hout, int wout, int B, ConvChoice *out);   // conv_s4 table row, if any
+// conv_s4 table row, if any: CONV_S4 with its shape, or CONV_AUTO = the fp32-source kernel measured faster in situ
+bool choose_s4(int ks, int cin, int cout, int hout, int wout, int B, ConvChoice *out);
+// Everything the schedules decide about one conv from its shape, the plan's options and the forced choice
+struct ConvQuery {
+    int ks, stride, cin, cout, hout, wout;
+    int B;          // the batch the choice is made for (option "table_batch")
+    int need;       // bit 1 = even tile rows (pooling epilogue), bit 2 = another fused stage
+    bool generic;   // input width % 4 != 0: the generic kernel, nothing to choose
+    bool has_split, has_s4;   // the plan packed the conv's weights for conv_split / conv_s4
+    bool use_tuned, split_f16, kacc;   // options "use_tuned_table", "split_f16"; blocked sums (training)
+    int rounds;     // K rounds of the S4 packing
+    ConvChoice force;   // conv_force()
+};
+struct ConvDecision {
+    ConvChoice ch;      // its fp32-source kernel (CONV_AUTO: generic)
+    bool wants_s4;      // S4 sources if the plan can give them to it ...
+    int s4_nt, s4_tile; // ... then conv_s4 is asked for this shape ...
+    S4Shape s4;         // ... and runs this one
+};
+ConvDecision decide_conv(const ConvQuery &q);
 long long *probe_buffer();
-// tuning hook (pf_debug_force_conv): kind 0 = automatic
-extern ConvChoice g_conv_force;
+// tuning hook (pf_debug_force_conv): CONV_AUTO = automatic
+ConvChoice conv_force();
+inline bool conv_forced() { return !conv_force().is(CONV_AUTO); }
+inline bool force_allows_s4() { return !conv_forced() || conv_force().is(CONV_S4); }
+// pf_debug_force_conv(1, wm > 0, nt, 0): the conv_dma shape of every convolution of a training step
+inline bool forced_dma_shape(int *wm, int *nt) {
+    const ConvChoice f = conv_force();
+    if (!f.is(CONV_DMA) || f.dma_wm() <= 0) return false;
+    *wm = f.dma_wm(); *nt = f.dma_nt();
+    return true;
+}
 
 }  // namespace pf

@@ -117,71 +117,39 @@ struct S4Cfg {
 #undef S4_KERNEL_EPI
 #undef S4_KERNEL_WAVES
 
-template <int NT, int TW_, int TH_ = 8, int KS_ = 1>
-static int launch_s4_cfg(const ConvArgs &a0, int B, hipStream_t s) {
+// one launcher for the four forms of the 3x3 kernel (conv_s4_kernel.inc); the label = the symbol rocprofv3 reports (bench.py looks
+// its PMC bytes up by it)
+enum S4Form { S4_PLAIN, S4_BLOCKED, S4_SHARE, S4_ADD };
+template <S4Form FORM, int NT, int TW_, int TH_, int KS_>
+static constexpr auto s4_kernel() {   // (only the form asked for is instantiated)
+    if constexpr (FORM == S4_PLAIN) return &conv_s4_kernel<NT, TW_, TH_, KS_>;
+    else if constexpr (FORM == S4_BLOCKED) return &conv_s4_blocked_kernel<NT, TW_, TH_, KS_>;
+    else if constexpr (FORM == S4_SHARE) return &conv_s4_share_kernel<NT, TW_, TH_, KS_>;
+    else return &conv_s4_add_kernel<NT, TW_, TH_, KS_>;
+}
+template <S4Form FORM, int NT, int TW_ = 32, int TH_ = 8, int KS_ = 1>
+static int launch_s4_form(const ConvArgs &a0, int B, hipStream_t s) {
     using C = S4Cfg<NT, TW_, TH_, KS_>;
+    constexpr auto kernel = s4_kernel<FORM, NT, TW_, TH_, KS_>();
+    constexpr const char *name = FORM == S4_PLAIN ? "conv_s4_kernel" : FORM == S4_BLOCKED ? "conv_s4_blocked_kernel"
+                               : FORM == S4_SHARE ? "conv_s4_share_kernel" : "conv_s4_add_kernel";
     ConvArgs a = a0;
     a.tilesX = (a.Wout + C::TW - 1) / C::TW;
     a.tilesY = (a.Hout + C::TH - 1) / C::TH;
     static bool attr_set = false;
     if (!attr_set) {
-        PF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_s4_kernel<NT, TW_, TH_, KS_>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
+        PF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
         attr_set = true;
     }
     char label[96];
-    snprintf(label, sizeof(label), "void pf::conv_s4_kernel<%d, %d, %d, %d>(pf::ConvArgs)", NT, TW_, TH_, KS_);   // = the symbol rocprofv3 reports (bench.py looks its PMC bytes up by it)
+    snprintf(label, sizeof(label), "void pf::%s<%d, %d, %d, %d>(pf::ConvArgs)", name, NT, TW_, TH_, KS_);
     const double px = (double)B * a.Hout * a.Wout;
-    ProfScope ps(s, label, 2.0 * px * a.Cout * a.Cin * 9,
-                 4.0 * ((double)B * a.Cin * a.Hin * a.Win + px * a.Cout + (double)a.Cout * a.Cin * 9));
-    hipLaunchKernelGGL((conv_s4_kernel<NT, TW_, TH_, KS_>), dim3(a.tilesX * a.tilesY, (a.ntiles + NT - 1) / NT, B), dim3(C::NTHR * C::KS), C::LDS_BYTES, s, a);
-    PF_LAUNCH_CHECK("conv_s4_kernel");
-    return PF_OK;
-}
-
-template <int NT>
-static int launch_s4_blocked_cfg(const ConvArgs &a0, int B, hipStream_t s) {
-    using C = S4Cfg<NT, 32, 8, 1>;
-    ConvArgs a = a0;
-    a.tilesX = (a.Wout + C::TW - 1) / C::TW;
-    a.tilesY = (a.Hout + C::TH - 1) / C::TH;
-    static bool attr_set = false;
-    if (!attr_set) {
-        PF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_s4_blocked_kernel<NT, 32, 8, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
-        attr_set = true;
-    }
-    char label[96];
-    snprintf(label, sizeof(label), "void pf::conv_s4_blocked_kernel<%d, 32, 8, 1>(pf::ConvArgs)", NT);
-    const double px = (double)B * a.Hout * a.Wout;
-    ProfScope ps(s, label, 2.0 * px * a.Cout * a.Cin * 9, 4.0 * ((double)B * a.Cin * a.Hin * a.Win + px * a.Cout + (double)a.Cout * a.Cin * 9));
-    hipLaunchKernelGGL((conv_s4_blocked_kernel<NT, 32, 8, 1>), dim3(a.tilesX * a.tilesY, (a.ntiles + NT - 1) / NT, B), dim3(C::NTHR), C::LDS_BYTES, s, a);
-    PF_LAUNCH_CHECK("conv_s4_blocked_kernel");
-    return PF_OK;
-}
-
-// the share (ADD = false) / add form on 8 x 32 tiles, NT cout tiles per workgroup
-template <int NT, bool ADD>
-static int launch_s4_share_cfg(const ConvArgs &a0, int B, hipStream_t s) {
-    using C = S4Cfg<NT, 32, 8, 1>;
-    ConvArgs a = a0;
-    a.tilesX = (a.Wout + C::TW - 1) / C::TW;
-    a.tilesY = (a.Hout + C::TH - 1) / C::TH;
-    const void *fn = ADD ? reinterpret_cast<const void *>(&conv_s4_add_kernel<NT, 32, 8, 1>) : reinterpret_cast<const void *>(&conv_s4_share_kernel<NT, 32, 8, 1>);
-    static bool attr_set = false;
-    if (!attr_set) {
-        PF_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
-        attr_set = true;
-    }
-    char label[96];
-    snprintf(label, sizeof(label), "void pf::conv_s4_%s_kernel<%d, 32, 8, 1>(pf::ConvArgs)", ADD ? "add" : "share", NT);
-    const double px = (double)B * a.Hout * a.Wout;
-    const int rows = ADD ? a.Cout : a.Cout + a.share_cout;   // output channels the matrix instructions produce
-    ProfScope ps(s, label, 2.0 * px * rows * a.Cin * 9,
-                 4.0 * ((double)B * a.Cin * a.Hin * a.Win + px * (a.Cout + (double)(a.share_cout + 3) / 4 * 4) + (double)rows * a.Cin * 9));
-    const dim3 grid(a.tilesX * a.tilesY, (a.ntiles + NT - 1) / NT, B);
-    if (ADD) hipLaunchKernelGGL((conv_s4_add_kernel<NT, 32, 8, 1>), grid, dim3(C::NTHR), C::LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((conv_s4_share_kernel<NT, 32, 8, 1>), grid, dim3(C::NTHR), C::LDS_BYTES, s, a);
-    PF_LAUNCH_CHECK(ADD ? "conv_s4_add_kernel" : "conv_s4_share_kernel");
+    // share: the matrix instructions also produce the consumer's rows, stored as fp32 sums in groups of 4; add: reads them
+    const int rows = FORM == S4_SHARE ? a.Cout + a.share_cout : a.Cout;
+    const double sums = FORM == S4_SHARE || FORM == S4_ADD ? (double)(a.share_cout + 3) / 4 * 4 : 0.0;
+    ProfScope ps(s, label, 2.0 * px * rows * a.Cin * 9, 4.0 * ((double)B * a.Cin * a.Hin * a.Win + px * (a.Cout + sums) + (double)rows * a.Cin * 9));
+    hipLaunchKernelGGL(kernel, dim3(a.tilesX * a.tilesY, (a.ntiles + NT - 1) / NT, B), dim3(C::NTHR * C::KS), C::LDS_BYTES, s, a);
+    PF_LAUNCH_CHECK(name);
     return PF_OK;
 }
 
@@ -197,21 +165,21 @@ static int check_share(const ConvArgs &a, const char *who) {
     if (!a.share || a.share_cout < 1 || (reinterpret_cast<uintptr_t>(a.share) & 15) != 0) return fail(PF_EINVAL, "%s: no scratch tensor", who);
     return PF_OK;
 }
-#define PF_S4_SHARE(ADD_) \
+#define PF_S4_SHARE(FORM_) \
     nt = nt < 1 ? 1 : (nt > a.ntiles ? a.ntiles : nt); \
-    if (nt == 1) return launch_s4_share_cfg<1, ADD_>(a, B, s); \
-    if (nt == 2) return launch_s4_share_cfg<2, ADD_>(a, B, s); \
-    return launch_s4_share_cfg<3, ADD_>(a, B, s);
+    if (nt == 1) return launch_s4_form<FORM_, 1>(a, B, s); \
+    if (nt == 2) return launch_s4_form<FORM_, 2>(a, B, s); \
+    return launch_s4_form<FORM_, 3>(a, B, s);
 int launch_conv_s4_share(const ConvArgs &a, int nt, int B, hipStream_t s) {
     if (int rc = check_share(a, "conv_s4 share")) return rc;
     if ((a.share_off & 3) != 0 || a.share_off < a.Cout || a.share_off + a.share_cout > a.ntiles * 16)
         return fail(PF_EINVAL, "conv_s4 share: rows %d + %d in %d tiles", a.share_off, a.share_cout, a.ntiles);
-    PF_S4_SHARE(false)
+    PF_S4_SHARE(S4_SHARE)
 }
 int launch_conv_s4_add(const ConvArgs &a, int nt, int B, hipStream_t s) {
     if (int rc = check_share(a, "conv_s4 add")) return rc;
     if (a.share_cout != a.Cout) return fail(PF_EINVAL, "conv_s4 add: stored sums of %d channels for %d", a.share_cout, a.Cout);
-    PF_S4_SHARE(true)
+    PF_S4_SHARE(S4_ADD)
 }
 #undef PF_S4_SHARE
 
@@ -570,49 +538,34 @@ static int launch_s41_cfg(const ConvArgs &a0, int B, hipStream_t s) {
 
 // a.wpk = pack_conv_weights_s4() output, a.nchunks = s4_rounds(), a.src_fmt = 1 (sources in the S4 layout, a.src_c4 /
 // src_g0 / src_ent0 filled), a.chunk_begin/chunk_end = the rounds to run.
-// ks = 3: nt = cout tiles per workgroup (1..3), wide = 8x64-pixel tiles.  ks = 1: nt = 1..4.
-int launch_conv_s4(const ConvArgs &a, int ks, int nt, int wide, int B, hipStream_t s) {
+// sh = s4_resolve() of the request (the schedules keep it in the step): the instantiations below are all it can name
+int launch_conv_s4(const ConvArgs &a, int ks, const S4Shape &sh, int B, hipStream_t s) {
     if (!a.src_fmt) return fail(PF_EINVAL, "conv_s4: sources are not in the S4 layout");
     if ((a.Wout & 3) != 0 || a.Hin != a.Hout || a.Win != a.Wout) return fail(PF_EUNSUPPORTED, "conv_s4: stride 1, width % 4 == 0 only");
-    nt = nt < 1 ? 1 : (nt > a.ntiles ? a.ntiles : nt);
     if (ks == 3) {
         if (a.pool || a.res || a.no_bias) return fail(PF_EUNSUPPORTED, "conv_s4 3x3: no fused epilogue stages");
         if (a.chunk_begin != 0 || a.chunk_end != a.nchunks) return fail(PF_EUNSUPPORTED, "conv_s4 3x3: whole K range only");
-        if (a.kacc) {      // blocked summation (training): 8 x 32 tiles, 1 - 3 cout tiles
-            if (nt == 1) return launch_s4_blocked_cfg<1>(a, B, s);
-            if (nt == 2) return launch_s4_blocked_cfg<2>(a, B, s);
-            return launch_s4_blocked_cfg<3>(a, B, s);
+#define PF_S4(FORM_, NT_, TW_, TH_, KS_) \
+    if (sh.NT == NT_ && sh.TW == TW_ && sh.TH == TH_ && sh.KS == KS_) return launch_s4_form<FORM_, NT_, TW_, TH_, KS_>(a, B, s);
+        if (a.kacc) {   // blocked summation (training)
+            PF_S4(S4_BLOCKED, 1, 32, 8, 1) PF_S4(S4_BLOCKED, 2, 32, 8, 1) PF_S4(S4_BLOCKED, 3, 32, 8, 1)
+        } else {
+            PF_S4(S4_PLAIN, 1, 32, 8, 1) PF_S4(S4_PLAIN, 2, 32, 8, 1) PF_S4(S4_PLAIN, 3, 32, 8, 1)
+            PF_S4(S4_PLAIN, 4, 32, 8, 1)    // 4 cout tiles per pixel fragment read from LDS (2 workgroups per CU)
+            PF_S4(S4_PLAIN, 1, 64, 8, 1) PF_S4(S4_PLAIN, 2, 64, 8, 1)
+            PF_S4(S4_PLAIN, 1, 32, 16, 1) PF_S4(S4_PLAIN, 2, 32, 16, 1)   // 8 waves
+            PF_S4(S4_PLAIN, 1, 32, 8, 2) PF_S4(S4_PLAIN, 2, 32, 8, 2)     // two wave groups split the rounds ...
+            PF_S4(S4_PLAIN, 1, 32, 8, 4) PF_S4(S4_PLAIN, 2, 32, 8, 4)     // ... FOUR (16 waves on one tile)
         }
-        if (wide == 2) {   // 16x32-pixel tiles, 8 waves
-            if (nt == 1) return launch_s4_cfg<1, 32, 16>(a, B, s);
-            return launch_s4_cfg<2, 32, 16>(a, B, s);
-        }
-        if (wide == 4 && a.nchunks >= 16) {   // 8x32-pixel tiles, FOUR wave groups split the rounds (16 waves on one tile)
-            if (nt == 1) return launch_s4_cfg<1, 32, 8, 4>(a, B, s);
-            return launch_s4_cfg<2, 32, 8, 4>(a, B, s);
-        }
-        if (wide >= 3 && a.nchunks >= 8) {   // 8x32-pixel tiles, two wave groups split the rounds (small images, long K)
-            if (nt == 1) return launch_s4_cfg<1, 32, 8, 2>(a, B, s);
-            return launch_s4_cfg<2, 32, 8, 2>(a, B, s);
-        }
-        if (wide >= 3) wide = 0;
-        if (wide) {
-            if (nt == 1) return launch_s4_cfg<1, 64>(a, B, s);
-            if (nt == 2) return launch_s4_cfg<2, 64>(a, B, s);
-            return launch_s4_cfg<3, 32>(a, B, s);   // 3 cout tiles: the 8x64 stages would leave one workgroup per CU
-        }
-        if (nt == 1) return launch_s4_cfg<1, 32>(a, B, s);
-        if (nt == 2) return launch_s4_cfg<2, 32>(a, B, s);
-        if (nt == 3) return launch_s4_cfg<3, 32>(a, B, s);
-        return launch_s4_cfg<4, 32>(a, B, s);   // 4 cout tiles per pixel fragment read from LDS (2 workgroups per CU)
-    }
-    nt = nt > 4 ? 4 : nt;
-    const bool fused = a.pool || a.res || a.no_bias;
+#undef PF_S4
+    } else if (sh.TW == 32 && sh.TH == 8 && sh.KS == 1) {
+        const bool fused = a.pool || a.res || a.no_bias;
 #define PF_S41(NT_) \
-    if (nt == NT_) return fused ? launch_s41_cfg<NT_, 1>(a, B, s) : launch_s41_cfg<NT_, 0>(a, B, s);
-    PF_S41(1) PF_S41(2) PF_S41(3) PF_S41(4)
+    if (sh.NT == NT_) return fused ? launch_s41_cfg<NT_, 1>(a, B, s) : launch_s41_cfg<NT_, 0>(a, B, s);
+        PF_S41(1) PF_S41(2) PF_S41(3) PF_S41(4)
 #undef PF_S41
-    return PF_EUNSUPPORTED;
+    }
+    return fail(PF_EUNSUPPORTED, "conv_s4 %dx%d: shape <%d, %d, %d, %d> is not built", ks, ks, sh.NT, sh.TW, sh.TH, sh.KS);
 }
 
 // ------------------------------------------------------------------------------------------------ host side: weights

@@ -3,9 +3,8 @@
 
 namespace pf {
 
-ConvChoice g_conv_force = {0, 0, 0, 0};
-
 namespace {
+ConvChoice g_conv_force = {CONV_AUTO, 0, 0, 0};   // pf_debug_force_conv
 struct Tuned {
     int ks, cin, cout, hout, wout, B;
     ConvChoice c;
@@ -17,8 +16,8 @@ const Tuned kTuned[] = {
 };
 
 // conv_s4 (packed-pair sources): measured per-layer shapes with every eligible layer on conv_s4 (tools/tune_s4.py --emit).
-// kind 5 = run it on conv_s4 with (p0 = cout tiles per workgroup, p1 = 8x64-pixel tiles) if the plan can give it S4 sources,
-// kind 0 = the table's fp32-source kernel measured faster in situ: do not ask for S4 sources.
+// kind 5 (CONV_S4) = run it on conv_s4 with (p0 = cout tiles per workgroup, p1 = S4Tile) if the plan can give it S4 sources,
+// kind 0 (CONV_AUTO) = the table's fp32-source kernel measured faster in situ: do not ask for S4 sources.
 const Tuned kTunedS4[] = {
     {0, 0, 0, 0, 0, 0, {0, 0, 0, 0}},
 #include "conv_s4_tuned.inc"
@@ -110,7 +109,7 @@ bool share_wanted(int p_cin, int p_cout, int c_cin, int c_cout, int h, int w, in
 }
 
 ConvChoice choose_conv(int ks, int stride, int cin, int cout, int hout, int wout, int B, int need, int use_tuned) {
-    if (stride != 1) return ConvChoice{1, 0, 0, 0};           // conv_dma, shape by its cost model
+    if (stride != 1) return ConvChoice::dma();           // shape by its cost model
     // The table was measured at B = 1, 2, 4, 8, 16 and (round 5, the strict-fp32 model at the headline's sub-batch) 32; a layer
     // without a row at one of those: the heuristics below won there.  Any other batch size takes the decision of the nearest
     // measured one (in ratio; the larger on a tie; beyond the largest: the largest): the choice depends on how many tiles the
@@ -130,7 +129,7 @@ ConvChoice choose_conv(int ks, int stride, int cin, int cout, int hout, int wout
     //  > 3 % - so it does NOT fall back to its B = 16 row)
     for (const Tuned &t : kTuned)
         if (use_tuned && t.ks == ks && t.cin == cin && t.cout == cout && t.hout == ht && t.wout == wt && t.B == Bt &&
-            (!(need & 2) || t.c.kind != 2 || t.c.p0 != 1))
+            (!(need & 2) || !t.c.is(CONV_WAVE) || t.c.wave_mh() != 1))
             return t.c;
     // Untuned shape.  Large stride-1 3x3 layers go to the split kernel: on every measured shape with >= 64x128
     // pixels x 4 images it beat the fp32-MFMA kernels by 1.3-2.2x (profiles/README.md); cout tiles per workgroup by
@@ -139,7 +138,7 @@ ConvChoice choose_conv(int ks, int stride, int cin, int cout, int hout, int wout
     if (ks == 3 && (need == 0) && (wout & 3) == 0 && (long)B * hout * wout >= 32768) {
         const int nt = cout <= 16 ? 1 : (cout <= 32 ? 2 : 3);
         const long tiles_wide = (long)B * ((hout + 7) / 8) * ((wout + 63) / 64) * (((cout + 15) / 16 + nt - 1) / nt);
-        return ConvChoice{4, nt, (nt <= 2 && tiles_wide >= 512) ? 1 : 0, 0};
+        return ConvChoice::split(nt, (nt <= 2 && tiles_wide >= 512) ? 1 : 0);
     }
     // Images of >= 256x512 pixels keep the barrier-synchronised kernel (its big shared tiles move the
     // fewest bytes); below that the wave-autonomous kernel wins everywhere it was measured.  Pick the tile with the
@@ -148,9 +147,9 @@ ConvChoice choose_conv(int ks, int stride, int cin, int cout, int hout, int wout
     //  cannot write the packed-pair layout, so every 3x3 layer of that level fell back to the fp32-source split kernel: 0.56 of
     //  2.76 ms.  The measured table of the 1024x2048 network makes the same cut: packed pairs down to 32x64 at B = 16.)
     const long px = (long)B * hout * wout;
-    if (px >= 131072 || (ks == 1 && px >= 32768)) return ConvChoice{1, 0, 0, 0};
+    if (px >= 131072 || (ks == 1 && px >= 32768)) return ConvChoice::dma();
     const int ntiles = (cout + 15) / 16;
-    ConvChoice best{2, (need & 2) ? 2 : 1, 1, 8};
+    ConvChoice best = ConvChoice::wave((need & 2) ? 2 : 1, 1, 8);
     long best_reuse = -1, best_waves = -1;
     const int mhs[3] = {4, 2, 1}, wks[3] = {2, 4, 8};
     for (int mh : mhs)
@@ -162,13 +161,58 @@ ConvChoice choose_conv(int ks, int stride, int cin, int cout, int hout, int wout
                 const long waves = (long)B * ((hout + mh - 1) / mh) * ((wout + 15) / 16) * ((ntiles + nt - 1) / nt) * wk;
                 const long reuse = waves >= 2048 ? mh * nt : 0;
                 if (reuse > best_reuse || (reuse == best_reuse && reuse == 0 && waves > best_waves)) {
-                    best = ConvChoice{2, mh, nt, wk};
+                    best = ConvChoice::wave(mh, nt, wk);
                     best_reuse = reuse;
                     best_waves = waves;
                 }
             }
         }
     return best;
+}
+
+S4Shape s4_resolve(int ks, int nt, int tile, int ntiles, int rounds, bool kacc) {
+    nt = nt < 1 ? 1 : (nt > ntiles ? ntiles : nt);
+    if (ks != 3) return {nt > 4 ? 4 : nt, 32, 8, 1};
+    if (kacc) return {nt > 3 ? 3 : nt, 32, 8, 1};   // one workgroup per CU fewer than the plain form: 1 - 3 cout tiles
+    const int nt2 = nt == 1 ? 1 : 2;
+    if (tile == S4_16x32) return {nt2, 32, 16, 1};
+    if (tile == S4_8x32_K4 && rounds >= 16) return {nt2, 32, 8, 4};   // (small images, long K)
+    if (tile >= S4_8x32_K2 && rounds >= 8) return {nt2, 32, 8, 2};
+    if (tile >= S4_8x32_K2 || tile == S4_8x32) return {nt > 4 ? 4 : nt, 32, 8, 1};   // too few rounds to split: plain 8x32
+    if (nt <= 2) return {nt, 64, 8, 1};
+    return {3, 32, 8, 1};   // 3 cout tiles: the 8x64 stages would leave one workgroup per CU
+}
+
+ConvChoice conv_force() { return g_conv_force; }
+
+// pf_debug_force_conv in the inference schedule: (1, ..) and (2, ..) replace the fp32-source kernel of every conv (conv_wave: stride 1),
+// (4, ..) where the plan has the split packing and the kernel the epilogue, (5, nt, tile) puts every eligible conv on conv_s4 with that shape
+// and the others on conv_dma, which can write what those read
+ConvDecision decide_conv(const ConvQuery &q) {
+    const ConvChoice &f = q.force;
+    const bool forced_s4 = f.is(CONV_S4), split_ok = q.has_split && (!q.need || q.ks == 1);
+    ConvDecision d{{CONV_AUTO, 0, 0, 0}, false, 0, 0, {}};
+    ConvChoice &ch = d.ch;
+    if (!q.generic) {
+        ch = choose_conv(q.ks, q.stride, q.cin, q.cout, q.hout, q.wout, q.B, q.need, q.use_tuned);
+        if (f.is(CONV_WAVE) && q.stride == 1) ch = ConvChoice::wave((q.need & 2) && f.wave_mh() == 1 ? 2 : f.wave_mh(), f.wave_nt(), f.wave_wk());
+        if (f.is(CONV_DMA) || (f.is(CONV_SPLIT) && split_ok)) ch = f;
+        if (forced_s4 || (ch.is(CONV_SPLIT) && !(split_ok && q.split_f16))) ch = ConvChoice::dma();
+    }
+    // reads S4: the layers the table gives to the split kernels (same tile parameters), big 1x1 convs, all under a forced conv_s4 -
+    // unless the measured conv_s4 row of the layer decides, and names the shape
+    const bool split = ch.is(CONV_SPLIT);
+    bool want = split || (q.ks == 1 && (long)q.B * q.hout * q.wout >= 32768 && ch.is(CONV_DMA)) || forced_s4;
+    d.s4_nt = forced_s4 ? f.s4_nt() : (q.ks == 1 ? 4 : (split ? ch.split_nt() : 2));
+    d.s4_tile = forced_s4 ? f.s4_tile() : (split ? ch.split_wide() : S4_8x32);
+    ConvChoice row;
+    if (!forced_s4 && !q.generic && q.use_tuned && choose_s4(q.ks, q.cin, q.cout, q.hout, q.wout, q.B, &row)) {
+        want = row.is(CONV_S4);
+        if (want) { d.s4_nt = row.s4_nt(); d.s4_tile = row.s4_tile(); }
+    }
+    d.wants_s4 = want && (forced_s4 || f.is(CONV_AUTO)) && !q.generic && q.stride == 1 && q.has_s4 && (q.need == 0 || q.ks == 1);
+    d.s4 = s4_resolve(q.ks, d.s4_nt, d.s4_tile, (q.cout + 15) / 16, q.rounds, q.kacc);
+    return d;
 }
 
 }  // namespace pf
@@ -196,5 +240,15 @@ extern "C" int pf_debug_probe_read(long long *host64) {
 
 extern "C" int pf_debug_force_conv(int kind, int p0, int p1, int p2) {
     pf::g_conv_force = pf::ConvChoice{kind, p0, p1, p2};
+    return PF_OK;
+}
+
+extern "C" int pf_debug_conv_decision(int ks, int stride, int cin, int cout, int hout, int wout, int B, int need, int flags, int rounds,
+                                      int *out, int cap) {
+    if (!out || cap < 11) return pf::fail(PF_EINVAL, "pf_debug_conv_decision: 11 ints of output");
+    const pf::ConvDecision d = pf::decide_conv({ks, stride, cin, cout, hout, wout, B, need, (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0,
+                                                (flags & 8) != 0, (flags & 16) != 0, (flags & 32) != 0, rounds, pf::conv_force()});
+    const int v[11] = {d.ch.kind, d.ch.p0, d.ch.p1, d.ch.p2, d.wants_s4, d.s4_nt, d.s4_tile, d.s4.NT, d.s4.TW, d.s4.TH, d.s4.KS};
+    for (int i = 0; i < 11; ++i) out[i] = v[i];
     return PF_OK;
 }

@@ -29,8 +29,7 @@ struct Step {
     int ci, need, sb, se;   // op whose weights it runs; need: bit 1 = even tile rows (pooling epilogue), bit 2 = fused stage
     uint32_t src_t[kConvMaxSrc], dst_t;
     bool can_read, can_write, can_write_s4;
-    ConvChoice ch;   // fp32-source kernel (table or pf_debug_force_conv); once picked, the launched kernel's shape
-    int nt, wide;    // conv_s4 shape if it reads S4
+    ConvDecision dec;   // decide_conv: its conv_s4 shape if it reads S4, else dec.ch = its fp32-source kernel (once picked: the launched shape)
     union {
         ConvArgs c; PairArgs pair; PlainArgs x;
         struct { StemArgs stem; FrontArgs front; char front_tag[96]; } sf;
@@ -78,7 +77,7 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
     std::vector<uint8_t> cand(nT, 1);
     std::vector<std::vector<uint8_t>> written(nT);
     for (size_t t = 0; t < nT; ++t) written[t].assign(p->net.tensors[t].channels + 8, 0);
-    const bool s4_allowed = p->opt.packed_acts && p->opt.split_f16 && (g_conv_force.kind == 0 || g_conv_force.kind == 5);
+    const bool s4_allowed = p->opt.packed_acts && p->opt.split_f16 && force_allows_s4();
     // a step stores channels [lo, hi) of tensor t: returns its S4 dst_limit (zero-fill the tail of the last group unless its owner
     // wrote it already)
     auto claim = [&](uint32_t t, int lo, int hi) -> int {
@@ -134,44 +133,19 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
         a.status = status_of(o.dst); a.range_slot = slot_of(ci, o.dst);
         return st;
     };
-    // its fp32-source kernel (conv_select.cpp, pf_debug_force_conv) and what it can read / write as S4
+    // its kernels (conv_select.cpp: decide_conv) and what it can read / write as S4
     auto choose = [&](Step &st, int need) {
         const BlobOp &o = p->net.ops[st.ci];
         const ConvPlan &cp = p->conv[st.ci];
         const ConvArgs &a = st.u.c;
         const bool generic = (a.Win & 3) != 0;
-        ConvChoice ch{0, 0, 0, 0};
-        if (!generic) {
-            ch = choose_conv((int)o.k, (int)o.stride, a.Cin, a.Cout, a.Hout, a.Wout, Bt, need, p->opt.use_tuned_table);
-            if (g_conv_force.kind == 2 && o.stride == 1) {
-                ch = g_conv_force;
-                if ((need & 2) && ch.p0 == 1) ch.p0 = 2;
-            }
-            if (g_conv_force.kind == 1) ch = g_conv_force;
-            if (g_conv_force.kind == 4 && cp.split_off && (!need || o.k == 1)) ch = g_conv_force;
-            if (ch.kind == 4 && (!cp.split_off || (need && o.k != 1) || !p->opt.split_f16)) ch = ConvChoice{1, 0, 0, 0};
-            // pf_debug_force_conv(5, ..): launches that cannot read S4 (fp32 sources) still have to be able to WRITE it
-            if (g_conv_force.kind == 5) ch = ConvChoice{1, 0, 0, 0};
-        }
-        st.ch = ch; st.need = need; st.sb = a.src_begin; st.se = a.src_end;
-        // reads S4: the layers the table gives to the split kernels (same tile parameters), big 1x1 convs, or all
-        // eligible convs under pf_debug_force_conv(5, nt, wide)
-        const bool forced = g_conv_force.kind == 5;
-        const long px = (long)Bt * a.Hout * a.Wout;
-        bool want = ch.kind == 4 || (o.k == 1 && px >= 32768 && ch.kind == 1) || forced;
-        st.nt = forced ? g_conv_force.p0 : (o.k == 1 ? 4 : (ch.kind == 4 ? ch.p0 : 2));
-        st.wide = forced ? g_conv_force.p1 : (ch.kind == 4 ? ch.p1 : 0);
-        ConvChoice s4c;   // measured conv_s4 row of this layer (conv_select.cpp): decides, and names the shape
-        if (!forced && !generic && p->opt.use_tuned_table && choose_s4((int)o.k, a.Cin, a.Cout, a.Hout, a.Wout, Bt, &s4c)) {
-            want = s4c.kind == 5;
-            if (want) { st.nt = s4c.p0; st.wide = s4c.p1; }
-        }
-        const int nt1 = st.nt < 1 ? 1 : (st.nt > a.ntiles ? a.ntiles : st.nt);
-        const bool res_fits = !a.res || (size_t)nt1 * 16 * res_chan_stride(res_extent(8, a.res_sh), res_extent(32, a.res_sw)) * sizeof(float) <= 60 * 1024;
-        st.can_read = s4_allowed && !generic && o.stride == 1 && o.kind == OP_CONV && cp.s4_off && (need == 0 || o.k == 1) && want &&
-                      res_fits && ((a.src_begin == 0 && a.src_end == a.n_src) || cp.s4_pad);
+        st.dec = decide_conv({(int)o.k, (int)o.stride, a.Cin, a.Cout, a.Hout, a.Wout, Bt, need, generic, cp.split_off != 0, cp.s4_off != 0,
+                              p->opt.use_tuned_table != 0, p->opt.split_f16 != 0, false, cp.s4_rounds, conv_force()});
+        st.need = need; st.sb = a.src_begin; st.se = a.src_end;
+        const bool res_fits = !a.res || (size_t)st.dec.s4.NT * 16 * res_chan_stride(res_extent(8, a.res_sh), res_extent(32, a.res_sw)) * sizeof(float) <= 60 * 1024;
+        st.can_read = s4_allowed && o.kind == OP_CONV && st.dec.wants_s4 && res_fits && ((a.src_begin == 0 && a.src_end == a.n_src) || cp.s4_pad);
         st.can_write_s4 = s4_allowed && !generic && (a.dst_choff & 1) == 0;
-        st.can_write = st.can_write_s4 && (ch.kind == 1 || ch.kind == 4);
+        st.can_write = st.can_write_s4 && (st.dec.ch.is(CONV_DMA) || st.dec.ch.is(CONV_SPLIT));
         st.u.c.dst_limit = claim(st.dst_t, a.dst_choff, a.dst_choff + a.Cout);
     };
     // pf_set_option("fuse_upsample", 0/1); at B=4: transUp.3 + conv1x1_up.3 144 us fused vs 233 us as two passes
@@ -207,7 +181,7 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
                         p->readers[o.dst] == 1 && p->readers[n1.dst] == 1 && n1.relu && p->conv[i + 1].s4_off && p->conv[i + 1].s4_rounds == 2 &&
                         n2.kind == OP_CONV && n2.k == 3 && n2.stride == 2 && n2.n_src == 1 && n2.src[0].tensor == n1.dst && n2.src[0].choff == 0 &&
                         n2.src[0].ch == n1.cout && p->conv[i + 2].front_off && (n2.dst_choff & 3) == 0 &&
-                        conv_front_supports((int)o.cout, (int)n1.cout, (int)n2.cout, out.h, out.w, (int)p->net.tensors[n2.dst].channels) && stem_writes_s4(a) && g_conv_force.kind == 0;
+                        conv_front_supports((int)o.cout, (int)n1.cout, (int)n2.cout, out.h, out.w, (int)p->net.tensors[n2.dst].channels) && stem_writes_s4(a) && !conv_forced();
             }
             if (!front) {
                 if (o.cout != 16 || o.k != 3 || o.stride != 2 || o.dst_choff != 0 ||
@@ -385,39 +359,39 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
             a.chunk_begin = a.src_chunk0[a.src_begin];
             a.chunk_end = a.src_chunk0[a.src_end];
         };
-        ConvChoice &ch = st.ch;
-        if (ch.kind == 4) {
+        ConvChoice &ch = st.dec.ch;
+        if (ch.is(CONV_SPLIT)) {
             use(cp.split_off, cp.split_chunks, o.k == 1 ? 32 : 8);
             a.acc_scale = cp.split_acc_scale;
             st.kind = o.k == 1 ? S_CONV_SPLIT1 : S_CONV_SPLIT;
-            if (o.k == 1 ? conv_split1_supported(a, ch.p0) : conv_split_supported(a)) continue;
-            ch = ConvChoice{1, 0, 0, 0};
+            if (o.k == 1 ? conv_split1_supported(a, ch.split_nt()) : conv_split_supported(a)) continue;
+            ch = ConvChoice::dma();
         }
-        if (ch.kind == 2) {
+        if (ch.is(CONV_WAVE)) {
             use(cp.wave_off, cp.wave_chunks, wave_kc((int)o.k));
-            ch.p1 = ch.p1 < a.ntiles ? ch.p1 : a.ntiles;
+            ch = ConvChoice::wave(ch.wave_mh(), ch.wave_nt() < a.ntiles ? ch.wave_nt() : a.ntiles, ch.wave_wk());
             st.kind = S_CONV_WAVE;
-            if (conv_wave_supported(a, (int)o.k, ch.p0, ch.p1, ch.p2)) continue;
-            ch = ConvChoice{1, 0, 0, 0};   // shape not built: conv_dma with its cost model
+            if (conv_wave_supported(a, (int)o.k, ch.wave_mh(), ch.wave_nt(), ch.wave_wk())) continue;
+            ch = ConvChoice::dma();   // shape not built: conv_dma with its cost model
         }
         use(cp.tiled_off, cp.tiled_chunks, dma_kc((int)o.k, (int)o.stride));
         st.kind = S_CONV_DMA;
         // the trailing rem_count output channels of a big image go to the vector ALU instead of an MFMA tile
         // (conv_dma WM=4 shapes only, forced or cost-model-chosen)
         int wm, nt;
-        if (p->opt.valu_remainder && cp.rem_off && !st.need && !a.dst_fmt && a.src_begin == 0 && a.src_end == a.n_src && (ch.p0 == 0 || ch.p0 == 4)) {
+        if (p->opt.valu_remainder && cp.rem_off && !st.need && !a.dst_fmt && a.src_begin == 0 && a.src_end == a.n_src && (ch.dma_wm() == 0 || ch.dma_wm() == 4)) {
             ConvArgs r = a;
             r.rem = cp.rem_count;
             r.wrem = p->dev_weights + cp.rem_off;
             r.ntiles = ((int)o.cout - r.rem) / 16;
-            if (conv_dma_supported(r, (int)o.k, (int)o.stride, B, 4, ch.p0 == 4 && ch.p1 > 0 ? ch.p1 : 0, p->opt.table_batch, &wm, &nt)) {
+            if (conv_dma_supported(r, (int)o.k, (int)o.stride, B, 4, ch.dma_wm() == 4 && ch.dma_nt() > 0 ? ch.dma_nt() : 0, p->opt.table_batch, &wm, &nt)) {
                 a = r;
-                ch = ConvChoice{1, wm, nt, 0};
+                ch = ConvChoice::dma(wm, nt);
                 continue;
             }
         }
-        conv_dma_supported(a, (int)o.k, (int)o.stride, B, ch.p0, ch.p1, p->opt.table_batch, &wm, &nt);   // (no kernel: the launcher says so)
-        ch = ConvChoice{1, wm, nt, 0};
+        conv_dma_supported(a, (int)o.k, (int)o.stride, B, ch.dma_wm(), ch.dma_nt(), p->opt.table_batch, &wm, &nt);   // (no kernel: the launcher says so)
+        ch = ConvChoice::dma(wm, nt);
     }
 
     // ---- 5. an odd HarDBlock layer inside its consumer (conv_pair.hip): two adjacent steps P = op i, C = op i + 1 that both read
@@ -434,7 +408,7 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
         if (!pair || !pair_wanted((int)o.cin, (int)o.cout, (int)p->net.ops[i + 1].cin, (int)p->net.ops[i + 1].cout, d[o.dst].h, d[o.dst].w, Bt,
                                   p->opt.fuse_pairs)) {
             // share / add: 8 x 32 tiles without a K split for both launches, packings made at plan creation
-            if (adjacent && p->opt.share_s && p->conv[i + 1].share_a_off && share_off != (size_t)-1 && steps[k].wide == 0 && steps[k + 1].wide == 0 &&
+            if (adjacent && p->opt.share_s && p->conv[i + 1].share_a_off && share_off != (size_t)-1 && steps[k].dec.s4_tile == S4_8x32 && steps[k + 1].dec.s4_tile == S4_8x32 &&
                 share_wanted((int)o.cin, (int)o.cout, (int)p->net.ops[i + 1].cin, (int)p->net.ops[i + 1].cout, d[o.dst].h, d[o.dst].w, Bt, p->opt.share_s)) {
                 const ConvPlan &cc = p->conv[i + 1];
                 Step sa = steps[k], sb = steps[k + 1];
@@ -443,7 +417,7 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
                 sa.kind = S_CONV_S4_SHARE;
                 a.wpk = p->dev_weights + cc.share_a_off; a.ntiles = cc.share_a_tiles;
                 a.share = sums; a.share_off = share_row0((int)o.cout); a.share_cout = c.Cout; a.share_scale = cc.split_acc_scale;
-                sa.nt = cc.share_a_tiles <= 3 ? cc.share_a_tiles : 2;
+                sa.dec.s4_nt = cc.share_a_tiles <= 3 ? cc.share_a_tiles : 2;
                 // the consumer without its second range S
                 sb.kind = S_CONV_S4_ADD;
                 c.Cin -= c.src_cstart[2] - c.src_cstart[1];
@@ -531,6 +505,7 @@ int run_net(const pf_plan *p, const StemArgs *stem, const float *dense_x, int B,
         if (st.tag[0]) prof_set_tag(st.tag);
         const BlobOp &o = p->net.ops[st.ci];
         ConvArgs &a = st.u.c;   // (the conv kinds)
+        const ConvChoice &ch = st.dec.ch;
         const PlainArgs &x = st.u.x;
         if (is_conv_step(st.kind)) a.probe = probe;
         switch (st.kind) {
@@ -541,14 +516,14 @@ int run_net(const pf_plan *p, const StemArgs *stem, const float *dense_x, int B,
                 if (st.u.sf.front_tag[0]) prof_set_tag(st.u.sf.front_tag);
                 st.u.sf.front.probe = probe; rc = launch_conv_front(st.u.sf.front, B, s); break;
             case S_PAIR: st.u.pair.c.probe = probe; rc = launch_conv_pair(st.u.pair, B, s); break;
-            case S_CONV_S4: rc = launch_conv_s4(a, (int)o.k, st.nt, st.wide, B, s); break;
-            case S_CONV_S4_SHARE: rc = launch_conv_s4_share(a, st.nt, B, s); break;
-            case S_CONV_S4_ADD: rc = launch_conv_s4_add(a, st.nt, B, s); break;
+            case S_CONV_S4: rc = launch_conv_s4(a, (int)o.k, st.dec.s4, B, s); break;
+            case S_CONV_S4_SHARE: rc = launch_conv_s4_share(a, st.dec.s4_nt, B, s); break;
+            case S_CONV_S4_ADD: rc = launch_conv_s4_add(a, st.dec.s4_nt, B, s); break;
             case S_CONV_GENERIC: rc = launch_conv(a, p->conv[st.ci].tiling, B, s); break;
-            case S_CONV_SPLIT: rc = launch_conv_split(a, st.ch.p0, st.ch.p1, B, s); break;
-            case S_CONV_SPLIT1: rc = launch_conv_split1(a, st.ch.p0, B, s); break;
-            case S_CONV_WAVE: rc = launch_conv_wave(a, (int)o.k, st.ch.p0, st.ch.p1, st.ch.p2, B, s); break;
-            case S_CONV_DMA: rc = launch_conv_dma(a, (int)o.k, (int)o.stride, B, s, st.ch.p0, st.ch.p1, p->opt.table_batch); break;
+            case S_CONV_SPLIT: rc = launch_conv_split(a, ch.split_nt(), ch.split_wide(), B, s); break;
+            case S_CONV_SPLIT1: rc = launch_conv_split1(a, ch.split_nt(), B, s); break;
+            case S_CONV_WAVE: rc = launch_conv_wave(a, (int)o.k, ch.wave_mh(), ch.wave_nt(), ch.wave_wk(), B, s); break;
+            case S_CONV_DMA: rc = launch_conv_dma(a, (int)o.k, (int)o.stride, B, s, ch.dma_wm(), ch.dma_nt(), p->opt.table_batch); break;
             case S_POOL: rc = launch_avgpool2(x.src, x.dst, x.planes, x.hin, x.win, x.status, x.slot, s); break;
             case S_UPSAMPLE: rc = launch_upsample(x.src, x.dst, x.planes, x.hin, x.win, x.hout, x.wout, x.status, x.slot, s); break;
             case S_HEAD:

@@ -513,7 +513,8 @@ struct TStep {
     uint8_t stats;       // bit k: the step counts in pf_train_path_stats slot k
     int side, slot;      // side stream of the step (-1: the caller's stream); the dy slot of fork / wait_wg / wg_done
     ConvArgs a;          // conv_dma, conv_s4, pad_gather (the ranges it gathers), wgrad (the forward conv)
-    int ks, stride, wm, nt, wide;   // conv_dma: wm x nt (measure: chosen at enqueue); conv_s4: nt, wide; wgrad: ks, stride
+    int ks, stride, wm, nt;   // conv_dma: wm x nt (measure: chosen at enqueue); wgrad: ks, stride
+    S4Shape s4;          // conv_s4: the instantiation that runs
     int Wp;              // pad_gather: the pitch of the gathered copy and where it goes
     float *gather;
     char tag[64];        // wgrad: profile tag of its launches (set when profiling)
@@ -643,10 +644,10 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<Di
         const std::array<int, 8> key = tune_key(c, ks, stride, B);
         int wm = 0, nt = 0, src = 1;
         const auto it = p->autotune ? p->tuned.find(key) : p->tuned.end();
-        if (g_conv_force.kind == 1 && g_conv_force.p0 > 0) {
+        if (forced_dma_shape(&wm, &nt)) {
             // pf_debug_force_conv(1, wm, nt, 0): every conv_dma step of the schedule with that shape (conv_dma_supported clamps nt to
             // the layer's cout tiles); counted in none of the path statistics' table / cost-model / measured slots
-            wm = g_conv_force.p0, nt = g_conv_force.p1, src = 3;
+            src = 3;
         } else if (it != p->tuned.end()) {
             wm = it->second.first, nt = it->second.second, src = 2;
         } else if (measuring) {
@@ -762,9 +763,10 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<Di
                 c.kacc = (kacc && o.k == 3) ? 1 : 0;      // blocked summation, as in the fp32 step (conv_s4_kernel.inc: KACC)
                 TStep &st = add(T_CONV_S4, 0x80);
                 st.a = c; st.ks = (int)o.k;
-                st.nt = c.ntiles == 3 ? 3 : (c.ntiles < 2 ? 1 : 2);
-                ConvChoice ch4;
-                if (use_tuned && choose_s4((int)o.k, c.Cin, c.Cout, c.Hout, c.Wout, B, &ch4) && ch4.kind == 5) { st.nt = ch4.p0; st.wide = ch4.p1; }
+                int nt = c.ntiles == 3 ? 3 : (c.ntiles < 2 ? 1 : 2), tile = S4_8x32;   // unless the layer's measured row names a shape
+                ConvChoice row;
+                if (use_tuned && choose_s4((int)o.k, c.Cin, c.Cout, c.Hout, c.Wout, B, &row) && row.is(CONV_S4)) { nt = row.s4_nt(); tile = row.s4_tile(); }
+                st.s4 = s4_resolve(st.ks, nt, tile, c.ntiles, c.nchunks, c.kacc != 0);
             }
             float *aux = k.theta + p->aux_off[i], *stat = buf(L.stat[i]);
             add(T_BN_FWD).u.bnf = {y, (int)o.cout, out.h, out.w, k.bn_eps, k.bn_momentum, aux, aux + o.cout,
@@ -934,7 +936,7 @@ int train_pass(const pf_train *p, TCall k, bool measuring) {
             case T_PAD_GATHER: rc = launch_pad_gather(st.a, B, st.Wp, st.gather, s); break;
             case T_CONV_DMA: rc = launch_conv_dma(st.a, st.ks, st.stride, B, s, st.wm, st.nt); break;
             case T_CONV_DMA_MEASURE: rc = tune_conv_dma(p, st.a, st.ks, st.stride, B, s); break;
-            case T_CONV_S4: rc = launch_conv_s4(st.a, st.ks, st.nt, st.wide, B, s); break;
+            case T_CONV_S4: rc = launch_conv_s4(st.a, st.ks, st.s4, B, s); break;
             case T_UNPAD: { const TUnpadArgs &x = u.unpad;
                 rc = launch_unpad_scatter(x.src, B, x.C, x.H, x.W, x.Wp, x.dst, x.ctotal, x.choff, x.accum, s); break; }
             case T_UNPAD_MULTI: { const TUnpadMultiArgs &x = u.unpadm;

@@ -506,6 +506,18 @@ int pf_debug_force_conv(int kind, int p0, int p1, int p2);
  * tile it then asks for, and NT, TW, TH, KS of the conv_s4 instantiation that request runs (s4_resolve). */
 int pf_debug_conv_decision(int ks, int stride, int cin, int cout, int hout, int wout, int B, int need, int flags, int rounds,
                            int *out, int cap);
+/* Host only, no device involved, nothing enqueued (tests): the range tables of one launch of a convolution that reads n_src (1..4) channel
+ * ranges - range j = channels [choff[j], choff[j] + ch[j]) of a tensor of ctotal[j] channels - as the packers and the schedules take them from
+ * csrc/conv_ranges.cpp; n_cases convolutions per call: choff, ch, ctotal = [n_cases][4] ints, out = [n_cases][39] (cap ints, >= 39 * n_cases).
+ * form: 0 = the op's ranges as they are, 1 = the consumer of a conv_pair launch ([S, others.., P], P at channel 0 of its own planes),
+ * 2 = the add launch (without S, the op's range 1); forms 1 and 2 need n_src >= 2.  kc > 0: the tables of a kernel family
+ * that walks chunks of kc input channels; kc = 0: the packed-pair tables of a ks x ks conv (ks 1 or 3), pad = every range padded to whole
+ * rounds.  0 <= src_begin < src_end <= the launch's ranges: the ranges it accumulates (else all of them).  Per case: [0] ranges of
+ * the launch, [1] its chunks (kc > 0) or rounds, [2..5] which range of the op each is, [6..10] src_cstart, [11..14] each range's first input
+ * channel in the op's weight numbering, [15..19] src_chunk0, [20..23] src_c4, [24..27] src_g0, [28..31] src_gn, [32..36] src_ent0,
+ * [37] chunk_begin, [38] chunk_end; what the chosen tables do not fill is 0. */
+int pf_debug_conv_ranges(int form, int ks, int kc, int pad, int n_src, int n_cases, const int *choff, const int *ch, const int *ctotal,
+                         int src_begin, int src_end, int *out, size_t cap);
 /* Host only, no device involved (tests): the weight arena a plan created now from this blob would upload - every packing of every
  * convolution under the process-wide options - copied to out when cap >= *n_floats, and per op of the table (table_ops rows of six
  * numbers, nullable): offset in floats and rounds of its packed-pair packing, offset and cout tiles of its share launch's packing,

@@ -569,13 +569,6 @@ void pack_conv_weights_rem(const float *w, int cin, int cout, int rem, int ks, i
     }
 }
 
-int dma_chunks(const int *src_ch, int n_src, int ks, int stride) {
-    const int kc = dma_kc(ks, stride);
-    int n = 0;
-    for (int j = 0; j < n_src; ++j) n += (src_ch[j] + kc - 1) / kc;
-    return n;
-}
-
 // per-tile packing: [cout tile][chunk][kgroup][tap][64 lanes]; K order = the input ranges in order, each padded to
 // whole chunks (zero weights), so a chunk never straddles two source tensors
 void pack_conv_weights_tiled(const float *w, int cin, int cout, int ks, int kc, const int *src_ch, int n_src, float *out) {

@@ -228,7 +228,6 @@ int launch_conv(const ConvArgs &a, const ConvTiling &t, int B, hipStream_t strea
 // a.nchunks = ceil(Cin / kc) with kc = dma_kc(ks, stride) input channels per double-buffered stage.
 constexpr int dma_kc_ct(int ks, int stride) { return ks == 1 ? 16 : (stride == 2 ? 4 : 8); }
 inline int dma_kc(int ks, int stride) { return dma_kc_ct(ks, stride); }
-int dma_chunks(const int *src_ch, int n_src, int ks, int stride);
 // conv_dma's vector-ALU cout path: the last `rem` (1..16) output channels; accumulators rv in {2,4,8,12,16} >= rem
 inline int dma_rem_rv(int rem) { return rem <= 2 ? 2 : (rem + 3) / 4 * 4; }
 // how many trailing output channels of a 3x3/s1 conv go to the vector ALU (0 = none): the partial tile
@@ -248,8 +247,7 @@ bool conv_dma_supported(const ConvArgs &a, int ks, int stride, int B, int force_
 // output and a.nchunks = ceil(Cin / wave_kc(ks)).  Tile = mh rows x 16 pixels, nt cout tiles, wk-way K split.
 constexpr int wave_kc_ct(int ks) { return ks == 1 ? 32 : 8; }
 inline int wave_kc(int ks) { return wave_kc_ct(ks); }
-// src_ch[n_src]: channels of each input range (sum = cin); K order = ranges in order, each padded to whole chunks
-int wave_chunks(const int *src_ch, int n_src, int ks);
+// src_ch[n_src]: channels of each input range (sum = cin); K order = ranges in order, each padded to whole chunks (conv_ranges.h)
 void pack_conv_weights_wave(const float *w_oihw, int cin, int cout, int ks, const int *src_ch, int n_src, float *out);
 size_t wave_packed_floats(const int *src_ch, int n_src, int cout, int ks);
 int launch_conv_wave(const ConvArgs &a, int ks, int mh, int nt, int wk, int B, hipStream_t stream);
@@ -265,13 +263,11 @@ constexpr size_t wave_lds_bytes(int ks, int mh, int nt, int wk) {
 // split path (conv_split.hip; 3x3/s1, Wout % 4 == 0, no fused epilogue; two fp16 terms per operand, see split_terms2
 // above): a.wpk must point at pack_conv_weights_split() output, chunks of 8 channels; the packers take the weights
 // ALREADY multiplied by split_weight_scale() and a.acc_scale = 1 / that scale.
-int split_chunks(const int *src_ch, int n_src);
 size_t split_packed_floats(const int *src_ch, int n_src, int cout);
 void pack_conv_weights_split(const float *w_oihw, int cin, int cout, const int *src_ch, int n_src, float *out);
 int launch_conv_split(const ConvArgs &a, int nt, int wide, int B, hipStream_t stream);
 bool conv_split_supported(const ConvArgs &a);   // launch_conv_split has a kernel for this launch
 // 1x1/s1 on the same scheme (chunks of 32 channels; pack_conv_weights_split1()); supports the fused epilogue stages
-int split1_chunks(const int *src_ch, int n_src);
 size_t split1_packed_floats(const int *src_ch, int n_src, int cout);
 void pack_conv_weights_split1(const float *w_oihw, int cin, int cout, const int *src_ch, int n_src, float *out);
 int launch_conv_split1(const ConvArgs &a, int nt, int B, hipStream_t stream);
@@ -281,11 +277,11 @@ bool conv_split1_supported(const ConvArgs &a, int nt);   // ... and launch_conv_
 // phase.  K order = the group entries of the ranges in order, two entries (8 channels) per 3x3 round, eight (32 channels)
 // per 1x1 round; weights of channels a range does not own inside its first/last group are zero.
 struct S4Range { int choff, ch; };   // a source range in the channel numbering of its tensor
+struct KOrder;   // the ranges of a launch in K order with their starts in the conv's input-channel numbering (conv_ranges.h, which counts
+                 // the entries and rounds): they may be packed in ANOTHER order than the one they are concatenated in (conv_pair.hip)
 // pad_sources: every range padded to whole rounds (convs that may be launched one range at a time)
-int s4_entries(const S4Range *r, int n_src, int ks, int pad_sources);
-int s4_rounds(const S4Range *r, int n_src, int ks, int pad_sources);
-size_t s4_packed_floats(const S4Range *r, int n_src, int cout, int ks, int pad_sources);
-void pack_conv_weights_s4(const float *w_oihw, int cin, int cout, int ks, const S4Range *r, int n_src, int pad_sources, float *out);
+size_t s4_packed_floats(const KOrder &k, int cout, int ks, int pad_sources);
+void pack_conv_weights_s4(const float *w_oihw, int cin, int cout, int ks, const KOrder &k, int pad_sources, float *out);
 // the pixel tile a 3x3 launch is asked for: 8x32, 8x64, 16x32 on 8 waves, 8x32 with 2 / 4 wave groups splitting the rounds.  The values
 // are the ABI of pf_debug_force_conv(5, nt, tile, 0) and the contents of conv_s4_tuned.inc
 enum S4Tile : int { S4_8x32 = 0, S4_8x64 = 1, S4_16x32 = 2, S4_8x32_K2 = 3, S4_8x32_K4 = 4 };
@@ -303,9 +299,6 @@ int launch_conv_s4_share(const ConvArgs &a, int nt, int B, hipStream_t stream);
 int launch_conv_s4_add(const ConvArgs &a, int nt, int B, hipStream_t stream);
 inline int share_row0(int p_cout) { return (p_cout + 3) / 4 * 4; }   // a lane's four couts never straddle the two convs
 bool share_wanted(int p_cin, int p_cout, int c_cin, int c_cout, int h, int w, int B, int mode);
-// the same with an explicit start of every range in the conv's input-channel numbering (cstart[j]; nullptr = the ranges are
-// consecutive): ranges may then be packed in ANOTHER order than the one they are concatenated in (conv_pair.hip)
-void pack_conv_weights_s4_ex(const float *w_oihw, int cin, int cout, int ks, const S4Range *r, const int *cstart, int n_src, int pad_sources, float *out);
 
 // conv_pair.hip: an odd HarDBlock layer P = conv3x3(S) computed inside its consumer C = conv3x3(P ++ S ++ others) (hardnet.py:177-194)
 struct PairArgs {

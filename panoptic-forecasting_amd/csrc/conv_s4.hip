@@ -31,6 +31,7 @@
 #include <cstring>
 #include <vector>
 
+#include "conv_ranges.h"
 #include "conv_s4.h"
 #include "pf_prof.h"
 
@@ -569,21 +570,8 @@ int launch_conv_s4(const ConvArgs &a, int ks, const S4Shape &sh, int B, hipStrea
 }
 
 // ------------------------------------------------------------------------------------------------ host side: weights
-// group entries of range j; with pad_sources every range is padded to whole rounds (convs that may run one range at a
-// time: the two halves of a commuted upsample + 1x1, hardnet_plan.hip)
-static int s4_range_groups(const S4Range &r) { return (r.choff + r.ch + 3) / 4 - r.choff / 4; }
-int s4_entries(const S4Range *r, int n_src, int ks, int pad_sources) {
-    const int per = ks == 3 ? 2 : 8;
-    int n = 0;
-    for (int j = 0; j < n_src; ++j) n += pad_sources ? (s4_range_groups(r[j]) + per - 1) / per * per : s4_range_groups(r[j]);
-    return n;
-}
-int s4_rounds(const S4Range *r, int n_src, int ks, int pad_sources) {
-    const int per = ks == 3 ? 2 : 8;
-    return (s4_entries(r, n_src, ks, pad_sources) + per - 1) / per;
-}
-size_t s4_packed_floats(const S4Range *r, int n_src, int cout, int ks, int pad_sources) {
-    const int rounds = s4_rounds(r, n_src, ks, pad_sources);
+size_t s4_packed_floats(const KOrder &k, int cout, int ks, int pad_sources) {
+    const int rounds = s4_rounds(k, ks, pad_sources);
     return (size_t)((cout + 15) / 16) * (ks == 3 ? s4_blocks_total(rounds) : rounds) * 2 * 64 * 4;
 }
 
@@ -591,29 +579,24 @@ size_t s4_packed_floats(const S4Range *r, int n_src, int cout, int ks, int pad_s
 // of two group entries.  1x1: [tile][round], g = entry pair of the round.  3x3: [tile][per round: instr 0, instr 1, and after
 // every 4th (and the last) round the collected-tap block]; instr blocks: g = tap, entries of the round; collected block:
 // g = round 4q + g of its group of four, tap (2,2)
-void pack_conv_weights_s4(const float *w, int cin, int cout, int ks, const S4Range *r, int n_src, int pad_sources, float *out_f) {
-    pack_conv_weights_s4_ex(w, cin, cout, ks, r, nullptr, n_src, pad_sources, out_f);
-}
-void pack_conv_weights_s4_ex(const float *w, int cin, int cout, int ks, const S4Range *r, const int *cstart, int n_src, int pad_sources, float *out_f) {
+void pack_conv_weights_s4(const float *w, int cin, int cout, int ks, const KOrder &k, int pad_sources, float *out_f) {
     unsigned short *out = reinterpret_cast<unsigned short *>(out_f);
     // entry -> (first conv input channel of the group's channel 0, may be negative; valid channel window)
     std::vector<int> ent_c0, ent_lo, ent_hi;
-    const int per = ks == 3 ? 2 : 8;
-    int c0 = 0;
-    for (int j = 0; j < n_src; ++j) {
-        if (cstart) c0 = cstart[j];
-        const int g0 = r[j].choff / 4, g1 = (r[j].choff + r[j].ch + 3) / 4;
-        for (int g = g0; g < g1; ++g) {
-            ent_c0.push_back(c0 + 4 * g - r[j].choff);
-            ent_lo.push_back(c0);
-            ent_hi.push_back(c0 + r[j].ch);
+    const int per = s4_per_round(ks);
+    for (int j = 0; j < k.n; ++j) {
+        const KRange &r = k.r[j];
+        const int g0 = r.choff / 4;
+        for (int g = g0; g < g0 + s4_range_groups(r.choff, r.ch); ++g) {
+            ent_c0.push_back(r.cstart + 4 * g - r.choff);
+            ent_lo.push_back(r.cstart);
+            ent_hi.push_back(r.cstart + r.ch);
         }
         while (pad_sources && ent_c0.size() % per != 0) {   // padding entry: no valid channel
             ent_c0.push_back(0);
             ent_lo.push_back(0);
             ent_hi.push_back(0);
         }
-        c0 += r[j].ch;
     }
     const int n_ent = (int)ent_c0.size(), rounds = (n_ent + per - 1) / per, ntiles = (cout + 15) / 16;
     size_t o = 0;

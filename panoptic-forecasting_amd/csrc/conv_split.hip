@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "conv_epilogue.h"
+#include "conv_ranges.h"
 #include "pf_prof.h"
 
 #ifndef PF_PROBE
@@ -564,15 +565,9 @@ int launch_conv_split1(const ConvArgs &a, int nt, int B, hipStream_t s) {
     return PF_EUNSUPPORTED;
 }
 
-int split1_chunks(const int *src_ch, int n_src) {
-    int n = 0;
-    for (int j = 0; j < n_src; ++j) n += (src_ch[j] + 31) / 32;
-    return n;
-}
-
 // bytes as floats: [tile][chunk of 32 ch][term 2][lane 64][8 fp16]; lane = (cout n = lane & 15, k-group lane >> 4)
 size_t split1_packed_floats(const int *src_ch, int n_src, int cout) {
-    return (size_t)((cout + 15) / 16) * split1_chunks(src_ch, n_src) * 2 * 64 * 4;
+    return (size_t)((cout + 15) / 16) * range_chunks(src_ch, n_src, 32) * 2 * 64 * 4;
 }
 
 void pack_conv_weights_split1(const float *w, int cin, int cout, const int *src_ch, int n_src, float *out_f) {
@@ -637,15 +632,9 @@ float split_weight_scale(const float *w, size_t n) {
     return ldexpf(1.0f, 15 - e);             // mx * 2^(15 - e) in [2^14, 2^15)
 }
 
-int split_chunks(const int *src_ch, int n_src) {
-    int n = 0;
-    for (int j = 0; j < n_src; ++j) n += (src_ch[j] + 7) / 8;
-    return n;
-}
-
 // bytes as floats (the weight arena is a float array): [tile][chunk][step 3][term 2][lane 64][8 fp16] = 16 B per lane
 size_t split_packed_floats(const int *src_ch, int n_src, int cout) {
-    return (size_t)((cout + 15) / 16) * split_chunks(src_ch, n_src) * 3 * 2 * 64 * 4;
+    return (size_t)((cout + 15) / 16) * range_chunks(src_ch, n_src, 8) * 3 * 2 * 64 * 4;
 }
 
 void pack_conv_weights_split(const float *w, int cin, int cout, const int *src_ch, int n_src, float *out_f) {

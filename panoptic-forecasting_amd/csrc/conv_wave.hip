@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "conv_epilogue.h"
+#include "conv_ranges.h"
 #include "pf_prof.h"
 
 #ifndef PF_PROBE
@@ -366,13 +367,6 @@ int launch_conv_wave(const ConvArgs &a, int ks, int mh, int nt, int wk, int B, h
     return PF_EUNSUPPORTED;   // (unreachable: conv_wave_supported)
 }
 
-int wave_chunks(const int *src_ch, int n_src, int ks) {
-    const int kc = wave_kc(ks);
-    int n = 0;
-    for (int j = 0; j < n_src; ++j) n += (src_ch[j] + kc - 1) / kc;
-    return n;
-}
-
 // fragment-order packing for direct L2 -> VGPR loads, per (cout tile, chunk): [quad][64 lanes][4] then the
 // remainder [64 lanes][NR];  value idx = q*4+e (or 4*NQ+e) -> (kg, tap) = (idx / ks2, idx % ks2):
 //   W[t*16 + (lane&15)][first channel of the chunk + kg*4 + (lane>>4)][tap]
@@ -403,7 +397,7 @@ void pack_conv_weights_wave(const float *w, int cin, int cout, int ks, const int
 
 size_t wave_packed_floats(const int *src_ch, int n_src, int cout, int ks) {
     const int kc = wave_kc(ks), nv = (kc / 4) * ks * ks;
-    return (size_t)((cout + 15) / 16) * wave_chunks(src_ch, n_src, ks) * ((nv / 4) * 256 + (nv % 4) * 64);
+    return (size_t)((cout + 15) / 16) * range_chunks(src_ch, n_src, kc) * ((nv / 4) * 256 + (nv % 4) * 64);
 }
 
 }  // namespace pf

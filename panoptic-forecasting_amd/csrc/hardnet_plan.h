@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "conv_epilogue.h"
+#include "conv_ranges.h"
 #include "net_kernels.h"
 #include "pf_net.h"
 

@@ -53,6 +53,7 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
     auto tptr = [&](uint32_t t) -> float * {
         return t == input ? const_cast<float *>(dense_x) : reinterpret_cast<float *>((char *)ws + off[t]);
     };
+    auto tref = [&](uint32_t t) { return TensorRef{tptr(t), (int)p->net.tensors[t].channels}; };
 
     // option "profile_tag_ops" (per plan, or process-wide for tools that switch it on late): per-op labels in pf_profile_* records
     const bool tags = (p->opt.profile_tag_ops != 0 || g_plan_opt.profile_tag_ops != 0) && prof_enabled();
@@ -104,22 +105,14 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
         if (tags) snprintf(st.tag, sizeof(st.tag), "%02zu %s %u->%u %dx%d", i, p->net.tensors[o.dst].name, o.cin, o.cout, out.h, out.w);
         return st;
     };
-    // a step of op i running convolution ci
-    auto conv_step = [&](size_t i, size_t ci, const Dims &in, const Dims &out) -> Step & {
+    // a step of op i running convolution ci over the ranges ko
+    auto conv_step = [&](size_t i, size_t ci, const KOrder &ko, const Dims &in, const Dims &out) -> Step & {
         Step &st = push(S_CONV, i);
         const BlobOp &o = p->net.ops[ci];
         ConvArgs &a = st.u.c;
         st.ci = (int)ci; st.dst_t = o.dst;
-        a.n_src = (int)o.n_src;
-        int c0 = 0;
-        for (int j = 0; j < a.n_src; ++j) {
-            a.src[j] = tptr((st.src_t[j] = o.src[j].tensor));
-            a.src_ctotal[j] = (int)p->net.tensors[o.src[j].tensor].channels;
-            a.src_choff[j] = (int)o.src[j].choff;
-            a.src_cstart[j] = c0;
-            c0 += (int)o.src[j].ch;
-        }
-        for (int j = a.n_src; j <= kConvMaxSrc; ++j) a.src_cstart[j] = c0;
+        set_sources(a, ko, tref);
+        for (int j = 0; j < ko.n; ++j) st.src_t[j] = ko.r[j].tensor;
         a.bias = p->dev_weights + p->conv[ci].bias_off;
         a.dst = tptr(o.dst);
         a.dst_ctotal = (int)p->net.tensors[o.dst].channels; a.dst_choff = (int)o.dst_choff;
@@ -128,7 +121,6 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
         a.relu = (int)o.relu;
         a.zero_page = p->dev_weights;   // first 64 floats of the weight arena are zeros
         a.ntiles = ((int)o.cout + 15) / 16;
-        a.src_end = a.n_src;
         a.acc_scale = 1.0f;
         a.status = status_of(o.dst); a.range_slot = slot_of(ci, o.dst);
         return st;
@@ -230,7 +222,7 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
                 p->net.ops[i + 1].src[0].tensor == o.dst && o.dst_choff == 0 && o.cout == p->net.tensors[o.dst].channels &&
                 p->readers[o.dst] == 1 && out.h >= 2 && out.w >= 2)
                 pool = &p->net.ops[i + 1];
-            Step &st = conv_step(i, i, in, out);
+            Step &st = conv_step(i, i, order_plain(o.src, (int)o.n_src), in, out);
             if (pool) {
                 ConvArgs &a = st.u.c;
                 a.pool = 1; a.dst = tptr(pool->dst); a.dst_ctotal = (int)p->net.tensors[pool->dst].channels;
@@ -249,11 +241,11 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
                     snprintf(st.tag, sizeof(st.tag), "%02zu%c %s.%s %d->%u %dx%d", i + 1, half[0] == 'l' ? 'a' : 'b', p->net.tensors[n.dst].name,
                              half, cin, n.cout, dd.h, dd.w);
             };
-            Step &ls = conv_step(i, i + 1, in, in);
+            const KOrder kn = order_plain(n.src, (int)n.n_src);
+            KOrder kx = kn;                                    // range 0: x at the low resolution
+            kx.r[0].tensor = o.src[0].tensor; kx.r[0].choff = (int)o.src[0].choff;
+            Step &ls = conv_step(i, i + 1, kx, in, in);
             ConvArgs &lo = ls.u.c;
-            lo.src[0] = tptr(o.src[0].tensor);                 // x at the low resolution
-            ls.src_t[0] = o.src[0].tensor;
-            lo.src_ctotal[0] = (int)p->net.tensors[o.src[0].tensor].channels; lo.src_choff[0] = (int)o.src[0].choff;
             lo.dst = tptr(o.dst);                              // scratch: the slot of the (never built) upsampled tensor
             ls.dst_t = o.dst;
             lo.dst_ctotal = (int)n.cout; lo.dst_choff = 0;
@@ -263,7 +255,7 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
             lo.src_end = 1;
             tag_half(ls, "lo", lo.Cin, in);
             choose(ls, 4);
-            Step &hs = conv_step(i, i + 1, hi, hi);
+            Step &hs = conv_step(i, i + 1, kn, hi, hi);
             ConvArgs &ha = hs.u.c;
             ha.Cin = (int)n.src[1].ch;
             ha.src_begin = 1; ha.src_end = 2;
@@ -328,21 +320,9 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
         bool s4 = st.can_read;
         for (int j = st.sb; j < st.se; ++j) s4 = s4 && fmt[st.src_t[j]];
         if (s4) {
-            const int per = o.k == 3 ? 2 : 8;
-            int e = 0;
-            for (int j = 0; j < a.n_src; ++j) {
-                const int ch0 = a.src_choff[j], chn = a.src_cstart[j + 1] - a.src_cstart[j];
-                a.src_c4[j] = (a.src_ctotal[j] + 3) / 4;
-                a.src_g0[j] = ch0 / 4;
-                a.src_gn[j] = (ch0 + chn + 3) / 4 - ch0 / 4;
-                a.src_ent0[j] = e;
-                e += cp.s4_pad ? (a.src_gn[j] + per - 1) / per * per : a.src_gn[j];
-            }
-            for (int j = a.n_src; j <= kConvMaxSrc; ++j) a.src_ent0[j] = e;
             a.src_fmt = 1; a.acc_scale = cp.split_acc_scale;
             a.wpk = p->dev_weights + cp.s4_off; a.nchunks = cp.s4_rounds;
-            a.chunk_begin = a.src_ent0[a.src_begin] / per;
-            a.chunk_end = (a.src_ent0[a.src_end] + per - 1) / per;
+            set_s4_entries(a, (int)o.k, cp.s4_pad);
             st.kind = S_CONV_S4; continue;
         }
         if ((a.Win & 3) != 0) {
@@ -353,11 +333,7 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
         auto use = [&](size_t wpk_off, int nchunks, int kc) {   // a packing of the weights in chunks of kc input channels
             a.wpk = p->dev_weights + wpk_off;
             a.nchunks = nchunks;
-            a.src_chunk0[0] = 0;
-            for (int j = 0; j < kConvMaxSrc; ++j)
-                a.src_chunk0[j + 1] = a.src_chunk0[j] + (j < a.n_src ? ((int)o.src[j].ch + kc - 1) / kc : 0);
-            a.chunk_begin = a.src_chunk0[a.src_begin];
-            a.chunk_end = a.src_chunk0[a.src_end];
+            set_chunks(a, kc);
         };
         ConvChoice &ch = st.dec.ch;
         if (ch.is(CONV_SPLIT)) {
@@ -420,20 +396,10 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
                 sa.dec.s4_nt = cc.share_a_tiles <= 3 ? cc.share_a_tiles : 2;
                 // the consumer without its second range S
                 sb.kind = S_CONV_S4_ADD;
-                c.Cin -= c.src_cstart[2] - c.src_cstart[1];
-                for (int j = 1; j + 1 < c.n_src; ++j) {
-                    c.src[j] = c.src[j + 1]; c.src_ctotal[j] = c.src_ctotal[j + 1]; c.src_choff[j] = c.src_choff[j + 1];
-                    c.src_c4[j] = c.src_c4[j + 1]; c.src_g0[j] = c.src_g0[j + 1]; c.src_gn[j] = c.src_gn[j + 1];
-                }
-                --c.n_src;
-                int e = 0;
-                for (int j = 0; j <= kConvMaxSrc; ++j) {
-                    c.src_ent0[j] = e;
-                    if (j < c.n_src) e += c.src_gn[j];
-                }
-                c.src_end = c.n_src;
+                set_sources(c, order_add(p->net.ops[i + 1].src, (int)p->net.ops[i + 1].n_src), tref);
+                c.Cin = c.src_cstart[c.n_src];
                 c.wpk = p->dev_weights + cc.share_b_off; c.nchunks = cc.share_b_rounds;
-                c.chunk_begin = 0; c.chunk_end = c.nchunks;
+                set_s4_entries(c, 3, 0);
                 c.share = sums; c.share_cout = c.Cout;
                 steps[w] = sa;
                 steps[++w] = sb;
@@ -443,8 +409,7 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
             if (w != k) steps[w] = steps[k];
             continue;
         }
-        // the consumer's S4 launch (pa.c) with its sources in the K order [S, others.., P]: source j of the launch = source (j + 1) % n
-        // of the op
+        // the consumer's S4 launch (pa.c) with its sources in the pair's K order [S, others.., P]
         const BlobOp &C = p->net.ops[i + 1];
         Step st = steps[k + 1];
         st.kind = S_PAIR; st.op = (int)i;
@@ -454,22 +419,9 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
         PairArgs &pa = st.u.pair;
         ConvArgs &a = pa.c;
         const int n = (int)C.n_src;
-        int e = 0;
-        for (int j = 0; j < n; ++j) {
-            const BlobSrc &sj = C.src[(j + 1) % n];
-            const bool isP = j == n - 1;
-            a.src[j] = tptr(sj.tensor);
-            a.src_ctotal[j] = (int)p->net.tensors[sj.tensor].channels;
-            a.src_choff[j] = (int)sj.choff;
-            a.src_c4[j] = (a.src_ctotal[j] + 3) / 4;
-            a.src_g0[j] = isP ? 0 : (int)sj.choff / 4;
-            a.src_gn[j] = isP ? ((int)sj.ch + 3) / 4 : ((int)sj.choff + (int)sj.ch + 3) / 4 - (int)sj.choff / 4;
-            a.src_ent0[j] = e;
-            e += (a.src_gn[j] + 1) / 2 * 2;
-        }
-        for (int j = n; j <= kConvMaxSrc; ++j) a.src_ent0[j] = e;
-        a.chunk_begin = a.chunk_end = 0;
+        set_sources(a, order_pair(C.src, n), tref);
         a.wpk = p->dev_weights + p->conv[i + 1].pair_c_off; a.nchunks = p->conv[i + 1].pair_rounds;
+        set_s4_entries(a, 3, 1);
         pa.p_wpk = p->dev_weights + p->conv[i + 1].pair_two_off; pa.p_w9 = p->dev_weights + p->conv[i + 1].pair_nine_off;
         pa.p_bias = p->dev_weights + p->conv[i].bias_off; pa.p_acc_scale = p->conv[i].split_acc_scale;
         pa.p_dst = tptr(o.dst); pa.p_dst_c4 = ((int)p->net.tensors[o.dst].channels + 3) / 4;

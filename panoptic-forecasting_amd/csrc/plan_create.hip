@@ -215,7 +215,7 @@ void pack_generic(const BlobOp &o, const float *w, const float *bias, Arena &a, 
 
 void pack_dma(const BlobOp &o, const float *w, const int *src_ch, Arena &a, ConvPlan &c) {
     const int kc = dma_kc((int)o.k, (int)o.stride);
-    c.tiled_chunks = dma_chunks(src_ch, (int)o.n_src, (int)o.k, (int)o.stride);
+    c.tiled_chunks = range_chunks(src_ch, (int)o.n_src, kc);
     c.tiled_off = a.take((size_t)((o.cout + 15) / 16) * c.tiled_chunks * (kc / 4) * o.k * o.k * 64);
     pack_conv_weights_tiled(w, (int)o.cin, (int)o.cout, (int)o.k, kc, src_ch, (int)o.n_src, a.at(c.tiled_off));
     // trailing couts that may run on the vector ALU beside the MFMA tiles (conv_dma.hip): groups of at most valu_max (beyond
@@ -239,43 +239,32 @@ float scale_weights(const float *w, size_t n, std::vector<float> &ws) {
 
 void pack_split(const BlobOp &o, const float *ws, const int *src_ch, Arena &a, ConvPlan &c) {   // stride 1: 3x3 or 1x1
     if (o.k == 3) {
-        c.split_chunks = split_chunks(src_ch, (int)o.n_src);
+        c.split_chunks = range_chunks(src_ch, (int)o.n_src, 8);
         c.split_off = a.take(split_packed_floats(src_ch, (int)o.n_src, (int)o.cout), 16);
         pack_conv_weights_split(ws, (int)o.cin, (int)o.cout, src_ch, (int)o.n_src, a.at(c.split_off));
     } else {
-        c.split_chunks = split1_chunks(src_ch, (int)o.n_src);
+        c.split_chunks = range_chunks(src_ch, (int)o.n_src, 32);
         c.split_off = a.take(split1_packed_floats(src_ch, (int)o.n_src, (int)o.cout), 16);
         pack_conv_weights_split1(ws, (int)o.cin, (int)o.cout, src_ch, (int)o.n_src, a.at(c.split_off));
     }
 }
 
 void pack_s4(const BlobOp &o, const float *ws, Arena &a, ConvPlan &c) {   // stride 1; none if a range starts at an odd channel
-    S4Range rg[kConvMaxSrc];
-    for (uint32_t j = 0; j < o.n_src; ++j) {
-        rg[j] = S4Range{(int)o.src[j].choff, (int)o.src[j].ch};
+    for (uint32_t j = 0; j < o.n_src; ++j)
         if (o.src[j].choff & 1) return;
-    }
+    const KOrder ko = order_plain(o.src, (int)o.n_src);
     c.s4_pad = o.k == 1 && o.n_src == 2;
-    c.s4_rounds = s4_rounds(rg, (int)o.n_src, (int)o.k, c.s4_pad);
-    c.s4_off = a.take(s4_packed_floats(rg, (int)o.n_src, (int)o.cout, (int)o.k, c.s4_pad), 16);
-    pack_conv_weights_s4(ws, (int)o.cin, (int)o.cout, (int)o.k, rg, (int)o.n_src, c.s4_pad, a.at(c.s4_off));
+    c.s4_rounds = s4_rounds(ko, (int)o.k, c.s4_pad);
+    c.s4_off = a.take(s4_packed_floats(ko, (int)o.cout, (int)o.k, c.s4_pad), 16);
+    pack_conv_weights_s4(ws, (int)o.cin, (int)o.cout, (int)o.k, ko, c.s4_pad, a.at(c.s4_off));
 }
 
-// conv_pair.hip: o is the consumer C of a pair, P its producer (the op before it).  C's weights in the K order [S, others.., P], every
-// range padded to whole rounds, P's range declared at channel 0 of its own planes; P's weights (wP: unscaled) as two-instruction
-// rounds + a ninth-tap stream, scaled by P's own 2^k
+// conv_pair.hip: o is the consumer C of a pair, P its producer (the op before it).  C's weights in the pair's K order (order_pair), every
+// range padded to whole rounds; P's weights (wP: unscaled) as two-instruction rounds + a ninth-tap stream, scaled by P's own 2^k
 void pack_pair(const BlobOp &P, const float *wP, const BlobOp &o, const float *ws, Arena &a, ConvPlan &c) {
-    const int n = (int)o.n_src;
-    S4Range rg[kConvMaxSrc];
-    int cstart[kConvMaxSrc], c0s[kConvMaxSrc], acc0 = 0;
-    for (int j = 0; j < n; ++j) { c0s[j] = acc0; acc0 += (int)o.src[j].ch; }
-    for (int j = 0; j < n; ++j) {
-        const int sj = (j + 1) % n;
-        rg[j] = sj == 0 ? S4Range{0, (int)o.src[0].ch} : S4Range{(int)o.src[sj].choff, (int)o.src[sj].ch};
-        cstart[j] = c0s[sj];
-    }
-    c.pair_rounds = s4_rounds(rg, n, 3, 1);
-    c.pair_c_off = a.take(s4_packed_floats(rg, n, (int)o.cout, 3, 1), 16);
+    const KOrder ko = order_pair(o.src, (int)o.n_src);
+    c.pair_rounds = s4_rounds(ko, 3, 1);
+    c.pair_c_off = a.take(s4_packed_floats(ko, (int)o.cout, 3, 1), 16);
     std::vector<float> wp;
     scale_weights(wP, (size_t)P.cout * P.cin * 9, wp);
     c.pair_merged = conv_pair_merged_supports((int)o.cout, (int)P.cout);
@@ -283,15 +272,15 @@ void pack_pair(const BlobOp &P, const float *wP, const BlobOp &o, const float *w
         // P's couts ride in the rows C's last cout tile pads with zeros (from the next multiple of four on), over the columns of
         // S: C's matrix instructions over S then produce P at the tile's own pixels for nothing.  Harmless for the plain kernel
         // (its epilogue never looks at those rows)
-        const int nt = ((int)o.cout + 15) / 16, row0 = ((int)o.cout + 3) / 4 * 4, cS = c0s[1 % n];
+        const int nt = ((int)o.cout + 15) / 16, row0 = ((int)o.cout + 3) / 4 * 4, cS = ko.r[0].cstart;   // (S leads the order)
         std::vector<float> waug((size_t)nt * 16 * o.cin * 9, 0.f);
         std::copy(ws, ws + (size_t)o.cout * o.cin * 9, waug.begin());
         for (int pc = 0; pc < (int)P.cout; ++pc)
             for (int ci = 0; ci < (int)P.cin; ++ci)
                 for (int t = 0; t < 9; ++t) waug[((size_t)(row0 + pc) * o.cin + cS + ci) * 9 + t] = wp[((size_t)pc * P.cin + ci) * 9 + t];
-        pack_conv_weights_s4_ex(waug.data(), (int)o.cin, nt * 16, 3, rg, cstart, n, 1, a.at(c.pair_c_off));
+        pack_conv_weights_s4(waug.data(), (int)o.cin, nt * 16, 3, ko, 1, a.at(c.pair_c_off));
     } else {
-        pack_conv_weights_s4_ex(ws, (int)o.cin, (int)o.cout, 3, rg, cstart, n, 1, a.at(c.pair_c_off));
+        pack_conv_weights_s4(ws, (int)o.cin, (int)o.cout, 3, ko, 1, a.at(c.pair_c_off));
     }
     const S4Range rs{(int)P.src[0].choff, (int)P.src[0].ch};
     c.pair_two_off = a.take(pair_p_two_floats(rs, (int)P.cout), 16);
@@ -300,41 +289,32 @@ void pack_pair(const BlobOp &P, const float *wP, const BlobOp &o, const float *w
 }
 
 // conv_s4.hip share / add: o is the consumer C of a pair, P its producer.  The share launch's matrix over S: P's rows (scaled by P's own
-// 2^k), zero rows up to share_row0, C's rows restricted to the columns of S (C's 2^k); the add launch's: C over [P's output, others..]
+// 2^k), zero rows up to share_row0, C's rows restricted to the columns of S (C's 2^k); the add launch's: C over [P's output, others..] (order_add)
 void pack_share(const BlobOp &P, const float *wP, const BlobOp &o, const float *ws, Arena &a, ConvPlan &c) {
-    const int n = (int)o.n_src, row0 = share_row0((int)P.cout), rows = row0 + (int)o.cout, cS = (int)o.src[0].ch;
+    const int row0 = share_row0((int)P.cout), rows = row0 + (int)o.cout, cS = (int)o.src[0].ch;
     std::vector<float> wp, wa((size_t)rows * P.cin * 9, 0.f);
     scale_weights(wP, (size_t)P.cout * P.cin * 9, wp);
     std::copy(wp.begin(), wp.end(), wa.begin());
     for (int co = 0; co < (int)o.cout; ++co)
         for (int ci = 0; ci < (int)P.cin; ++ci)
             for (int t = 0; t < 9; ++t) wa[((size_t)(row0 + co) * P.cin + ci) * 9 + t] = ws[((size_t)co * o.cin + cS + ci) * 9 + t];
-    const S4Range rs{(int)P.src[0].choff, (int)P.src[0].ch};
+    const KOrder ko_s = order_plain(P.src, 1), ko_b = order_add(o.src, (int)o.n_src);
     c.share_a_tiles = (rows + 15) / 16;
-    c.share_a_off = a.take(s4_packed_floats(&rs, 1, rows, 3, 0), 16);
-    pack_conv_weights_s4(wa.data(), (int)P.cin, rows, 3, &rs, 1, 0, a.at(c.share_a_off));
-    S4Range rg[kConvMaxSrc];
-    int cstart[kConvMaxSrc], c0 = 0;
-    for (int j = 0, k = 0; j < n; ++j) {
-        if (j != 1) {
-            rg[k] = S4Range{(int)o.src[j].choff, (int)o.src[j].ch};
-            cstart[k++] = c0;
-        }
-        c0 += (int)o.src[j].ch;
-    }
-    c.share_b_rounds = s4_rounds(rg, n - 1, 3, 0);
-    c.share_b_off = a.take(s4_packed_floats(rg, n - 1, (int)o.cout, 3, 0), 16);
-    pack_conv_weights_s4_ex(ws, (int)o.cin, (int)o.cout, 3, rg, cstart, n - 1, 0, a.at(c.share_b_off));
+    c.share_a_off = a.take(s4_packed_floats(ko_s, rows, 3, 0), 16);
+    pack_conv_weights_s4(wa.data(), (int)P.cin, rows, 3, ko_s, 0, a.at(c.share_a_off));
+    c.share_b_rounds = s4_rounds(ko_b, 3, 0);
+    c.share_b_off = a.take(s4_packed_floats(ko_b, (int)o.cout, 3, 0), 16);
+    pack_conv_weights_s4(ws, (int)o.cin, (int)o.cout, 3, ko_b, 0, a.at(c.share_b_off));
 }
 
 void pack_front(const BlobOp &o, const float *ws, Arena &a, ConvPlan &c) {   // 3x3 stride 2, one range
-    const S4Range rg{(int)o.src[0].choff, (int)o.src[0].ch};
-    c.front_off = a.take(s4_packed_floats(&rg, 1, (int)o.cout, 3, 0), 16);
-    pack_conv_weights_s4(ws, (int)o.cin, (int)o.cout, 3, &rg, 1, 0, a.at(c.front_off));
+    const KOrder ko = order_plain(o.src, 1);
+    c.front_off = a.take(s4_packed_floats(ko, (int)o.cout, 3, 0), 16);
+    pack_conv_weights_s4(ws, (int)o.cin, (int)o.cout, 3, ko, 0, a.at(c.front_off));
 }
 
 void pack_wave(const BlobOp &o, const float *w, const int *src_ch, Arena &a, ConvPlan &c) {   // stride 1
-    c.wave_chunks = wave_chunks(src_ch, (int)o.n_src, (int)o.k);
+    c.wave_chunks = range_chunks(src_ch, (int)o.n_src, wave_kc((int)o.k));
     c.wave_off = a.take(wave_packed_floats(src_ch, (int)o.n_src, (int)o.cout, (int)o.k));
     pack_conv_weights_wave(w, (int)o.cin, (int)o.cout, (int)o.k, src_ch, (int)o.n_src, a.at(c.wave_off));
 }

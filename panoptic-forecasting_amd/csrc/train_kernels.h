@@ -1,6 +1,6 @@
 // Training-side kernels — interface (train_kernels.hip); orchestrated by train_plan.hip.
 #pragma once
-#include "conv_mfma.h"
+#include "conv_ranges.h"
 
 namespace pf {
 
@@ -56,7 +56,7 @@ struct S4WBatch {
     S4WJob job[kS4WBatch];
 };
 static_assert(sizeof(S4WBatch) <= 3584, "S4WBatch travels as kernel arguments");
-size_t s4_wjob_init(S4WJob &jb, size_t w_off, int cin, int cout, int ks, const S4Range *r, int n_src, int pad_sources);
+size_t s4_wjob_init(S4WJob &jb, size_t w_off, int cin, int cout, int ks, const KOrder &k, int pad_sources);
 int launch_s4_pack_weights_dev(const float *theta, float *arena, const S4WJob *jobs, int n, float scale, hipStream_t s);
 // channels [c0, c1) of the fp32 tensor src [B][ctotal][H][W], times `scale` (a power of two) -> its packed-pair shadow with rows of
 // Wp >= W pixels (zeros in the pad columns).  fill_lo / fill_up: also zero the half group in front of / behind a slice that starts /

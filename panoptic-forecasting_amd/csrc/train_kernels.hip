@@ -59,7 +59,7 @@ int launch_onehot_dense(const void *seg, int seg_i64, const float *depth, const 
 
 // ------------------------------------------------------------------------------------------------ weight packing on the device
 size_t tiled_packed_floats(const int *src_ch, int n_src, int cout, int ks, int stride) {
-    return (size_t)((cout + 15) / 16) * dma_chunks(src_ch, n_src, ks, stride) * (dma_kc(ks, stride) / 4) * ks * ks * 64;
+    return (size_t)((cout + 15) / 16) * range_chunks(src_ch, n_src, dma_kc(ks, stride)) * (dma_kc(ks, stride) / 4) * ks * ks * 64;
 }
 
 // OIHW -> the per-tile order of the LDS-DMA kernels (conv_dma.hip::pack_conv_weights_tiled: [cout tile][chunk][kgroup][tap][64 lanes],
@@ -103,11 +103,8 @@ void pack_job_fill(PackJob &q, size_t w_off, int cin_f, int cout_f, int ks, int 
     const int kc = dma_kc(ks, stride);
     q.w_off = (long long)w_off; q.out_off = (long long)out_off;
     q.cin_f = cin_f; q.cout_f = cout_f; q.ks2 = ks * ks; q.kc = kc; q.tflip = transpose_flip; q.c0 = c0; q.ch = ch; q.n_src = n_src;
-    q.cstart[0] = 0; q.chunk0[0] = 0;
-    for (int j = 0; j < kConvMaxSrc; ++j) {
-        q.cstart[j + 1] = q.cstart[j] + (j < n_src ? src_ch[j] : 0);
-        q.chunk0[j + 1] = q.chunk0[j] + (j < n_src ? (src_ch[j] + kc - 1) / kc : 0);
-    }
+    range_starts(src_ch, n_src, 1, q.cstart);
+    range_starts(src_ch, n_src, kc, q.chunk0);
     q.total = (long long)tiled_packed_floats(src_ch, n_src, transpose_flip ? ch : cout_f, ks, stride);
     q.block0 = 0;
 }

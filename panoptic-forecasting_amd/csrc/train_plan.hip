@@ -259,16 +259,14 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<Dims> &d, int out_h
             const BlobOp &o = p->net.ops[i];
             if (o.kind != OP_STEM && o.kind != OP_CONV) continue;
             L.bwd_job[i].assign(o.n_src, -1);
-            int c0 = 0;
             const int dy_ch = (int)o.cout;
             if (L.odd[i]) {
                 L.bwd_all_job[i] = add(p->w_off[i], (int)o.cin, (int)o.cout, (int)o.k, 1, &dy_ch, 1, 1, 0, (int)o.cin);
                 continue;
             }
-            for (uint32_t j = 0; j < o.n_src; ++j) {
-                if (o.src[j].tensor != input) L.bwd_job[i][j] = add(p->w_off[i], (int)o.cin, (int)o.cout, (int)o.k, 1, &dy_ch, 1, 1, c0, (int)o.src[j].ch);
-                c0 += (int)o.src[j].ch;
-            }
+            const KOrder ko = order_plain(o.src, (int)o.n_src);
+            for (int j = 0; j < ko.n; ++j)
+                if (ko.r[j].tensor != input) L.bwd_job[i][j] = add(p->w_off[i], (int)o.cin, (int)o.cout, (int)o.k, 1, &dy_ch, 1, 1, ko.r[j].cstart, ko.r[j].ch);
         }
         L.wpk_arena = take(arena * sizeof(float) + 256);
     }
@@ -281,13 +279,9 @@ TLayout t_layout(const pf_train *p, int B, const std::vector<Dims> &d, int out_h
         for (size_t i = 0; i < p->net.ops.size(); ++i) {
             if (!s4_fwd_ok(p, i)) continue;
             const BlobOp &o = p->net.ops[i];
-            S4Range rg[kConvMaxSrc];
-            for (uint32_t j = 0; j < o.n_src; ++j) {
-                rg[j] = S4Range{(int)o.src[j].choff, (int)o.src[j].ch};
-                need[o.src[j].tensor] = 1;
-            }
+            for (uint32_t j = 0; j < o.n_src; ++j) need[o.src[j].tensor] = 1;
             S4WJob jb;
-            const size_t fl = s4_wjob_init(jb, p->w_off[i], (int)o.cin, (int)o.cout, (int)o.k, rg, (int)o.n_src, o.k == 1 && o.n_src == 2);
+            const size_t fl = s4_wjob_init(jb, p->w_off[i], (int)o.cin, (int)o.cout, (int)o.k, order_plain(o.src, (int)o.n_src), o.k == 1 && o.n_src == 2);
             jb.out_off = (unsigned)arena;
             arena += align_up(fl, 64);
             L.s4_job[i] = (int)L.s4jobs.size();
@@ -565,10 +559,8 @@ int tune_conv_dma(const pf_train *p, const ConvArgs &c, int ks, int stride, int 
 // conv `c` reading ONE source instead of its ranges: all `cin` channels of buffer x, rows of `win` pixels (the gathered copy of an
 // odd-width conv, the backward-data convs over dy)
 ConvArgs over_buffer(ConvArgs c, const float *x, int cin, int win, int wout) {
-    c.n_src = 1;
-    c.src[0] = x; c.src_ctotal[0] = cin; c.src_choff[0] = 0;
-    for (int k = 0; k <= kConvMaxSrc; ++k) c.src_cstart[k] = k ? cin : 0;
-    c.src_begin = 0; c.src_end = 1;
+    const BlobSrc all{0, 0, (uint32_t)cin};
+    set_sources(c, order_plain(&all, 1), [&](uint32_t) { return TensorRef{x, cin}; });
     c.Cin = cin; c.Win = win; c.Wout = wout;
     return c;
 }
@@ -586,6 +578,7 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<Di
     char *wsb = (char *)k.ws;
     auto buf = [&](size_t off) { return reinterpret_cast<float *>(wsb + off); };
     auto act = [&](uint32_t t) { return buf(L.act[t]); };
+    auto act_ref = [&](uint32_t t) { return TensorRef{act(t), (int)p->net.tensors[t].channels}; };
     auto gradt = [&](uint32_t t) { return buf(L.grad[t]); };
     const uint32_t input = p->net.ops[0].src[0].tensor;
     const int in_ch = (int)p->net.tensors[input].channels, n_cls = (int)p->net.hdr.n_cls;
@@ -604,20 +597,10 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<Di
     auto conv_args = [&](const BlobOp &o, const Dims &in, const Dims &out) {
         ConvArgs a;
         memset(&a, 0, sizeof(a));
-        a.n_src = (int)o.n_src;
-        int c0 = 0;
-        for (int j = 0; j < a.n_src; ++j) {
-            a.src[j] = act(o.src[j].tensor);
-            a.src_ctotal[j] = (int)p->net.tensors[o.src[j].tensor].channels;
-            a.src_choff[j] = (int)o.src[j].choff;
-            a.src_cstart[j] = c0;
-            c0 += (int)o.src[j].ch;
-        }
-        for (int j = a.n_src; j <= kConvMaxSrc; ++j) a.src_cstart[j] = c0;
+        set_sources(a, order_plain(o.src, (int)o.n_src), act_ref);
         a.bias = a.zero_page = p->dev_zero;
         a.Cin = (int)o.cin; a.Cout = (int)o.cout; a.ntiles = ((int)o.cout + 15) / 16;
         a.Hin = in.h; a.Win = in.w; a.Hout = out.h; a.Wout = out.w;
-        a.src_end = a.n_src;
         return a;
     };
     // backward-data conv: `ch` gradient channels into dst from the cout_f channels of dy ([B][cout_f][h][w])
@@ -635,11 +618,7 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<Di
         const PackJob &q = L.jobs[job];
         if (q.n_src != c.n_src) return fail(PF_EUNSUPPORTED, "training: a conv reads %d ranges, its weight packing %d", c.n_src, q.n_src);
         c.wpk = wpk_arena + q.out_off;
-        const int kc = dma_kc(ks, stride);
-        c.src_chunk0[0] = 0;
-        for (int j = 0; j < kConvMaxSrc; ++j)
-            c.src_chunk0[j + 1] = c.src_chunk0[j] + (j < c.n_src ? (c.src_cstart[j + 1] - c.src_cstart[j] + kc - 1) / kc : 0);
-        c.nchunks = c.chunk_end = c.src_chunk0[c.n_src]; c.chunk_begin = 0; c.rem = 0;
+        c.nchunks = set_chunks(c, dma_kc(ks, stride)); c.rem = 0;
         c.kacc = (kacc && ks == 3) ? 1 : 0;     // blocked summation in the 3x3 convolutions (conv_dma.hip: KACC; option train_blocked_sum)
         const std::array<int, 8> key = tune_key(c, ks, stride, B);
         int wm = 0, nt = 0, src = 1;
@@ -741,25 +720,15 @@ int build_train_schedule(const pf_train *p, const TCall &k, const std::vector<Di
                 // the tiled fp32 path leaves them).  The weight gradient of an odd-width layer still reads the gathered, row-padded
                 // fp32 copy of x
                 const S4WJob &jb = L.s4jobs[L.s4_job[i]];
-                const int per = o.k == 3 ? 2 : 8;
                 if (L.odd[i]) pad_gather(a, Wp, gather, true);
                 ConvArgs c = a;
-                int e = 0;
-                for (int j = 0; j < c.n_src; ++j) {
-                    const int ch0 = (int)o.src[j].choff, chn = (int)o.src[j].ch;
-                    c.src[j] = buf(L.s4act[o.src[j].tensor]);
-                    c.src_c4[j] = (c.src_ctotal[j] + 3) / 4;
-                    c.src_g0[j] = ch0 / 4;
-                    c.src_gn[j] = (ch0 + chn + 3) / 4 - ch0 / 4;
-                    c.src_ent0[j] = e;
-                    e += jb.pad ? (c.src_gn[j] + per - 1) / per * per : c.src_gn[j];
-                }
-                for (int j = c.n_src; j <= kConvMaxSrc; ++j) c.src_ent0[j] = e;
-                c.src_fmt = 1; c.dst_fmt = 0; c.src_begin = 0;
+                set_sources(c, order_plain(o.src, (int)o.n_src), [&](uint32_t t) { return TensorRef{buf(L.s4act[t]), (int)p->net.tensors[t].channels}; });
+                c.src_fmt = 1; c.dst_fmt = 0;
                 c.Win = Wp; c.Wout = Wp;
                 c.acc_scale = 1.0f / (kS4TrainWeightScale * kS4TrainActScale);
                 c.wpk = buf(L.s4w_arena) + jb.out_off;
-                c.nchunks = c.chunk_end = jb.rounds; c.chunk_begin = 0;
+                c.nchunks = jb.rounds;
+                set_s4_entries(c, (int)o.k, jb.pad);
                 c.kacc = (kacc && o.k == 3) ? 1 : 0;      // blocked summation, as in the fp32 step (conv_s4_kernel.inc: KACC)
                 TStep &st = add(T_CONV_S4, 0x80);
                 st.a = c; st.ks = (int)o.k;

@@ -125,14 +125,14 @@ int launch_s4_pack_weights_dev(const float *theta, float *arena, const S4WJob *j
 }
 
 // fills what the host needs of a job (rounds, blocks, arena bytes) from the conv's ranges; returns the packed floats
-size_t s4_wjob_init(S4WJob &jb, size_t w_off, int cin, int cout, int ks, const S4Range *r, int n_src, int pad_sources) {
+size_t s4_wjob_init(S4WJob &jb, size_t w_off, int cin, int cout, int ks, const KOrder &k, int pad_sources) {
     jb.w_off = (long long)w_off;
-    jb.cin = cin; jb.cout = cout; jb.ks = ks; jb.n_src = n_src; jb.pad = pad_sources;
-    for (int j = 0; j < kConvMaxSrc; ++j) { jb.choff[j] = j < n_src ? r[j].choff : 0; jb.ch[j] = j < n_src ? r[j].ch : 0; }
-    jb.rounds = s4_rounds(r, n_src, ks, pad_sources);
+    jb.cin = cin; jb.cout = cout; jb.ks = ks; jb.n_src = k.n; jb.pad = pad_sources;
+    for (int j = 0; j < kConvMaxSrc; ++j) { jb.choff[j] = j < k.n ? k.r[j].choff : 0; jb.ch[j] = j < k.n ? k.r[j].ch : 0; }
+    jb.rounds = s4_rounds(k, ks, pad_sources);
     jb.nblocks = ks == 3 ? s4_blocks_total(jb.rounds) : jb.rounds;
     jb.first_block = 0;
-    return s4_packed_floats(r, n_src, cout, ks, pad_sources);
+    return s4_packed_floats(k, cout, ks, pad_sources);
 }
 
 // ------------------------------------------------------------------------------------------------ activations: fp32 NCHW slice -> shadow

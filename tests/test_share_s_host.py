@@ -124,7 +124,9 @@ def test_share_and_add_packings_hold_the_consumers_weights_once(c_odd, c_even, d
 
 def test_plans_created_with_share_s_off_pack_what_they_packed_before(option):
     """FC-HarDNet-70: the weight arena of a plan created under share_s = 0 is byte for byte the arena of the library before the share /
-    add launches existed (tests/golden/arena_fchardnet70_seed1234.json: its size and SHA-256); with share_s = 1 it only grows."""
+    add launches existed (tests/golden/arena_fchardnet70_seed1234.json: its size and SHA-256); with share_s = 1 it only grows, to the arena
+    recorded under the library's default options at 56bf59a (default_floats, default_sha256: the share and add packings included), before
+    the packers took the order of their ranges from csrc/conv_ranges.cpp."""
     with open(os.path.join(GOLDEN, 'calib_seed1234.json')) as f:
         sd = synth.make_state_dict(seed=1234, calib=json.load(f))
     blob = packing.pack_blob(sd, 36, 11)
@@ -137,3 +139,5 @@ def test_plans_created_with_share_s_off_pack_what_they_packed_before(option):
     option('share_s', 1, 1)
     on, _ = plan_arena(blob, 36, 11, 1)
     assert on.size > off.size
+    assert on.size == want['default_floats']
+    assert hashlib.sha256(on.tobytes()).hexdigest() == want['default_sha256']

@@ -230,7 +230,11 @@ __global__ __launch_bounds__(256) void bn_apply_relu_kernel(const float *y, BnSt
 }
 
 // ---- the same four passes with 16-B accesses and no per-element index division (planes of HW % 4 == 0 elements): a block
-// walks the planes of its channel sample by sample, a thread adds its four values in fp32 and accumulates those in fp64
+// walks the planes of its channel sample by sample.  The statistics kernel widens each of its four values and sums x and x^2 in
+// fp64, as the scalar kernel does: var = E[x^2] - mean^2 cancels, so with |mean| / std = R a quad's fp32 sum of squares (rounded
+// at 2^-24 of mean^2) and its fp32 sum (an error d of the mean is 2 * mean * d of the variance) EACH put R^2 * 2^-24 of the variance
+// into it (R = 300: 1e-3 of the running variance, 4e-4 of the activation; DESIGN.md, "Precision of the BatchNorm statistics").
+// The backward kernel's quad sums are of g' and g' * xhat, both O(1) with no cancellation behind them: fp32 per quad, fp64 across
 __global__ __launch_bounds__(256) void bn_stats_partial4_kernel(const float *y, int B, int C, int HW4, double *partial) {
     const int c = blockIdx.x, slab = blockIdx.y;
     __shared__ double sm[2 * 4];
@@ -239,8 +243,12 @@ __global__ __launch_bounds__(256) void bn_stats_partial4_kernel(const float *y, 
         const tr_f32x4 *p = reinterpret_cast<const tr_f32x4 *>(y) + ((long long)b * C + c) * HW4;
         for (int i = slab * 256 + threadIdx.x; i < HW4; i += kBnSlabs * 256) {
             const tr_f32x4 x = p[i];
-            v[0] += (double)((x[0] + x[1]) + (x[2] + x[3]));
-            v[1] += (double)((x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]));
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const double xk = (double)x[k];
+                v[0] += xk;
+                v[1] = __builtin_fma(xk, xk, v[1]);
+            }
         }
     }
     block_reduce_d<2>(v, sm);
@@ -325,6 +333,9 @@ int launch_bn_forward(const float *y, int B, int C, int H, int W, float eps, flo
     const long long HW = (long long)H * W;
     const int Wp = y_pitch > 0 ? y_pitch : W;
     const bool vec = (HW & 3) == 0 && HW / 4 < (1ll << 31) && Wp == W;
+    // the label names the two kernels launched (tests assert the form by it); bytes: y read twice, dst written
+    ProfScope ps(s, vec ? "bn_stats_partial4_kernel+bn_apply_relu4_kernel" : "bn_stats_partial_kernel+bn_apply_relu_kernel", 0.0,
+                 4.0 * B * C * (double)HW * 3.0);
     if (vec) hipLaunchKernelGGL(bn_stats_partial4_kernel, dim3(C, kBnSlabs), dim3(256), 0, s, y, B, C, (int)(HW / 4), partial);
     else hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, kBnSlabs), dim3(256), 0, s, y, B, C, HW, W, Wp, partial);
     const BnStats st{partial, (double)B * HW, eps, momentum, mean, invstd, running_mean, running_var};
@@ -413,13 +424,19 @@ int launch_bn_backward(const float *g, int t_ctotal, int choff, const float *y, 
     const int Wyp = y_pitch > 0 ? y_pitch : W;
     if (Wyp != W && dy_pitch != Wyp) return fail(PF_EINVAL, "bn_backward: a pitched y needs dy with the same pitch");
     const bool vec = (HW & 3) == 0 && HW / 4 < (1ll << 31) && Wyp == W;
+    const bool pitch = dy_pitch > 0 && dy_pitch != W;
+    // the label names the two kernels launched; bytes: g and y read twice, dy written
+    const char *label = pitch ? (vec ? "bn_bwd_partial4_kernel+bn_bwd_apply_pitch_kernel" : "bn_bwd_partial_kernel+bn_bwd_apply_pitch_kernel")
+                        : vec ? "bn_bwd_partial4_kernel+bn_bwd_apply4_kernel"
+                              : "bn_bwd_partial_kernel+bn_bwd_apply_kernel";
+    ProfScope ps(s, label, 0.0, 4.0 * B * C * (double)HW * 5.0);
     if (vec)
         hipLaunchKernelGGL(bn_bwd_partial4_kernel, dim3(C, kBnSlabs), dim3(256), 0, s, g, gamma, beta, t_ctotal, choff, y, mean, invstd, B, C,
                            (int)(HW / 4), relu, partial);
     else
         hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(C, kBnSlabs), dim3(256), 0, s, g, gamma, beta, t_ctotal, choff, y, mean, invstd, B, C, HW, W, Wyp,
                            relu, partial);
-    if (dy_pitch > 0 && dy_pitch != W)
+    if (pitch)
         hipLaunchKernelGGL(bn_bwd_apply_pitch_kernel, dim3((unsigned)((H * dy_pitch + 255) / 256), B * C), dim3(256), 0, s, g, beta, t_ctotal, choff, y, mean,
                            invstd, gamma, partial, dgamma, dbeta, B, C, H, W, dy_pitch, relu, Wyp != W, dy);
     else if (vec)
@@ -465,6 +482,7 @@ int launch_bias_backward(const float *g, int t_ctotal, int choff, int B, int C, 
         int rc = launch_zero_fill(dy, (size_t)B * C * H * Wp * sizeof(float), s);
         if (rc) return rc;
     }
+    ProfScope ps(s, "bias_bwd_kernel+bias_bwd_final_kernel", 0.0, 4.0 * B * C * (double)H * W * 2.0);
     hipLaunchKernelGGL(bias_bwd_kernel, dim3(C, kBnSlabs), dim3(256), 0, s, g, t_ctotal, choff, B, C, (long long)H * W, W, Wp, partial, dy);
     hipLaunchKernelGGL(bias_bwd_final_kernel, dim3((C + 63) / 64), dim3(64), 0, s, partial, C, dbias);
     PF_LAUNCH_CHECK("bias_bwd_kernel");

@@ -123,3 +123,67 @@ def test_probe_elementwise_bar_bites_where_relative_l2_does_not(case):
     assert d['dw L']['e_hip'] >= 5.0 * max(PROBE_M_CAP * d['dw L']['e_aten'], PROBE_FLOOR_CAP), d['dw L']
     if case.name in ('bites 50->70 17x136', 'bites 270->70 17x72', 'bites s2 40->24 35x70'):
         assert d['dw L']['rel_hip'] <= 1e-4, d['dw L']          # ... and the norm-wise bar does not see it
+
+
+def _bn_emulated(y, g, gamma, beta, squares64, sums64, eps=1e-5, momentum=0.1):
+    """What the 4-wide BatchNorm kernels of csrc/train_kernels.hip make of a conv output ``y`` (fp32 [B, C, H, W], H * W % 4 == 0)
+    and the gradient ``g`` arriving at the layer's output, operation for operation on the CPU.  Per quad the sum either in fp32,
+    (x0 + x1) + (x2 + x3), or of the four widened values (``sums64``); the sum of squares either as one fp32 expression
+    (x0 x0 + x1 x1) + (x2 x2 + x3 x3) or as four fp64 products (``squares64``); quads added in fp64; var = E[x^2] - mean^2 in fp64;
+    mean / invstd rounded to fp32; z = fma(y, sc, sh) in fp32; dgamma = sum g xhat with xhat in fp32
+    -> {'rvar L' (from a running variance of 0), 'act L', 'dgamma L'}, float64 tensors"""
+    b, c, h, w = y.shape
+    q = y.transpose(0, 1).reshape(c, -1, 4)                                       # fp32 quads per channel
+    n = float(b * h * w)
+    s = q.double().sum((1, 2)) if sums64 else ((q[..., 0] + q[..., 1]) + (q[..., 2] + q[..., 3])).double().sum(1)
+    if squares64:
+        sq = (q.double() ** 2).sum((1, 2))
+    else:
+        sq = ((q[..., 0] * q[..., 0] + q[..., 1] * q[..., 1]) + (q[..., 2] * q[..., 2] + q[..., 3] * q[..., 3])).double().sum(1)
+    mean = s / n
+    var = (sq / n - mean * mean).clamp_min(0.0)
+    mean_f, invstd_f = mean.float(), (1.0 / (var + eps).sqrt()).float()
+    rvar = (float(torch.tensor(momentum, dtype=torch.float32)) * var * n / (n - 1.0)).float()
+    sc = gamma * invstd_f
+    sh = beta - mean_f * sc
+    z = (y.double() * sc.double().view(1, c, 1, 1) + sh.double().view(1, c, 1, 1)).float()       # one rounding: the fma
+    xh = (y - mean_f.view(1, c, 1, 1)) * invstd_f.view(1, c, 1, 1)
+    dgamma = (g.double() * xh.double()).sum((0, 2, 3)).float()
+    return {'rvar L': rvar.double(), 'act L': z.double(), 'dgamma L': dgamma.double()}
+
+
+@pytest.mark.parametrize('which', [0, 1])
+def test_probe_bar_tells_fp32_quad_statistics_from_fp64_statistics(which):
+    """The ill-conditioned BatchNorm cases of tests/test_gpu_train_layers.py (|mean| / std ~ 270 per channel) can tell a statistics
+    kernel that sums each quad in fp32 from one that widens the values first, whatever M <= PROBE_M_CAP the measurement on the
+    device yields - pinned on the CPU, from the fp32 ATen conv output of the first two of those cases.
+      * fp32 quad sums of x and of x^2 (the 4-wide kernel as it was): misses the elementwise bar on the running variance by 5x or
+        more at the cap M = 32 (1.0e-3 / 6.9e-4 against 32 x 2.0e-6 / 2.6e-6).
+      * fp64 squares with the fp32 quad sum of x kept: still misses it by 5x or more (8.4e-4 / 5.9e-4).  The mean itself is
+        good to 1e-8, but var = E[x^2] - mean^2 takes an error d of the mean as 2 mean d: 2 x 270 x 2e-6.  So the kernel widens
+        both sums.
+      * both in fp64 (the kernel now, and the scalar kernel always): passes on the running variance, the activation and dgamma
+        at M = 2; e / e_aten is 1.0 on all three."""
+    from tests.helpers import PROBE_FLOOR_CAP, PROBE_M_CAP, mini_torch, probe_distances, probe_failures, probe_mean_over_std, probe_reference
+    from tests.test_gpu_train_layers import BN, PROBE_FLOOR
+    case = BN[which][0]
+    assert case.cond == 'ill' and 200.0 <= float(probe_mean_over_std(case).min()) <= 500.0
+    r64, r32 = probe_reference(case)
+    keys = ('rvar L', 'act L', 'dgamma L')
+    r64, r32 = {k: r64[k] for k in keys}, {k: r32[k] for k in keys}
+    params, x, lab = case.data()
+    pre = {}
+    _, leaves, kept = mini_torch(case.spec(), params, x, lab, dtype=torch.float32, pre=pre)
+    y, g = pre['L'].detach(), kept['L'].grad
+    assert y.dtype == torch.float32 and g.dtype == torch.float32
+    gamma, beta = params['L']['gamma'], params['L']['beta']
+    dist = {}
+    for form, sq64, s64 in (('fp32 quads', False, False), ('fp64 squares only', True, False), ('fp64', True, True)):
+        dist[form] = probe_distances(_bn_emulated(y, g, gamma, beta, squares64=sq64, sums64=s64), r64, r32)
+        print(case.name, '%-18s' % form, {k: 'e %.2e e_aten %.2e' % (d['e_hip'], d['e_aten']) for k, d in dist[form].items()})
+    for form in ('fp32 quads', 'fp64 squares only'):
+        bad = probe_failures(dist[form], PROBE_M_CAP, PROBE_FLOOR_CAP, rel_l2=False)
+        assert ('rvar L', 'elementwise') in [b[:2] for b in bad], (form, bad)
+        d = dist[form]['rvar L']
+        assert d['e_hip'] >= 5.0 * max(PROBE_M_CAP * d['e_aten'], PROBE_FLOOR_CAP), (form, d)
+    assert probe_failures(dist['fp64'], 2.0, PROBE_FLOOR, rel_l2=False) == [], dist['fp64']

@@ -227,6 +227,45 @@ int pf_panoptic_encode(const void *seg, int seg_is_i64, int convert_to_ids, int 
 int pf_panoptic_max_ids(void);
 
 /* ------------------------------------------------------------------------------------------
+ * Panoptic quality — the segment matching of the evaluation that ends scripts/fg/run_fg_eval_panoptic.sh
+ * (cityscapesscripts.evaluation.evalPanopticSemanticLabeling; absent and unpinned here: layout and parity unpinned).
+ *
+ *   pred, gt    [B,H,W] i32 or i64 label maps, each width chosen on its own; both are only read.  H*W % 4 == 0, 16-byte aligned.
+ *   fmt 0       trainId format (the merge output): stuff = trainId, thing = trainId*1000 + instance, void = 255;
+ *               category = v/1000 for v >= 1000, else v.
+ *   fmt 1       Cityscapes id format (what the exported / ground-truth PNG decodes to): void = 0; category id = v/1000 for
+ *               v >= 1000, else v, mapped to its trainId by the inverse of the export's trainId -> id table.
+ *   A pixel is VOID when its category is none of the n_cls (<= 19) evaluated classes; void is one pseudo-segment, every other
+ *   segment is identified by its raw value.  With crowd != 0 a ground-truth segment is CROWD iff it has no instance part
+ *   (v < 1000) and its trainId is a thing class (11..18), as the Cityscapes panoptic ground truth marks iscrowd.
+ *   TP   gt segment neither void nor crowd, same category as the prediction, and
+ *        iou = inter / (g_area + p_area - inter - p_void[p]) > 0.5 strictly (p_void[p]: pixels of p on void ground truth).
+ *   FN   a gt segment, neither void nor crowd, without a match.
+ *   FP   a non-void predicted segment without a match, unless p_void + p_crowd > 0.5 * p_area strictly, p_crowd being its
+ *        pixels on crowd ground truth of its own category.  A crowd segment is never TP or FN; its pixels stay in the union.
+ *   acc         [n_cls,4] f64 (sum_iou, TP, FP, FN), ADDED to; per_image (nullable) [B,n_cls,4] f64, written.
+ * Areas and counts are integers, an iou is one fp64 division; the ious of a class are added in ascending gt id inside an
+ * image and the images in index order, so two runs of a call give the same bits although the tables are filled by integer
+ * atomics.  Tables: pf_pq_table_slots() = 8192 distinct (gt, pred) pairs per image (a Cityscapes image has a few hundred);
+ * 1024-slot tables in LDS in front of them, whose overflow spills to the image's table without loss.
+ * Never silent: the first word of the workspace is a sticky status word, ORed with
+ *   PF_PQ_STATUS_FULL   an image had more distinct pairs than pf_pq_table_slots()
+ *   PF_PQ_STATUS_VALUE  a value outside [0, 65536) (compared in the map's own width: 2^33 + 5 is out of range)
+ * and an image flagged with either adds nothing to acc (its per_image row is zero).  The caller zeroes the first 256
+ * bytes of a fresh workspace once (pf_pq_status_reset enqueues that); everything else is zeroed by every call with the
+ * library's own fill kernel, so a captured call holds kernel nodes only.  pf_pq_accumulate enqueues only (4 launches);
+ * B == 0 launches nothing.  pf_pq_status copies the status word to the host and waits for the stream.
+ */
+#define PF_PQ_STATUS_FULL 1u
+#define PF_PQ_STATUS_VALUE 2u
+int pf_pq_workspace(int B, size_t *bytes);
+int pf_pq_table_slots(void);
+int pf_pq_accumulate(const void *pred, int pred_is_i64, const void *gt, int gt_is_i64, int fmt, int crowd, int n_cls, int B,
+                     int H, int W, double *acc, double *per_image, void *ws, size_t ws_bytes, void *stream);
+int pf_pq_status(const void *ws, void *stream, int *host_status);
+int pf_pq_status_reset(void *ws, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * pf_bg_dense_input - the network input of BGModel.forward (models/bg/bg_model.py:61-69) for the configurations the fused stem
  * of pf_bg_forward does not cover (convert2onehot = False, or no depth channels): writes x [B, T*C (+T), H, W] f32 for
  * pf_hardnet_forward_dense.

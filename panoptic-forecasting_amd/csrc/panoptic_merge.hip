@@ -25,6 +25,7 @@
 //                       (nearer) instances overwrite earlier ones.
 //   panoptic_encode_kernel  trainId-based panoptic ids -> Cityscapes ids (255 -> 0; >100: id2label; else trainId2label),
 //                       RGB = (id % 256, id // 256, id // 65536) and a presence byte per id for segments_info.
+#include "panoptic_ids.h"
 #include "pf_common.h"
 #include "pf_prof.h"
 
@@ -213,8 +214,7 @@ __global__ __launch_bounds__(256) void merge_kernel(MergeArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-__constant__ uint8_t kPanTrainId2Id[19] = {7, 8, 11, 12, 13, 17, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 31, 32, 33};
-
+// kPanTrainId2Id: panoptic_ids.h (shared with pq_kernels.hip)
 struct EncodeArgs {
     const void *seg;     // [B,H,W] i32 or i64 trainId-based panoptic ids
     uint8_t *rgb;        // [B,H,W,3]

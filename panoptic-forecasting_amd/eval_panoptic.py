@@ -1,0 +1,219 @@
+#!/usr/bin/env python
+"""Panoptic evaluation driver - takes the flags of the command that ends ``scripts/fg/run_fg_eval_panoptic.sh``:
+
+    python -u panoptic-forecasting_amd/eval_panoptic.py --gt-json-file GT.json --gt-folder GT_DIR \\
+        --prediction-json-file PRED.json --prediction-folder PRED_DIR --results_file OUT.json
+
+in place of ``python -m cityscapesscripts.evaluation.evalPanopticSemanticLabeling`` with the same flags.  That package is absent
+here and its version unpinned: the result file's layout ('All' / 'Things' / 'Stuff' with pq, sq, rq as fractions and n, 'per_class'
+keyed by label name) follows that evaluator as far as it is known; layout and parity unpinned.
+
+Images are paired by ``image_id``; the PNGs are read on a thread pool, turned into ids (R + 256 G + 65536 B) and matched in the
+'cityscapes' id format: on the device by ``pq.PanopticQuality`` (``--matcher device``, batches stay in flight: ``update`` only
+enqueues) or on the host by ``pq.pq_panoptic_host`` (``--matcher host``).  Under an initialised process group the images are
+sharded round-robin and the accumulators gathered; rank 0 writes the file.  Both matchers run under both backends: the gather takes
+its tensors where the backend carries them (``gather_total``) - on this rank's GPU under "nccl" (RCCL), which has no host
+tensors, so there the host matcher's accumulators are moved to the device for the exchange; in host memory under gloo.
+
+What is checked of the JSON files: every listed segment's ``category_id`` and ``iscrowd`` against what its id implies.  Not checked:
+that the ids listed are the ids in the PNG - a segment the JSON omits is evaluated as the image has it.
+"""
+import argparse
+import json
+import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if __package__ in (None, ''):                     # run as a script: make the package importable under its alias
+    sys.path.insert(0, os.path.dirname(_HERE))
+    import panoptic_forecasting_amd  # noqa: F401
+    __package__ = 'panoptic_forecasting_amd'
+
+from . import dist as pfdist       # noqa: E402
+from . import hop_io               # noqa: E402
+from . import panoptic             # noqa: E402
+from . import pq                   # noqa: E402
+
+LABEL_NAMES = ('road', 'sidewalk', 'building', 'wall', 'fence', 'pole', 'traffic light', 'traffic sign', 'vegetation', 'terrain',
+               'sky', 'person', 'rider', 'car', 'truck', 'bus', 'train', 'motorcycle', 'bicycle')
+N_CLS = 19
+THING_IDS = frozenset(panoptic.TRAINID2ID[pq.FIRST_THING:])
+
+
+class EvalError(RuntimeError):
+    pass
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--gt-json-file', dest='gt_json_file', required=True)
+    ap.add_argument('--gt-folder', dest='gt_folder', default=None, help='default: the json file name without .json')
+    ap.add_argument('--prediction-json-file', dest='prediction_json_file', required=True)
+    ap.add_argument('--prediction-folder', dest='prediction_folder', default=None)
+    ap.add_argument('--results_file', default='resultPanopticSemanticLabeling.json')
+    ap.add_argument('--matcher', choices=('device', 'host'), default='device')
+    ap.add_argument('--batch_size', type=int, default=8)
+    ap.add_argument('--num_workers', type=int, default=8)
+    a = ap.parse_args(argv)
+    a.gt_folder = a.gt_folder or os.path.splitext(a.gt_json_file)[0]
+    a.prediction_folder = a.prediction_folder or os.path.splitext(a.prediction_json_file)[0]
+    return a
+
+
+def load_annotations(path):
+    """{'annotations': [...]} with or without the 'images' / 'categories' of a ground-truth file, or the bare list."""
+    with open(path, encoding='utf-8') as f:
+        data = json.load(f)
+    ann = data['annotations'] if isinstance(data, dict) else data
+    names = None
+    if isinstance(data, dict) and data.get('categories'):
+        by_id = {int(c['id']): c['name'] for c in data['categories']}
+        if all(i in by_id for i in panoptic.TRAINID2ID):
+            names = tuple(by_id[i] for i in panoptic.TRAINID2ID)
+    return {a['image_id']: a for a in ann}, names
+
+
+def check_segments(ann, what):
+    """Each segment the JSON lists must say what its id implies: category_id = id // 1000 for id >= 1000 else id; iscrowd = no
+    instance part and a thing category.  (Whether the PNG holds exactly the listed ids is not checked.)"""
+    for seg in ann.get('segments_info', []):
+        v = int(seg['id'])
+        cat = v // 1000 if v >= 1000 else v
+        if 'category_id' in seg and int(seg['category_id']) != cat:
+            raise EvalError('%s image %s segment %d: category_id %s, but the id implies %d'
+                            % (what, ann['image_id'], v, seg['category_id'], cat))
+        crowd = int(v < 1000 and cat in THING_IDS)
+        if 'iscrowd' in seg and int(seg['iscrowd']) != crowd:
+            raise EvalError('%s image %s segment %d: iscrowd %s, but the id implies %d' % (what, ann['image_id'], v, seg['iscrowd'], crowd))
+
+
+def pair_images(a):
+    """[(image_id, gt png, prediction png)] in ground-truth order, after the JSON checks; the 19 label names."""
+    gt, names = load_annotations(a.gt_json_file)
+    pred, _ = load_annotations(a.prediction_json_file)
+    pairs = []
+    for image_id, g in gt.items():
+        if image_id not in pred:
+            raise EvalError('no prediction for ground-truth image %s in %s' % (image_id, a.prediction_json_file))
+        p = pred[image_id]
+        check_segments(g, 'ground truth')
+        check_segments(p, 'prediction')
+        gf, pf = os.path.join(a.gt_folder, g['file_name']), os.path.join(a.prediction_folder, p['file_name'])
+        for path, what in ((gf, 'ground-truth'), (pf, 'prediction')):
+            if not os.path.isfile(path):
+                raise EvalError('%s file missing for image %s: %s' % (what, image_id, path))
+        pairs.append((image_id, gf, pf))
+    return pairs, names or LABEL_NAMES
+
+
+def read_pair(item):
+    image_id, gf, pf = item
+    g, p = hop_io.read_png(gf), hop_io.read_png(pf)
+    for arr, path in ((g, gf), (p, pf)):
+        if arr.ndim != 3 or arr.shape[2] < 3 or arr.dtype != np.uint8:
+            raise EvalError('image %s: %s is not an 8-bit RGB panoptic PNG' % (image_id, path))
+    if g.shape[:2] != p.shape[:2]:
+        raise EvalError('image %s: ground truth is %dx%d, prediction %dx%d' % ((image_id,) + g.shape[:2] + p.shape[:2]))
+    return g[..., :3], p[..., :3]
+
+
+def _ids_on_device(rgb, device):
+    """[B,H,W,3] u8 host array -> [B,H,W] i32 ids on the device (pinned staging, asynchronous copy)."""
+    t = torch.from_numpy(rgb)
+    if torch.cuda.is_available():
+        t = t.pin_memory()
+    t = t.to(device, non_blocking=True).to(torch.int32)
+    return (t[..., 0] + 256 * t[..., 1] + 65536 * t[..., 2]).contiguous()
+
+
+def accumulate(pairs, a, device=None):
+    """[19,4] float64 accumulators of this rank's images (device matcher: on the device)."""
+    if a.matcher == 'device':
+        device = device or torch.device('cuda', torch.cuda.current_device())
+        meter = pq.PanopticQuality(N_CLS, fmt='cityscapes', crowd=True, device=device)
+    acc = torch.zeros(N_CLS, 4, dtype=torch.float64)
+    with ThreadPoolExecutor(max_workers=max(1, a.num_workers)) as pool:
+        loaded = pool.map(read_pair, pairs)
+        batch, shape = [], None
+        def flush():
+            if not batch:
+                return
+            g = np.stack([x[0] for x in batch])
+            p = np.stack([x[1] for x in batch])
+            if a.matcher == 'device':
+                meter.update(_ids_on_device(p, device), _ids_on_device(g, device))
+            else:
+                pq.pq_panoptic_host(torch.from_numpy(panoptic.decode_png(p)), torch.from_numpy(panoptic.decode_png(g)), N_CLS,
+                                    fmt='cityscapes', crowd=True, acc=acc)
+            del batch[:]
+        for g, p in loaded:
+            if batch and (g.shape != shape or len(batch) >= a.batch_size):
+                flush()
+            shape = g.shape
+            batch.append((g, p))
+        flush()
+    if a.matcher == 'device':
+        meter.result()                                    # waits; raises on a set status word
+        acc = meter.acc
+    return acc
+
+
+def gather_total(acc):
+    """This rank's [19,4] accumulators -> their sum over the ranks, on the host.  The exchange runs where the process group's
+    backend has tensors: RCCL ("nccl") carries device tensors only, gloo host tensors (dist.gather_accumulators moves those itself)."""
+    if pfdist.is_dist() and str(torch.distributed.get_backend()) != 'gloo':
+        acc = acc.to(torch.device('cuda', torch.cuda.current_device()))
+    return pfdist.gather_accumulators(acc).sum(0).cpu()
+
+
+def results_from_acc(acc, names):
+    s = pq.pq_splits(acc, scale=1.0)
+    out = {k: s[k] for k in ('All', 'Things', 'Stuff')}
+    out['per_class'] = {names[c]: s['per_class'][c] for c in range(len(names))}
+    return out
+
+
+def print_table(res, out=sys.stdout):
+    out.write('%-16s %7s %7s %7s %4s\n' % ('', 'PQ', 'SQ', 'RQ', 'N'))
+    for name, r in res['per_class'].items():
+        out.write('%-16s %7.2f %7.2f %7.2f\n' % (name, 100 * r['pq'], 100 * r['sq'], 100 * r['rq']))
+    out.write('-' * 46 + '\n')
+    for name in ('All', 'Things', 'Stuff'):
+        r = res[name]
+        out.write('%-16s %7.2f %7.2f %7.2f %4d\n' % (name, 100 * r['pq'], 100 * r['sq'], 100 * r['rq'], r['n']))
+
+
+def run(a):
+    rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if pfdist.is_dist() else (0, 1)
+    pairs, names = pair_images(a)
+    if a.matcher == 'device' and not torch.cuda.is_available():
+        raise EvalError('--matcher device needs a GPU (there is no fallback: pass --matcher host for the host path)')
+    mine = [pairs[i] for i in pfdist.shard_indices(len(pairs), rank, world)]
+    acc = accumulate(mine, a)
+    total = gather_total(acc)
+    res = results_from_acc(total, names)
+    if rank == 0:
+        with open(a.results_file, 'w', encoding='utf-8') as f:
+            json.dump(res, f, indent=4)
+        print_table(res)
+    return res
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    pfdist.init_distributed_mode()
+    try:
+        run(a)
+    except EvalError as e:                              # no barrier: the other ranks may not have failed
+        sys.exit('eval_panoptic: %s' % e)
+    if pfdist.is_dist():
+        torch.distributed.barrier()
+        torch.distributed.destroy_process_group()
+
+
+if __name__ == '__main__':
+    main()

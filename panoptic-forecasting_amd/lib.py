@@ -42,6 +42,11 @@ SIGNATURES = {
                                _vp, _i, _vp, _sz, _vp]),
     'pf_panoptic_encode': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'pf_panoptic_max_ids': (_i, []),
+    'pf_pq_workspace': (_i, [_i, _c.POINTER(_sz)]),
+    'pf_pq_table_slots': (_i, []),
+    'pf_pq_accumulate': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'pf_pq_status': (_i, [_vp, _vp, _c.POINTER(_i)]),
+    'pf_pq_status_reset': (_i, [_vp, _vp]),
     'pf_bg_dense_input': (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _i, _i, _i, _i, _vp, _vp]),
     'pf_seg_loss_workspace': (_i, [_i, _i, _i, _c.POINTER(_sz)]),
     'pf_seg_loss': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),

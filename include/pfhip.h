@@ -563,6 +563,23 @@ int pf_debug_conv_ranges(int form, int ks, int kc, int pad, int n_src, int n_cas
  * offset and rounds of its add launch's ("share_s"; 0 = the op has none). */
 int pf_debug_plan_arena(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
                         long long *table, int table_ops);
+/* Host only, no device involved, nothing enqueued (tests): the plan of one pf_train_forward_backward of a training plan created now
+ * from this blob - the workspace layout and the schedule of a step on B dense inputs of H x W with labels of out_h x out_w, under
+ * the process-wide options as pf_train_create and a step read them, without pf_train_autotune; the addresses it is built against
+ * are made up.  *n_regions / *n_steps = rows of the two tables; rows are copied while they fit (cap_regions, cap_steps rows).
+ * regions: rows of 4 {kind, index, offset, bytes}, one per workspace region in the order the layout hands them out.  kind: 0
+ * activation, 1 gradient, 6 packed-pair shadow (index = tensor); 2 conv output before BatchNorm, 3 batch statistics, 4 gathered
+ * row-padded input (index = op); 5 / 7 tiled / packed-pair weight packings; 8 the measuring pass's gradients; 9 dy (index = slot),
+ * 10 weight-gradient partial sums (index = side stream), 11 / 12 padded input / output copy, 13 the loss gradient at label size,
+ * 14 scratch of the two-pass bilinear transpose, 15 / 16 partial sums of the loss / of BatchNorm, 17 the loss sums; the last row
+ * is {18, 0, 0, workspace bytes} = pf_train_workspace.  Offsets are multiples of 256; bytes = what the region was asked to hold.
+ * steps: rows of 5.  {0, kind, side stream (-1 = the caller's), dy slot, stats bits} per step of the schedule, in order (kind: TStepKind
+ * of csrc/train_plan.h; bit k of the stats bits: the step counts in slot k of pf_train_path_stats), each followed by one row
+ * {1, tensor, first channel, channels, access} per channel range of a tensor's gradient buffer the step touches - access 0 = stores,
+ * 1 = adds, 2 = clears, 3 = reads - read back from the step's pointers, not from what the builder meant.
+ * slots_streams (nullable): {dy slots, side streams} the library was built with. */
+int pf_debug_train_plan(const void *blob, size_t bytes, int in_ch, int n_cls, int B, int H, int W, int out_h, int out_w,
+                        long long *regions, int cap_regions, int *n_regions, int *steps, int cap_steps, int *n_steps, int *slots_streams);
 /* Instrumented builds only (make libpfhip_probe.so, env PF_PROBE=1): the 64 in-kernel timestamps (shader clock)
  * written by workgroup 0 / wave 0 of the last conv_wave launch; PF_EINVAL when nothing was recorded. */
 int pf_debug_probe_read(long long *host64);

@@ -9,6 +9,7 @@ constexpr uint32_t kBlobVersion = 2;
 constexpr int kConvMaxSrc = 4;   // channel ranges a conv reads (BlobOp, ConvArgs)
 
 enum OpKind : uint32_t { OP_STEM = 0, OP_CONV = 1, OP_POOL = 2, OP_UPSAMPLE = 3, OP_HEAD = 4 };
+inline bool is_conv(uint32_t kind) { return kind == OP_STEM || kind == OP_CONV; }   // the ops that carry weights
 
 #pragma pack(push, 1)
 struct BlobHeader {  // 64 B

@@ -39,5 +39,6 @@ int launch_zero_fill(void *p, size_t bytes, hipStream_t s);
 int launch_copy(void *dst, const void *src, size_t bytes, hipStream_t s);
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static inline int round_up4(int w) { return (w + 3) / 4 * 4; }   // a row of w pixels padded to whole 16-byte pieces
 
 }  // namespace pf

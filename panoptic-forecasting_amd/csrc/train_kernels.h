@@ -1,4 +1,4 @@
-// Training-side kernels — interface (train_kernels.hip); orchestrated by train_plan.hip.
+// Training-side kernels — interface (train_kernels.hip); laid out by train_layout.cpp, scheduled by train_schedule.cpp, enqueued by train_plan.hip.
 #pragma once
 #include "conv_ranges.h"
 

@@ -259,6 +259,51 @@ class MiniTrain:
         _lib.load().pf_train_destroy(self.t)
 
 
+def mini_net():
+    """Every op kind of the training path in one small, well-conditioned network: stride-2 stem, 3x3 convs with one and
+    two input ranges, a conv writing into a slice of a wider tensor, 1x1 conv, pool, upsample + 1x1 over [up, skip],
+    plain final conv, bilinear head."""
+    sp = MiniSpec(6)
+    S = arch.Src
+    c0 = sp.conv('c0', [S(0, 0, 6)], 16, 3, stride=2, bn=True)
+    c1 = sp.conv('c1', [S(c0, 0, 16)], 24, 3, bn=True)
+    cat = sp.tensor('cat', 28 + 10 + 12)
+    sp.conv('c2', [S(c1, 0, 24), S(c0, 0, 16)], 28, 3, dst=cat, dst_choff=10, bn=True)
+    sp.conv('c2b', [S(c1, 4, 18)], 10, 3, dst=cat, dst_choff=0, bn=True)
+    # like the last layer of a HarDBlock: three ranges, the first one a slice of the tensor it writes into
+    sp.conv('c2c', [S(cat, 0, 10), S(c1, 0, 24), S(c0, 0, 16)], 12, 3, dst=cat, dst_choff=38, bn=True)
+    c3 = sp.conv('c3', [S(cat, 0, 50)], 20, 1, bn=True)
+    p = sp.pool('p', c3)
+    c4 = sp.conv('c4', [S(p, 0, 20)], 34, 3, bn=True)
+    up = sp.upsample('up', c4, c3)
+    c5 = sp.conv('c5', [S(up, 0, 34), S(c3, 0, 20)], 22, 1, bn=True)
+    fin = sp.conv('fin', [S(c5, 0, 22), S(cat, 10, 28)], 11, 1, relu=False, bn=False)
+    sp.head(fin)
+    return sp
+
+
+def train_plan_tables(blob, in_ch, n_cls, b, h, w, out_h, out_w):
+    """pf_debug_train_plan (no GPU) under the process-wide options as they are: (regions [n][4] = kind, index, offset, bytes;
+    steps [m][5]; (dy slots, side streams)) - include/pfhip.h documents the rows"""
+    import numpy as np
+    L = _lib.load()
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    nr, ns, consts = ctypes.c_int(), ctypes.c_int(), (ctypes.c_int * 2)()
+    args = (buf, len(blob), in_ch, n_cls, b, h, w, out_h, out_w)
+    _lib.check(L.pf_debug_train_plan(*args, None, 0, ctypes.byref(nr), None, 0, ctypes.byref(ns), consts), 'pf_debug_train_plan')
+    regions, steps = np.zeros((nr.value, 4), dtype=np.int64), np.zeros((ns.value, 5), dtype=np.int32)
+    _lib.check(L.pf_debug_train_plan(*args, regions.ctypes.data, nr.value, ctypes.byref(nr), steps.ctypes.data, ns.value, ctypes.byref(ns),
+                                     consts), 'pf_debug_train_plan')
+    assert (nr.value, ns.value) == (len(regions), len(steps))
+    return regions, steps, tuple(consts)
+
+
+def plan_path_stats(steps):
+    """pf_train_path_stats as a step counts it: per slot, the steps of the table whose stats bits have that bit"""
+    bits = steps[steps[:, 0] == 0][:, 4]
+    return [int(((bits >> k) & 1).sum()) for k in range(8)]
+
+
 def mini_torch(sp, params, x, labels, dtype=torch.float64, pre=None):
     """The same op table through torch autograd on the CPU, with gradients of every tensor retained: in float64 the checker, in
     float32 (ATen) the yardstick of what fp32 rounding alone does.  ``pre``: a dict that receives every conv's output before

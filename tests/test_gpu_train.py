@@ -426,31 +426,6 @@ def test_bgmodel_training_loss_is_a_drop_in_for_the_reference_loop():
     assert (out['orig_size_logits'].cpu() - want['orig_size_logits']).abs().max() <= 1e-3
 
 
-def _mini_net():
-    """Every op kind of the training path in one small, well-conditioned network: stride-2 stem, 3x3 convs with one and
-    two input ranges, a conv writing into a slice of a wider tensor, 1x1 conv, pool, upsample + 1x1 over [up, skip],
-    plain final conv, bilinear head."""
-    from panoptic_forecasting_amd import hardnet_arch as arch
-    from tests.helpers import MiniSpec
-    sp = MiniSpec(6)
-    S = arch.Src
-    c0 = sp.conv('c0', [S(0, 0, 6)], 16, 3, stride=2, bn=True)
-    c1 = sp.conv('c1', [S(c0, 0, 16)], 24, 3, bn=True)
-    cat = sp.tensor('cat', 28 + 10 + 12)
-    sp.conv('c2', [S(c1, 0, 24), S(c0, 0, 16)], 28, 3, dst=cat, dst_choff=10, bn=True)
-    sp.conv('c2b', [S(c1, 4, 18)], 10, 3, dst=cat, dst_choff=0, bn=True)
-    # like the last layer of a HarDBlock: three ranges, the first one a slice of the tensor it writes into
-    sp.conv('c2c', [S(cat, 0, 10), S(c1, 0, 24), S(c0, 0, 16)], 12, 3, dst=cat, dst_choff=38, bn=True)
-    c3 = sp.conv('c3', [S(cat, 0, 50)], 20, 1, bn=True)
-    p = sp.pool('p', c3)
-    c4 = sp.conv('c4', [S(p, 0, 20)], 34, 3, bn=True)
-    up = sp.upsample('up', c4, c3)
-    c5 = sp.conv('c5', [S(up, 0, 34), S(c3, 0, 20)], 22, 1, bn=True)
-    fin = sp.conv('fin', [S(c5, 0, 22), S(cat, 10, 28)], 11, 1, relu=False, bn=False)
-    sp.head(fin)
-    return sp
-
-
 @pytest.mark.parametrize('taps', [1, 0, 2])
 @pytest.mark.parametrize('size', [(24, 40), (34, 70)])
 def test_mini_network_training_step_vs_autograd(size, taps):
@@ -507,11 +482,8 @@ def test_forward_on_packed_pairs_is_the_same_step_to_rounding():
     assert _rel(got[1][1], got[0][1]) <= 3e-2
 
 
-def _mini_network_step(size):
-    from tests.helpers import MiniTrain, mini_torch as _mini_torch
-    from panoptic_forecasting_amd import lib as pflib
-    h, w = size
-    sp = _mini_net()
+def _mini_data(sp, h, w):
+    """(params, x [3, 6, h, w], labels [3, 2h - 3, 2w + 1]) of the mini network's step: CPU tensors, a function of the size alone"""
     g = torch.Generator().manual_seed(17)
     params = {}
     for op in sp.conv_ops():
@@ -525,6 +497,45 @@ def _mini_network_step(size):
     x = torch.randn(3, 6, h, w, generator=g)
     lab = torch.randint(0, 12, (3, 2 * h - 3, 2 * w + 1), generator=g)
     lab[lab == 11] = 255
+    return params, x, lab
+
+
+@pytest.mark.parametrize('side,s4', [(0, 0), (0, 1), (1, 0), (1, 1)])
+def test_the_inspected_plan_is_the_plan_that_runs(side, s4):
+    """pf_debug_train_plan (tests/test_train_plan_host.py asserts on its tables without a device) against a real plan created under
+    the same options: the same workspace size, and the path statistics summed from its step table are those of a real step."""
+    import ctypes
+    from tests.helpers import MiniTrain, mini_net, plan_path_stats, train_plan_tables
+    from panoptic_forecasting_amd import lib as pflib
+    L = pflib.load()
+    h, w = 34, 70
+    sp = mini_net()
+    params, x, lab = _mini_data(sp, h, w)
+    pflib.check(L.pf_set_option(b'train_side_stream', side), 'pf_set_option')
+    pflib.check(L.pf_set_option(b'train_forward_s4', s4), 'pf_set_option')
+    try:
+        net = MiniTrain(sp, params)
+        dims = (3, h, w) + tuple(lab.shape[-2:])
+        regions, steps, _ = train_plan_tables(net._buf.raw, sp.in_ch, sp.n_cls, *dims)
+        need = ctypes.c_size_t()
+        pflib.check(L.pf_train_workspace(net.t, *dims, ctypes.byref(need)), 'pf_train_workspace')
+        net.step(x.cuda(), lab.cuda())
+        ran = net.path_stats()
+        net.close()
+    finally:
+        L.pf_set_option(b'train_side_stream', 1)
+        L.pf_set_option(b'train_forward_s4', 0)
+    assert int(regions[-1, 3]) == need.value
+    assert plan_path_stats(steps) == ran and sum(ran) > 0, (plan_path_stats(steps), ran)
+    assert (ran[7] > 0) == bool(s4)
+
+
+def _mini_network_step(size):
+    from tests.helpers import MiniTrain, mini_net as _mini_net, mini_torch as _mini_torch
+    from panoptic_forecasting_amd import lib as pflib
+    h, w = size
+    sp = _mini_net()
+    params, x, lab = _mini_data(sp, h, w)
     want_loss, leaves, kept = _mini_torch(sp, params, x, lab)
     net = MiniTrain(sp, params)
     # a successful step leaves pf_last_error alone (no kernel is tried and then replaced by another one)

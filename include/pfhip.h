@@ -193,6 +193,32 @@ int pf_bg_augment(const uint8_t *seg_src, const uint8_t *label_src, const uint16
                   uint8_t *out_mask, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Batch assembly of the fg export path — what FGSceneDataset.__getitem__ (data/datasets/fg_scene_dataset.py:380-454)
+ * computes per scene after the has_gt rows and bbox_inds columns are selected, for all N instances of a batch in ONE launch:
+ * enqueue only, no workspace, a single kernel node.  N = 0 launches nothing.  T = 6 (else PF_EUNSUPPORTED), 0 <= T_in <= T.
+ *
+ *   bboxes [N,T,4] f32 ulbr as stored       feat_mask [N,T] u8       depth [N,T] f32       classes [N] i32 trainIds
+ *   feat_row [N,T_in] i32 row of feat_table or -1      feat_table [M,256,14,14] f32 (NULL when M = 0)
+ *   use_ulbr: keep ulbr, else convert_bbox_ulbr_cwh;  max_depth < 0: no depth bound;  filter_car_gap < 0: no car-gap filter
+ *   (_filter_car_gap :300-340 for class 13: it reads x0 / x1 from the boxes AFTER the conversion - restated, not repaired);
+ *   img_w: the image width the filter measures from (2048).  The two doubles are rounded to fp32 once, as torch rounds a
+ *   Python number it compares with a float32 tensor; img_w - filter_car_gap is formed in double and rounded once.
+ *
+ *   trajectories [N,T,8] (box, velocity)   bbox_masks, bbox_vel_masks, feat_masks, depth_masks [N,T] u8 (0/1)
+ *   depths [N,T,2] (depth, velocity)       classes_out [N] i64 = class - 11        one_hot_classes [N,8] f32
+ *   final_bboxes [N,4] = the last step's box      feats [N,T_in,256,14,14] = the gathered plane, or zeros
+ *
+ * Every step is one fp32 operation in the reference's order: all outputs are bit-identical to torch's.  A feat_row outside
+ * [0,M) is never followed as an address: its plane is zeros.  bboxes, feat_table, trajectories, one_hot_classes,
+ * final_bboxes and feats must be 16-byte aligned (the gather moves 16 bytes per lane and access).
+ */
+int pf_fg_assemble(const float *bboxes, const uint8_t *feat_mask, const float *depth, const int32_t *classes,
+                   const int32_t *feat_row, const float *feat_table, int N, int T, int T_in, int M, int use_ulbr,
+                   double max_depth, double filter_car_gap, int img_w, float *trajectories, uint8_t *bbox_masks,
+                   uint8_t *bbox_vel_masks, uint8_t *feat_masks, float *depths, uint8_t *depth_masks, int64_t *classes_out,
+                   float *one_hot_classes, float *final_bboxes, float *feats, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * fg -> panoptic merge — replaces the pasting loops of FGModel.predict_panoptic
  * (models/fg/fg_model.py:548-588; panoptic_ids=1, clear_things=1) and FGModel.predict_semantics (:455-480; panoptic_ids=0,
  * clear_things=0) together with model_utils.paste_mask (models/fg/model_utils.py:30-57).

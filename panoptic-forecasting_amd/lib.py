@@ -37,6 +37,8 @@ SIGNATURES = {
     'pf_hop_export': (_i, [_vp, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     'pf_hop_load': (_i, [_vp, _sz, _f, _f, _vp, _vp, _vp]),
     'pf_bg_augment': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    'pf_fg_assemble': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _c.c_double, _c.c_double, _i,
+                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pf_panoptic_merge_workspace': (_i, [_i, _c.POINTER(_sz)]),
     'pf_panoptic_merge': (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
                                _vp, _i, _vp, _sz, _vp]),

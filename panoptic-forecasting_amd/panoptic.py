@@ -144,6 +144,48 @@ def export_panoptic(seg, meta, result_dir, export_name, no_convert=False, annota
     return annotations
 
 
+def fill_missing_panoptic(result_dir, export_name, gt_split_dir, background_dir=None, annotations=None, shape=(1024, 2048)):
+    """The missing-file pass of export_results (export_cityscapes_panoptic_results.py:124-169): every
+    ``*_gtFine_labelIds.png`` under ``gt_split_dir/<city>`` without a prediction in ``<result_dir>/<export_name>`` gets one.  Where
+    ``background_dir/<city>/<same name>`` exists, that trainId map is written converted to ids and encoded (255 -> 0; converted
+    whatever ``--no_convert`` says, as in the reference), with its segments; otherwise an all-zero image with empty
+    ``segments_info``.  Appends to ``annotations``; returns the number of files written.  (The reference's ``nobg`` is
+    undefined when the folder holds no city: here the warning is printed, or not, without that.)"""
+    import glob
+    from PIL import Image
+    annotations = [] if annotations is None else annotations
+    seg_dir = os.path.join(result_dir, export_name)
+    os.makedirs(seg_dir, exist_ok=True)
+    lut = np.full(256, -1, np.int64)
+    lut[:len(TRAINID2ID)] = TRAINID2ID
+    lut[255] = 0
+    count, nobg = 0, False
+    for city in sorted(os.listdir(gt_split_dir)):
+        for gt_path in sorted(glob.glob(os.path.join(gt_split_dir, city, '*_gtFine_labelIds.png'))):
+            fname = os.path.basename(gt_path)
+            stem = '%s_%s_%s' % tuple(fname.split('_')[:3])
+            out_name = os.path.join(seg_dir, stem + '_pred_panoptic.png')
+            if os.path.exists(out_name):
+                continue
+            count += 1
+            src = os.path.join(background_dir, city, fname) if background_dir else None
+            if src and os.path.exists(src):
+                ids = lut[np.array(Image.open(src)).astype(np.uint8)]
+                if (ids < 0).any():
+                    raise ValueError('%s holds labels that are neither trainIds (0..18) nor 255' % src)
+                info = [{'category_id': int(v), 'id': int(v)} for v in np.unique(ids) if v != 0]
+            else:
+                nobg = True
+                ids, info = np.zeros(shape, np.int64), []
+            rgb = np.stack([ids % 256, ids // 256, ids // 65536], -1).astype(np.uint8)
+            annotations.append({'file_name': stem + '_pred_panoptic.png', 'image_id': stem, 'segments_info': info})
+            Image.fromarray(rgb).save(out_name)
+    if nobg:
+        print('WARNING: NO BG DIR FOUND')
+    print('NUM MISSING: ', count)
+    return count
+
+
 def write_annotations(annotations, result_dir, export_name):
     """:166-169."""
     path = os.path.join(result_dir, '%s.json' % export_name)

@@ -11,7 +11,7 @@ using namespace pf;
 
 namespace pf {
 PlanOptions g_plan_opt;
-// process-wide only: plain globals where their readers live (train_plan.hip, train_kernels.hip)
+// process-wide only: plain globals where their readers live (train_plan.hip, train_wgrad.hip)
 extern int g_opt_train_side, g_opt_wgrad_taps, g_opt_train_s4, g_opt_train_kacc, g_opt_train_table_batch, g_opt_up_two_pass;
 }
 

@@ -38,7 +38,7 @@ struct pf_train {
 };
 
 namespace pf {   // the process-wide switches of the training step (pf_set_option: plan_create.hip)
-int g_opt_up_two_pass = 1;         // upsample_bwd_two_pass: the bilinear transposes of large planes as rows-then-columns passes (train_kernels.hip)
+int g_opt_up_two_pass = 1;         // upsample_bwd_two_pass: the bilinear transposes of large planes as rows-then-columns passes (train_resample.hip)
 int g_opt_train_table_batch = 0;   // train_table_batch: batch size the rows of train_tuned.inc are looked up with (0 = the call's own)
 int g_opt_train_kacc = 1;          // train_blocked_sum: per-round partial sums in the 3x3 convolutions of a training step (conv_dma.hip: KACC)
 int g_opt_train_s4 = 0;            // train_forward_s4: the forward convolutions of a training step on conv_s4 with blocked sums (train_s4.hip); opt-in

@@ -11,7 +11,7 @@
 //     clipped weight;
 //   * activations are fp32 NCHW (BatchNorm, pooling, the weight gradients read them): s4_pack_act_kernel writes the packed-pair
 //     SHADOW of every slice a producer finishes, for the tensors a packed-pair convolution reads; odd-width levels (50, 25 pixels at
-//     800 x 800) get rows padded to a multiple of 4 with zero pad columns = the convolution's own zero padding (train_kernels.hip);
+//     800 x 800) get rows padded to a multiple of 4 with zero pad columns = the convolution's own zero padding (train_resample.hip);
 //   * outputs stay fp32 (pre-BatchNorm y): conv_s4's fp32 epilogue; the 3x3 layers run conv_s4_blocked_kernel (conv_s4_kernel.inc with
 //     KACC: per-round partial sums, like the fp32 step) - the forward pass is then 0.81-0.95 x as far from float64 as torch-CPU fp32.
 // Measured: profiles/r06_experiments.md (section 11).

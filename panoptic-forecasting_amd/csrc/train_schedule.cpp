@@ -6,7 +6,7 @@
 // (conv_dma.hip; widths that are not a multiple of 4 on copies with padded rows) with the weights re-packed on the device
 // every step (forward order, or transposed + flipped per input range; stride-2 backward-data = stride-1 conv over the
 // zero-stuffed gradient; a tensor's gradient accumulates over its consumers in the store), backward-weight through the
-// LDS-tiled wgrad kernels of train_kernels.hip.
+// LDS-tiled wgrad kernels of train_wgrad.hip.
 #include <algorithm>
 #include <cstring>
 

@@ -2,7 +2,7 @@
 //
 //   dW[co][ci][ky][kx] = sum over (b, iy, ix) of dy[b][co][iy - ky + 1][ix - kx + 1] * x[b][ci][iy][ix]
 //
-// train_kernels.hip: wgrad_tiled_kernel gives every tap its own accumulator: M = 16 couts per v_mfma_f32_16x16x4_f32, so a layer of
+// train_wgrad.hip: wgrad_tiled_kernel gives every tap its own accumulator: M = 16 couts per v_mfma_f32_16x16x4_f32, so a layer of
 // 10 output channels fills 10 of 16 matrix rows and one of 18 fills 18 of 32 (HarDNet's odd layers have 10, 16, 18, 24 ... outputs,
 // the even ones 18, 28, 30, 46 ...: models/bg/hardnet.py:177-194).  Here the matrix rows are the (cout, tap) PAIRS, packed densely:
 // row j = 9 co + tap, 16 rows per instruction, so 10 outputs are 90 rows = 6 instructions per four pixels instead of 9, 18 are 11
@@ -227,7 +227,7 @@ bool wgrad_taps_wanted(int mode, int ks, int stride, int Cin, int Cout, int Hin,
     return cob <= 19;
 }
 
-// workgroups = cout chunks x cin groups x slabs; `max_slabs` = what the partial buffer was sized for (train_kernels.hip: wgrad_slabs)
+// workgroups = cout chunks x cin groups x slabs; `max_slabs` = what the partial buffer was sized for (train_wgrad.hip: wgrad_slabs)
 int launch_wgrad_taps(const ConvArgs &a, const float *dy, int B, int max_slabs, int co_pad, int ci_pad, float *partial, int *slabs_used, hipStream_t s) {
     const int chunks = (a.Cout + 31) / 32, cob = (a.Cout + chunks - 1) / chunks;
     const int t_need = (cob * 9 + 15) / 16;

@@ -126,7 +126,7 @@ def test_probe_elementwise_bar_bites_where_relative_l2_does_not(case):
 
 
 def _bn_emulated(y, g, gamma, beta, squares64, sums64, eps=1e-5, momentum=0.1):
-    """What the 4-wide BatchNorm kernels of csrc/train_kernels.hip make of a conv output ``y`` (fp32 [B, C, H, W], H * W % 4 == 0)
+    """What the 4-wide BatchNorm kernels of csrc/train_bn.hip make of a conv output ``y`` (fp32 [B, C, H, W], H * W % 4 == 0)
     and the gradient ``g`` arriving at the layer's output, operation for operation on the CPU.  Per quad the sum either in fp32,
     (x0 + x1) + (x2 + x3), or of the four widened values (``sums64``); the sum of squares either as one fp32 expression
     (x0 x0 + x1 x1) + (x2 x2 + x3 x3) or as four fp64 products (``squares64``); quads added in fp64; var = E[x^2] - mean^2 in fp64;

@@ -438,6 +438,16 @@ int pf_odom_backward(const float *packed, int flags, int B, int T_in, int T_out,
  *                   weights for it -, 2 = wherever the two forms exist (A/B runs, tests); the workspace grows by one scratch region
  *                   of the largest such consumer (fp32); results agree with the two plain launches within 1e-5 (1 + max)
  *                   (tests/test_gpu_share_s.py);
+ *   "fold_final"    (default 1) a 3x3 packed-pair conv of two cout tiles whose slice has exactly one reader - the next op, a 1x1 conv
+ *                   of at most 16 couts without ReLU into fp32 whose other channels (at most 32, in front of the slice, both starting
+ *                   on a 4-channel boundary) were stored earlier - also computes that conv (csrc/conv_s4.hip, conv_s4_tail_kernel): its
+ *                   finished values stay in registers as the fp16 pair the reader would load, are multiplied by the reader's weights
+ *                   after the centre pixels of the reader's other channels, and the reader's output is stored; the slice never is,
+ *                   the reader's launch goes away, and pf_hardnet_tensor_read of the tensor the slice belongs to is refused
+ *                   ("elided").  In FC-HarDNet-70: the last decoder layer and finalConv.  1 = where it measured faster
+ *                   (csrc/conv_select.cpp::tail_wanted), 0 = never - and a plan CREATED while the process-wide value is 0 packs no
+ *                   weights for it -, 2 = wherever the form exists (A/B runs, tests); results agree with the two launches within
+ *                   1e-5 (1 + max) (tests/test_gpu_fold_final.py);
  *   "train_blocked_sum" (default 1; process-wide only) the 3x3 convolutions of a training step add every round of 8 input channels
  *                   into a second accumulator set (blocked summation, like ATen's): forward activations 0.79-0.95 x as far from
  *                   float64 as torch-CPU fp32; 0 = one fp32 chain over all 9 Cin terms;
@@ -589,6 +599,11 @@ int pf_debug_conv_ranges(int form, int ks, int kc, int pad, int n_src, int n_cas
  * offset and rounds of its add launch's ("share_s"; 0 = the op has none). */
 int pf_debug_plan_arena(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
                         long long *table, int table_ops);
+/* Host only, as pf_debug_plan_arena: the region that plan keeps beside its arena for the tail form ("fold_final") - its first 64 floats
+ * are zeros, *n_floats = 0 when no op has the form - copied to out when cap >= *n_floats, and per op of the table (table_ops numbers,
+ * nullable) the offset in floats of the 1x1 reader's fragments, kept on the 3x3 op: [chunk 2][term 2][lane 64][8 fp16]; 0 = none. */
+int pf_debug_plan_tail(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                       long long *table, int table_ops);
 /* Host only, no device involved, nothing enqueued (tests): the plan of one pf_train_forward_backward of a training plan created now
  * from this blob - the workspace layout and the schedule of a step on B dense inputs of H x W with labels of out_h x out_w, under
  * the process-wide options as pf_train_create and a step read them, without pf_train_autotune; the addresses it is built against

@@ -69,6 +69,16 @@ struct ConvArgs {
     int share_off;           // share form: first matrix row of C's part = P's couts rounded up to 4
     int share_cout;          // C's output channels
     float share_scale;       // share form: C's acc_scale (this launch's acc_scale is P's)
+    // ---- the tail form (conv_s4.hip: launch_conv_s4_tail; zero for every other launch): this launch's slice has one reader, a 1x1 conv
+    //      R without ReLU into fp32 NCHW, which is linear in its input: the launch keeps its values in registers, multiplies them (and the
+    //      centre pixels of R's other channels, read from their packed planes) by R's weights and stores R's output; its slice is never stored
+    const float *tail_w;     // pack_conv_weights_tail(): R's A fragments, [chunk 0: R's other channels, chunk 1: this launch's couts][term][64 lanes][8 fp16]
+    const float *tail_bias;  // R's bias, zero padded to 16
+    float tail_scale;        // R's acc_scale
+    const float *tail_src;   // R's other channels: the packed tensor they live in, tail_c4 channel groups (term stride = tail_c4 planes), ...
+    int tail_c4, tail_g0, tail_gn;   // ... its groups tail_g0 .. tail_g0 + tail_gn - 1 (tail_gn <= 8: one K = 32 chunk; 0: none)
+    float *tail_dst;         // R's destination [B, tail_ctotal, Hout, Wout] fp32, R's couts (<= 16) from channel tail_choff on
+    int tail_cout, tail_ctotal, tail_choff;
 };
 
 // ---- the two-term operand split of conv_split.hip / conv_s4.hip ------------------------------------------------------
@@ -299,6 +309,15 @@ int launch_conv_s4_share(const ConvArgs &a, int nt, int B, hipStream_t stream);
 int launch_conv_s4_add(const ConvArgs &a, int nt, int B, hipStream_t stream);
 inline int share_row0(int p_cout) { return (p_cout + 3) / 4 * 4; }   // a lane's four couts never straddle the two convs
 bool share_wanted(int p_cin, int p_cout, int c_cin, int c_cout, int h, int w, int B, int mode);
+// the tail form: a 3x3 launch of two cout tiles per workgroup on 8 x 32 tiles that also computes the 1x1 conv R reading its slice
+// (ConvArgs::tail_..) and stores R's output instead of its own.  tail_wanted (conv_select.cpp): mode = the plan's fold_final option
+// (0 never, 1 the measured rule, 2 wherever the form exists); cin, cout = the 3x3 conv's, r_cout = R's
+int launch_conv_s4_tail(const ConvArgs &a, int B, hipStream_t stream);
+bool tail_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode);
+constexpr int kTailChunks = 2;   // K = 32 chunks of R's A fragments: R's other channels (at most 8 groups), then the launch's 32 couts
+inline size_t tail_packed_floats() { return (size_t)kTailChunks * 2 * 64 * 4; }
+// R's weights (OIHW, 1x1, already scaled by its 2^k) in the tail form's K order (conv_ranges.h: order_tail, tail_channel)
+void pack_conv_weights_tail(const float *w_oihw, int cin, int cout, const KOrder &k, float *out);
 
 // conv_pair.hip: an odd HarDBlock layer P = conv3x3(S) computed inside its consumer C = conv3x3(P ++ S ++ others) (hardnet.py:177-194)
 struct PairArgs {

@@ -35,6 +35,22 @@ KOrder order_add(const BlobSrc *src, int n) {
     return k;
 }
 
+KOrder order_tail(const BlobSrc &src, int slice_choff, int slice_ch) {
+    KOrder k;
+    k.n = 2;
+    const int front = slice_choff - (int)src.choff;
+    k.r[0] = KRange{0, src.tensor, (int)src.choff, front, 0};
+    k.r[1] = KRange{0, src.tensor, slice_choff, slice_ch, front};
+    return k;
+}
+
+int tail_channel(const KOrder &k, int chunk, int g, int e) {
+    const KRange &r = k.r[chunk];
+    // chunk 0: channel (e & 3) of group entry 2g + e / 4 (the range starts on a group); chunk 1: cout 4g + (e & 3) of cout tile e / 4
+    const int c = chunk == 0 ? 4 * (2 * g + e / 4) + (e & 3) : 16 * (e / 4) + 4 * g + (e & 3);
+    return c < r.ch ? r.cstart + c : -1;
+}
+
 int range_starts(const int *len, int n, int unit, int *out) {
     out[0] = 0;
     for (int j = 0; j < kConvMaxSrc; ++j) out[j + 1] = out[j] + (j < n ? (len[j] + unit - 1) / unit : 0);

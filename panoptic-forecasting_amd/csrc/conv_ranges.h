@@ -25,6 +25,13 @@ KOrder order_plain(const BlobSrc *src, int n);
 KOrder order_pair(const BlobSrc *src, int n);
 // the add launch of conv_s4.hip: the same consumer without S, its range 1
 KOrder order_add(const BlobSrc *src, int n);
+// the tail form of conv_s4.hip: the single range of a 1x1 reader R, cut at the slice [slice_choff, slice_choff + slice_ch) that ends it:
+// [R's other channels (in front of the slice; may be empty), the slice]
+KOrder order_tail(const BlobSrc &src, int slice_choff, int slice_ch);
+// ... and its K order: R's input channel at K position e (0..7) of lane group g in chunk 0 (the other channels: group entries 2g and
+// 2g + 1 of range 0, four channels each) or chunk 1 (the slice as the producing launch holds it: couts 4g .. 4g + 3 of its first cout
+// tile, then of its second); -1 = no channel (the weight is zero)
+int tail_channel(const KOrder &k, int chunk, int g, int e);
 
 // starts of n ranges of len[j] elements, each padded to whole units of `unit`, counted in units: out[j] for j <= kConvMaxSrc (out[n]
 // and the tail = the total, which is returned)

@@ -6,6 +6,9 @@
 //   S4_KERNEL_EPI    0 | 1 "share" | 2 "add": the epilogue (DESIGN.md 4; ConvArgs::share ..).  share: matrix rows from a.share_off on are
 //                    ANOTHER conv's sums over this launch's source, stored as fp32 units of four channels (acc * a.share_scale; no bias,
 //                    no ReLU, no range report); the rows below it take the plain epilogue.  add: v = fma(acc, acc_scale, stored) + bias
+//                    3 "tail" (NT = 2; ConvArgs::tail_..): the finished values stay in registers as the two terms their single reader, a
+//                    1x1 conv R, would read back, and are multiplied by R's weights together with the centre pixels of R's other channels;
+//                    R's output is stored (fp32 NCHW), this conv's slice is not
 template <int NT, int TW_, int TH_, int KS_>
 __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAME(ConvArgs a) {
     [[maybe_unused]] constexpr int KACC = S4_KERNEL_KACC;
@@ -317,6 +320,41 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 }
             }
         }
+        // tail: the second conv R's operands that do not come out of this launch's accumulators, loaded in front of the same wait: its A
+        // fragments (one 16-row tile, two terms, chunk 0 = R's other channels, chunk 1 = this launch's couts; L2-resident) and bias, and the
+        // lane's B fragments of chunk 0 - lane group g supplies group entries 2g and 2g + 1 of R's other channels at the CENTRE pixel of
+        // every M-tile, straight from the packed planes (entries past the range, pixels outside the image: the zero page)
+        [[maybe_unused]] s4_h8 tw_h[EPI == 3 ? 2 : 1], tw_m[EPI == 3 ? 2 : 1];
+        [[maybe_unused]] s4_h4 to_h[EPI == 3 ? C::MP : 1][2], to_m[EPI == 3 ? C::MP : 1][2];
+        [[maybe_unused]] s4_f32x4 tbias = s4_f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (EPI == 3) {
+            static_assert(NT == 2, "a lane's 4 + 4 split values of two cout tiles are one K slice of the second conv");
+            const s4_h8 *tw = reinterpret_cast<const s4_h8 *>(a.tail_w);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                tw_h[c] = tw[(c * 2 + 0) * 64 + lane];
+                tw_m[c] = tw[(c * 2 + 1) * 64 + lane];
+            }
+            tbias = *reinterpret_cast<const s4_f32x4 *>(a.tail_bias + 4 * (lane >> 4));
+            const size_t tstride = (size_t)a.tail_c4 * plane_bytes;
+            const char *tbase = reinterpret_cast<const char *>(a.tail_src) + (size_t)b * 2 * tstride;
+#pragma unroll
+            for (int m = 0; m < C::MP; ++m) {
+                const int mt = wave * C::MP + m;
+                const int oy = tileY * C::TH + mt / C::MTR;
+                const int ox = tileX * C::TW + (mt % C::MTR) * 16 + (lane & 15);
+                const bool in = oy < a.Hout && ox < a.Wout;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int e = 2 * (lane >> 4) + h;
+                    const bool real = in && e < a.tail_gn;
+                    const char *p = real ? tbase + (size_t)(a.tail_g0 + e) * plane_bytes + ((size_t)oy * a.Wout + ox) * 8
+                                         : reinterpret_cast<const char *>(a.zero_page);
+                    to_h[m][h] = *reinterpret_cast<const s4_h4 *>(p);
+                    to_m[m][h] = *reinterpret_cast<const s4_h4 *>(real ? p + tstride : p);
+                }
+            }
+        }
         __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0), expcnt / lgkmcnt untouched
         const int g = lane >> 4, px = lane & 15;
         const size_t hw = (size_t)a.Hout * a.Wout;
@@ -356,6 +394,42 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
             const int mt = wave * C::MP + m;
             const int oy = tileY * C::TH + mt / C::MTR;
             const int ox = tileX * C::TW + (mt % C::MTR) * 16 + px;
+            if constexpr (EPI == 3) {
+                // this launch's values as the plain epilogue would store them (rows past its couts: zero weights, zero bias -> 0), split
+                // into the two terms R would read back; the lane's 4 + 4 values of the two cout tiles are K slice g of R's chunk 1 (the
+                // packer's order: conv_ranges.cpp tail_channel).  Every lane takes part in the matrix instructions; lanes whose pixel
+                // lies outside the image report nothing to the range guard and store nothing
+                const bool in = oy < a.Hout && ox < a.Wout;
+                s4_h4 xh[2], xm[2];
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    s4_f32x4 v = acc[m][n];
+                    const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(bias_lds + n * 16 + 4 * g);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r] * a.acc_scale + b4[r], relu_lo);
+                    const float vm = range_acc(vmax, v[0], v[1], v[2], v[3]);
+                    vmax = in ? vm : vmax;
+                    split_terms4(v, xh[n], xm[n]);
+                }
+                const s4_h8 x1h = s4_join(xh[0], xh[1]), x1m = s4_join(xm[0], xm[1]);
+                const s4_h8 x0h = s4_join(to_h[m][0], to_h[m][1]), x0m = s4_join(to_m[m][0], to_m[m][1]);
+                // R's sum: chunk 0 (its other channels), then chunk 1 (this launch's), three products each, one fp32 accumulator
+                s4_f32x4 t = s4_f32x4{0.f, 0.f, 0.f, 0.f};
+                t = PF_MFMA_SPLIT(tw_h[0], x0m, t);
+                t = PF_MFMA_SPLIT(tw_m[0], x0h, t);
+                t = PF_MFMA_SPLIT(tw_h[0], x0h, t);
+                t = PF_MFMA_SPLIT(tw_h[1], x1m, t);
+                t = PF_MFMA_SPLIT(tw_m[1], x1h, t);
+                t = PF_MFMA_SPLIT(tw_h[1], x1h, t);
+                if (in) {
+                    const size_t pix = (size_t)oy * a.Wout + ox;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (4 * g + r < a.tail_cout)
+                            a.tail_dst[((size_t)b * a.tail_ctotal + a.tail_choff + 4 * g + r) * hw + pix] = t[r] * a.tail_scale + tbias[r];
+                }
+                continue;
+            }
             if (oy >= a.Hout || ox >= a.Wout) continue;
             const size_t pix = (size_t)oy * a.Wout + ox;
 #pragma unroll

@@ -108,6 +108,20 @@ bool share_wanted(int p_cin, int p_cout, int c_cin, int c_cout, int h, int w, in
     return p_cout == 10 && c_cout == 18 && p_cin >= 48 && (long)B * h * w >= 4194304;
 }
 
+// conv_s4.hip tail (a 3x3 conv's launch also computes the 1x1 conv that alone reads its slice) instead of the two plain launches?  mode =
+// plan option fold_final: 0 never, 2 wherever the form exists (tests, A/B runs), 1 (default): only the class of launches whose folded
+// runs MEASURED faster than the two plain launches in every run (MI355X, 1024x2048 network, same box, fold_final 0 / 2 alternated:
+// profiles/r08_experiments.md): 91 -> 28 -> 11 at 256x512, B = 4 .. 32 - 99 -> 75 us, 200 -> 150 us, .., 745-755 -> 576-579 us: the 1x1
+// launch's time less 2-3 % of the 3x3 launch's.  Launches of more than 4 194 304 pixels and other channel counts were not measured and
+// keep their two launches; B = 2 (262 144 pixels) won too, 57 -> 42 us in both of its runs, and is left out: the parity and suite runs
+// of the change were made with the rule as it stands (B = 1 lies in pair_wanted's window: that layer runs inside conv_pair)
+bool tail_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode) {
+    if (mode >= 2) return true;
+    if (mode <= 0) return false;
+    const long px = (long)B * h * w;
+    return cin == 91 && cout == 28 && r_cout == 11 && px >= 524288 && px <= 4194304;
+}
+
 ConvChoice choose_conv(int ks, int stride, int cin, int cout, int hout, int wout, int B, int need, int use_tuned) {
     if (stride != 1) return ConvChoice::dma();           // shape by its cost model
     // The table was measured at B = 1, 2, 4, 8, 16 and (round 5, the strict-fp32 model at the headline's sub-batch) 32; a layer

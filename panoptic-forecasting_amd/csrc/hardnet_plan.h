@@ -39,6 +39,10 @@ struct ConvPlan {
     // [P's rows; C's rows over the columns of S] over S (share_a_tiles cout tiles), and C without the columns of S (share_b_rounds rounds)
     size_t share_a_off = 0, share_b_off = 0;
     int share_a_tiles = 0, share_b_rounds = 0;
+    // the tail form (conv_s4.hip), kept on the PRODUCER (op i; the 1x1 conv that alone reads its slice is op i + 1) and packed only by
+    // plans created with fold_final != 0: the reader's A fragments, an offset in floats into the plan's tail region (pf_plan::dev_tail,
+    // whose first 64 floats are zeros: 0 = the op has none).  A region of its own: the weight arena stays what it was without the form
+    size_t tail_off = 0;
 };
 
 // The switches a plan carries (include/pfhip.h documents each), with their defaults.  g_plan_opt is the process-wide set
@@ -55,6 +59,9 @@ struct PlanOptions {
     int fuse_pairs = 1;        // conv_pair.hip: an odd HarDBlock layer runs inside its consumer where both read / write packed pairs (0 = two launches)
     int share_s = 1;           // conv_s4.hip share / add: an odd HarDBlock layer's launch also sums its consumer's rows over their common source
                                // (0 = off, and a plan created with 0 packs nothing for it; 1 = conv_select.cpp::share_wanted; 2 = wherever built)
+    int fold_final = 1;        // conv_s4.hip tail: a 3x3 conv whose slice has one reader, a small 1x1 conv into fp32, also computes that conv
+                               // and never stores its slice (0 = off, and a plan created with 0 packs nothing for it; 1 = conv_select.cpp::tail_wanted;
+                               // 2 = wherever built)
 };
 
 struct pf_plan {
@@ -64,8 +71,11 @@ struct pf_plan {
     float *dev_weights = nullptr;
     uint8_t *dev_lut = nullptr;
     size_t dev_floats = 0;
+    std::vector<float> tail_host;   // the tail form's packings (ConvPlan::tail_off), empty when the plan has none ...
+    float *dev_tail = nullptr;      // ... and their upload
     PlanOptions opt;             // read only by forwards of this plan
-    // formats of the last forward (pf_hardnet_tensor_read): 1 = S4, 0xFF = elided (never stored: conv_front.hip)
+    // formats of the last forward (pf_hardnet_tensor_read): 1 = S4, 0xFF = elided (never stored: conv_front.hip), 0xFE = its last
+    // slice elided (never stored: the tail form of conv_s4.hip)
     mutable std::vector<uint8_t> last_fmt;
     // range normalisation (conv_mfma.h): tensor t, channel c is stored multiplied by chan_scale[t][c] (a power of two; 1 for
     // the network input, the head's input and every tensor no convolution reads); inv_scale_off[t] = offset in dev_weights
@@ -96,5 +106,8 @@ int layout(const pf_plan *p, int B, int H, int W, std::vector<Dims> &d, std::vec
 
 // ops i (P) and i + 1 (C) form a pair conv_pair.hip can run as one launch (plan_create.hip)
 bool is_conv_pair(const NetTable &t, size_t i);
+// op i is a 3x3 conv whose slice has exactly one reader, op i + 1, a 1x1 conv the tail form of conv_s4.hip can compute in op i's
+// launch (plan_create.hip)
+bool is_conv_tail(const NetTable &t, size_t i);
 
 }  // namespace pf

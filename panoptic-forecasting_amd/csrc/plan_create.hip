@@ -36,6 +36,7 @@ const Option kOptions[] = {
     {"fuse_front", nullptr, &PlanOptions::fuse_front, nullptr, true, true, false},   // (0: stem -> conv_split -> conv_dma stride 2, three kernels)
     {"fuse_pairs", nullptr, &PlanOptions::fuse_pairs, nullptr, true, true, false},
     {"share_s", nullptr, &PlanOptions::share_s, nullptr, true, true, false},
+    {"fold_final", nullptr, &PlanOptions::fold_final, nullptr, true, true, false},
     {"profile_tag_ops", nullptr, &PlanOptions::profile_tag_ops, nullptr, true, true, false},
     {"table_batch", nullptr, &PlanOptions::table_batch, nullptr, false, true, true},
     {"normalize_ranges", nullptr, &PlanOptions::normalize_ranges, nullptr, true, false, false},
@@ -83,6 +84,33 @@ bool pf::is_conv_pair(const NetTable &t, size_t i) {
     for (uint32_t j = 0; j < C.n_src; ++j)
         if (C.src[j].choff & 1) return false;
     return conv_pair_supports((int)C.cout, (int)P.cout);
+}
+
+// L = op i, a 3x3 stride-1 conv of two cout tiles; R = op i + 1, the only op that reads L's slice: a 1x1 conv of at most 16 couts without
+// ReLU whose single range ends with that slice.  The slice and R's range start on a 4-channel boundary, R's other channels (in front of
+// the slice) are at most 8 groups - one K = 32 chunk of the tail form - and every one of them was written by an earlier op.  (That R's
+// destination is fp32 and which kernels L and R run on is known to the schedule only: hardnet_plan.hip.)
+bool pf::is_conv_tail(const NetTable &t, size_t i) {
+    if (i + 1 >= t.ops.size()) return false;
+    const BlobOp &L = t.ops[i], &R = t.ops[i + 1];
+    if (L.kind != OP_CONV || R.kind != OP_CONV || L.k != 3 || L.stride != 1 || R.k != 1 || R.stride != 1 || R.relu || R.n_src != 1) return false;
+    if (L.cout <= 16 || L.cout > 32 || R.cout > 16) return false;
+    for (uint32_t j = 0; j < L.n_src; ++j)
+        if (L.src[j].choff & 1) return false;
+    const BlobSrc &rs = R.src[0];
+    const uint32_t d0 = L.dst_choff, d1 = L.dst_choff + L.cout;
+    if (rs.tensor != L.dst || (rs.choff & 3) || (d0 & 3) || rs.choff > d0 || rs.choff + rs.ch != d1 || d0 - rs.choff > 32) return false;
+    std::vector<uint8_t> written(t.tensors[L.dst].channels, 0);
+    for (size_t j = 0; j < t.ops.size(); ++j) {
+        const BlobOp &o = t.ops[j];
+        if (j < i && (o.kind == OP_CONV || o.kind == OP_STEM) && o.dst == L.dst)
+            for (uint32_t c = o.dst_choff; c < o.dst_choff + o.cout && c < written.size(); ++c) written[c] = 1;
+        for (uint32_t s = 0; s < o.n_src && j != i + 1; ++s)   // another reader of the slice
+            if (o.src[s].tensor == L.dst && o.src[s].choff < d1 && o.src[s].choff + o.src[s].ch > d0) return false;
+    }
+    for (uint32_t c = rs.choff; c < d0; ++c)
+        if (!written[c]) return false;
+    return true;
 }
 
 // Cityscapes id -> trainId (public label table; ids outside 0..33 -> 0, like the zeros_like init of
@@ -307,6 +335,13 @@ void pack_share(const BlobOp &P, const float *wP, const BlobOp &o, const float *
     pack_conv_weights_s4(ws, (int)o.cin, (int)o.cout, 3, ko_b, 0, a.at(c.share_b_off));
 }
 
+// conv_s4.hip tail: o is the 3x3 conv, R the 1x1 conv that alone reads its slice (is_conv_tail), wr = R's weights times R's 2^k (the
+// power-of-two scale of every source channel folded in by normalize_ranges, as for R's own packings).  Into the plan's tail region
+void pack_tail(const BlobOp &o, const BlobOp &R, const float *wr, Arena &tail, ConvPlan &c) {
+    c.tail_off = tail.take(tail_packed_floats(), 16);
+    pack_conv_weights_tail(wr, (int)R.cin, (int)R.cout, order_tail(R.src[0], (int)o.dst_choff, (int)o.cout), tail.at(c.tail_off));
+}
+
 void pack_front(const BlobOp &o, const float *ws, Arena &a, ConvPlan &c) {   // 3x3 stride 2, one range
     const KOrder ko = order_plain(o.src, 1);
     c.front_off = a.take(s4_packed_floats(ko, (int)o.cout, 3, 0), 16);
@@ -344,6 +379,8 @@ void pack_stem(const BlobOp &o, const float *w, int n_cls, Arena &a, ConvPlan &c
 int build_plan_weights(pf_plan &p, const float *wts, std::vector<float> &host) {
     host.assign(64, 0.f);
     Arena a{host};
+    p.tail_host.assign(64, 0.f);
+    Arena tail{p.tail_host};
     const std::vector<BlobOp> &ops = p.net.ops;
     p.conv.assign(ops.size(), ConvPlan());
     for (size_t i = 0; i < ops.size(); ++i) {
@@ -366,6 +403,7 @@ int build_plan_weights(pf_plan &p, const float *wts, std::vector<float> &host) {
         if (i > 0 && is_conv_pair(p.net, i - 1)) pack_pair(ops[i - 1], wts + ops[i - 1].w_off, o, ws, a, c);
         if (i > 0 && p.opt.share_s && is_conv_pair(p.net, i - 1)) pack_share(ops[i - 1], wts + ops[i - 1].w_off, o, ws, a, c);
         if (o.k == 3 && o.stride == 2 && o.kind == OP_CONV && o.n_src == 1 && (o.src[0].choff & 3) == 0 && o.cout <= 32) pack_front(o, ws, a, c);
+        if (i > 0 && p.opt.fold_final && is_conv_tail(p.net, i - 1)) pack_tail(ops[i - 1], o, ws, tail, p.conv[i - 1]);   // (o = the reader)
         if (o.stride == 1) pack_wave(o, w, src_ch, a, c);
         if (o.kind == OP_STEM) pack_stem(o, w, (int)p.net.hdr.n_cls, a, c);
         a.take(0, 64);
@@ -379,6 +417,7 @@ int build_plan_weights(pf_plan &p, const float *wts, std::vector<float> &host) {
         for (size_t ch = 0; ch < p.chan_scale[t].size(); ++ch) host[p.inv_scale_off[t] + ch] = 1.0f / p.chan_scale[t][ch];   // exact: powers of two
         a.take(0, 64);
     }
+    if (p.tail_host.size() == 64) p.tail_host.clear();   // no op has the form
     return PF_OK;
 }
 
@@ -433,6 +472,8 @@ extern "C" int pf_hardnet_plan_create(const void *blob, size_t bytes, int in_ch,
     if (e == hipSuccess) e = hipMalloc((void **)&p->dev_lut, 256);
     if (e == hipSuccess) e = hipMemcpy(p->dev_weights, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->dev_lut, lut, 256, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !p->tail_host.empty()) e = hipMalloc((void **)&p->dev_tail, p->tail_host.size() * sizeof(float));
+    if (e == hipSuccess && p->dev_tail) e = hipMemcpy(p->dev_tail, p->tail_host.data(), p->tail_host.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         pf_hardnet_plan_destroy(p);
         return fail(PF_EHIP, "plan upload: %s", hipGetErrorString(e));
@@ -467,9 +508,31 @@ extern "C" int pf_debug_plan_arena(const void *blob, size_t bytes, int in_ch, in
     return PF_OK;
 }
 
+// Host only, as pf_debug_plan_arena: the tail region of that plan ("fold_final"; its first 64 floats are zeros) and per op of the table its
+// offset into it (0 = the op has no tail packing)
+extern "C" int pf_debug_plan_tail(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                                  long long *table, int table_ops) {
+    if (!blob || !n_floats) return fail(PF_EINVAL, "pf_debug_plan_tail: null argument");
+    pf_plan p;
+    p.opt = g_plan_opt;
+    int rc = parse_net_table(blob, bytes, in_ch, n_cls, p.net);
+    const size_t n_w = rc ? 0 : (bytes - p.net.hdr.weights_off) / sizeof(float);
+    if (!rc) rc = check_plan_ops(p.net, n_w);
+    if (rc) return rc;
+    const float *w0 = reinterpret_cast<const float *>((const char *)blob + p.net.hdr.weights_off);
+    std::vector<float> wnorm(w0, w0 + n_w), host;
+    normalize_ranges(&p, wnorm);
+    if ((rc = build_plan_weights(p, wnorm.data(), host))) return rc;
+    *n_floats = p.tail_host.size();
+    if (out && cap >= p.tail_host.size() && !p.tail_host.empty()) memcpy(out, p.tail_host.data(), p.tail_host.size() * sizeof(float));
+    for (int i = 0; table && i < table_ops && i < (int)p.conv.size(); ++i) table[i] = (long long)p.conv[i].tail_off;
+    return PF_OK;
+}
+
 extern "C" void pf_hardnet_plan_destroy(pf_plan *p) {
     if (!p) return;
     if (p->dev_weights) (void)hipFree(p->dev_weights);
     if (p->dev_lut) (void)hipFree(p->dev_lut);
+    if (p->dev_tail) (void)hipFree(p->dev_tail);
     delete p;
 }

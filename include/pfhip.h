@@ -448,6 +448,16 @@ int pf_odom_backward(const float *packed, int flags, int B, int T_in, int T_out,
  *                   (csrc/conv_select.cpp::tail_wanted), 0 = never - and a plan CREATED while the process-wide value is 0 packs no
  *                   weights for it -, 2 = wherever the form exists (A/B runs, tests); results agree with the two launches within
  *                   1e-5 (1 + max) (tests/test_gpu_fold_final.py);
+ *   "fold_down"     (default 1) a 3x3 packed-pair conv of two cout tiles in front of a 1x1 conv with ReLU of at most 64 couts and that
+ *                   conv's 2x2 average pool - the 1x1 conv's single range ends with the 3x3 conv's slice, its other channels (at most 32,
+ *                   in front of the slice, both starting on a 4-channel boundary) were stored earlier - also computes the 1x1 conv
+ *                   and the pool (csrc/conv_s4.hip, conv_s4_down_kernel): its finished values are stored as ever (other ops may read
+ *                   them) and, still in registers as the fp16 pair the reader would load, are multiplied by the reader's weights after
+ *                   the centre pixels of the reader's other channels; the pooled output is stored as packed pairs and the reader's
+ *                   launch goes away.  In FC-HarDNet-70: base.4.layers.3 and base.5.  1 = where it measured faster
+ *                   (csrc/conv_select.cpp::down_wanted), 0 = never - and a plan CREATED while the process-wide value is 0 packs no
+ *                   weights for it -, 2 = wherever the form exists (A/B runs, tests); results agree with the two launches within
+ *                   1e-5 (1 + max) (tests/test_gpu_fold_down.py);
  *   "train_blocked_sum" (default 1; process-wide only) the 3x3 convolutions of a training step add every round of 8 input channels
  *                   into a second accumulator set (blocked summation, like ATen's): forward activations 0.79-0.95 x as far from
  *                   float64 as torch-CPU fp32; 0 = one fp32 chain over all 9 Cin terms;
@@ -603,6 +613,10 @@ int pf_debug_plan_arena(const void *blob, size_t bytes, int in_ch, int n_cls, fl
  * are zeros, *n_floats = 0 when no op has the form - copied to out when cap >= *n_floats, and per op of the table (table_ops numbers,
  * nullable) the offset in floats of the 1x1 reader's fragments, kept on the 3x3 op: [chunk 2][term 2][lane 64][8 fp16]; 0 = none. */
 int pf_debug_plan_tail(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                       long long *table, int table_ops);
+/* Host only, as pf_debug_plan_tail: the region of the down form ("fold_down"), and per op the offset in floats of the 1x1 reader's
+ * fragments, kept on the 3x3 op: [cout tile 4][chunk 2][term 2][lane 64][8 fp16]; 0 = none. */
+int pf_debug_plan_down(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
                        long long *table, int table_ops);
 /* Host only, no device involved, nothing enqueued (tests): the plan of one pf_train_forward_backward of a training plan created now
  * from this blob - the workspace layout and the schedule of a step on B dense inputs of H x W with labels of out_h x out_w, under

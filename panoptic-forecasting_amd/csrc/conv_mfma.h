@@ -79,6 +79,15 @@ struct ConvArgs {
     int tail_c4, tail_g0, tail_gn;   // ... its groups tail_g0 .. tail_g0 + tail_gn - 1 (tail_gn <= 8: one K = 32 chunk; 0: none)
     float *tail_dst;         // R's destination [B, tail_ctotal, Hout, Wout] fp32, R's couts (<= 16) from channel tail_choff on
     int tail_cout, tail_ctotal, tail_choff;
+    // ---- the down form (conv_s4.hip: launch_conv_s4_down; zero for every other launch): the slice is stored as by the plain form and its
+    //      values, still in registers, also feed the 1x1 conv R behind it, which has a ReLU, up to 64 couts and a 2x2 average pool: R's
+    //      pooled output is stored (packed pairs, or fp32 where its readers want that) and R's launch goes away.  R's operands are the tail form's: tail_w =
+    //      pack_conv_weights_down() ([cout tile 4][chunk][term][64 lanes][8 fp16]), tail_bias (zero padded to whole tiles), tail_scale,
+    //      tail_src / tail_c4 / tail_g0 / tail_gn, tail_cout (<= 64); tail_dst / tail_ctotal / tail_choff are not used
+    float *down_dst;         // R's pooled destination: down_fmt = 1, the S4 layout [B][2 terms][down_c4][Hout / 2][Wout / 2][4] fp16 ...
+    int down_c4, down_choff, down_limit;   // ... its channel groups, R's first channel in it and the dst_limit of R's stores;
+    int down_fmt, down_ctotal;             // down_fmt = 0: fp32 [B, down_ctotal, Hout / 2, Wout / 2], R's couts from channel down_choff on
+    unsigned *down_status, *down_slot;     // range guard of the pooled values: the status word and slot of R's destination (nullable)
 };
 
 // ---- the two-term operand split of conv_split.hip / conv_s4.hip ------------------------------------------------------
@@ -318,6 +327,16 @@ constexpr int kTailChunks = 2;   // K = 32 chunks of R's A fragments: R's other 
 inline size_t tail_packed_floats() { return (size_t)kTailChunks * 2 * 64 * 4; }
 // R's weights (OIHW, 1x1, already scaled by its 2^k) in the tail form's K order (conv_ranges.h: order_tail, tail_channel)
 void pack_conv_weights_tail(const float *w_oihw, int cin, int cout, const KOrder &k, float *out);
+// the down form: a 3x3 launch of two cout tiles on 8 x 32 tiles that stores its slice and also computes the 1x1 conv R (ReLU, at most
+// kDownTiles cout tiles) with the 2x2 average pool behind it (ConvArgs::down_..).  down_wanted (conv_select.cpp): mode = the plan's
+// fold_down option (0 never, 1 the measured rule, 2 wherever the form exists); cin, cout = the 3x3 conv's, r_cout = R's
+int launch_conv_s4_down(const ConvArgs &a, int B, hipStream_t stream);
+bool down_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode);
+constexpr int kDownTiles = 4;    // R's cout tiles: [tile][chunk][term][64 lanes][8 fp16], zeros past R's couts
+constexpr int kDownFragBytes = kDownTiles * kTailChunks * 2 * 64 * 16;
+inline size_t down_packed_floats() { return (size_t)kDownFragBytes / 4; }
+// R's weights as for pack_conv_weights_tail, cout tile by cout tile in the same K order
+void pack_conv_weights_down(const float *w_oihw, int cin, int cout, const KOrder &k, float *out);
 
 // conv_pair.hip: an odd HarDBlock layer P = conv3x3(S) computed inside its consumer C = conv3x3(P ++ S ++ others) (hardnet.py:177-194)
 struct PairArgs {

@@ -111,6 +111,13 @@ struct S4Cfg {
 #include "conv_s4_kernel.inc"
 #undef S4_KERNEL_NAME
 #undef S4_KERNEL_EPI
+// the down form (the launch stores its slice and also computes the 1x1 conv + 2x2 average pool behind it: launch_conv_s4_down below),
+// instantiated for two cout tiles on 8 x 32 tiles without a K split at the plain form's launch bounds
+#define S4_KERNEL_NAME conv_s4_down_kernel
+#define S4_KERNEL_EPI 4
+#include "conv_s4_kernel.inc"
+#undef S4_KERNEL_NAME
+#undef S4_KERNEL_EPI
 #undef S4_KERNEL_KACC
 #undef S4_KERNEL_WAVES
 // the blocked-sum form (instantiated for 8 x 32 tiles without a K split): one workgroup per CU fewer than the plain form where the
@@ -125,23 +132,25 @@ struct S4Cfg {
 #undef S4_KERNEL_EPI
 #undef S4_KERNEL_WAVES
 
-// one launcher for the five forms of the 3x3 kernel (conv_s4_kernel.inc); the label = the symbol rocprofv3 reports (bench.py looks
+// one launcher for the six forms of the 3x3 kernel (conv_s4_kernel.inc); the label = the symbol rocprofv3 reports (bench.py looks
 // its PMC bytes up by it)
-enum S4Form { S4_PLAIN, S4_BLOCKED, S4_SHARE, S4_ADD, S4_TAIL };
+enum S4Form { S4_PLAIN, S4_BLOCKED, S4_SHARE, S4_ADD, S4_TAIL, S4_DOWN };
 template <S4Form FORM, int NT, int TW_, int TH_, int KS_>
 static constexpr auto s4_kernel() {   // (only the form asked for is instantiated)
     if constexpr (FORM == S4_PLAIN) return &conv_s4_kernel<NT, TW_, TH_, KS_>;
     else if constexpr (FORM == S4_BLOCKED) return &conv_s4_blocked_kernel<NT, TW_, TH_, KS_>;
     else if constexpr (FORM == S4_SHARE) return &conv_s4_share_kernel<NT, TW_, TH_, KS_>;
     else if constexpr (FORM == S4_ADD) return &conv_s4_add_kernel<NT, TW_, TH_, KS_>;
-    else return &conv_s4_tail_kernel<NT, TW_, TH_, KS_>;
+    else if constexpr (FORM == S4_TAIL) return &conv_s4_tail_kernel<NT, TW_, TH_, KS_>;
+    else return &conv_s4_down_kernel<NT, TW_, TH_, KS_>;
 }
 template <S4Form FORM, int NT, int TW_ = 32, int TH_ = 8, int KS_ = 1>
 static int launch_s4_form(const ConvArgs &a0, int B, hipStream_t s) {
     using C = S4Cfg<NT, TW_, TH_, KS_>;
     constexpr auto kernel = s4_kernel<FORM, NT, TW_, TH_, KS_>();
     constexpr const char *name = FORM == S4_PLAIN ? "conv_s4_kernel" : FORM == S4_BLOCKED ? "conv_s4_blocked_kernel"
-                               : FORM == S4_SHARE ? "conv_s4_share_kernel" : FORM == S4_ADD ? "conv_s4_add_kernel" : "conv_s4_tail_kernel";
+                               : FORM == S4_SHARE ? "conv_s4_share_kernel" : FORM == S4_ADD ? "conv_s4_add_kernel"
+                               : FORM == S4_TAIL ? "conv_s4_tail_kernel" : "conv_s4_down_kernel";
     ConvArgs a = a0;
     a.tilesX = (a.Wout + C::TW - 1) / C::TW;
     a.tilesY = (a.Hout + C::TH - 1) / C::TH;
@@ -157,9 +166,11 @@ static int launch_s4_form(const ConvArgs &a0, int B, hipStream_t s) {
     const int rows = FORM == S4_SHARE ? a.Cout + a.share_cout : a.Cout;
     const double sums = FORM == S4_SHARE || FORM == S4_ADD ? (double)(a.share_cout + 3) / 4 * 4 : 0.0;
     // tail: both convs' flops; reads the 3x3 conv's input and the other channels of the 1x1 conv's, writes the 1x1 conv's output only
-    const double flops = 2.0 * px * rows * a.Cin * 9 + (FORM == S4_TAIL ? 2.0 * px * a.tail_cout * (4 * a.tail_gn + a.Cout) : 0.0);
-    const double stored = FORM == S4_TAIL ? (double)a.tail_cout : a.Cout + sums;
-    const double extra = FORM == S4_TAIL ? px * 4 * a.tail_gn + (double)a.tail_cout * (4 * a.tail_gn + a.Cout) : 0.0;
+    // down: both convs' flops too; writes its slice and a quarter of the 1x1 conv's pixels
+    constexpr bool FOLD = FORM == S4_TAIL || FORM == S4_DOWN;
+    const double flops = 2.0 * px * rows * a.Cin * 9 + (FOLD ? 2.0 * px * a.tail_cout * (4 * a.tail_gn + a.Cout) : 0.0);
+    const double stored = FORM == S4_TAIL ? (double)a.tail_cout : FORM == S4_DOWN ? a.Cout + 0.25 * a.tail_cout : a.Cout + sums;
+    const double extra = FOLD ? px * 4 * a.tail_gn + (double)a.tail_cout * (4 * a.tail_gn + a.Cout) : 0.0;
     ProfScope ps(s, label, flops, 4.0 * ((double)B * a.Cin * a.Hin * a.Win + px * stored + (double)rows * a.Cin * 9 + extra));
     hipLaunchKernelGGL(kernel, dim3(a.tilesX * a.tilesY, (a.ntiles + NT - 1) / NT, B), dim3(C::NTHR * C::KS), C::LDS_BYTES, s, a);
     PF_LAUNCH_CHECK(name);
@@ -207,6 +218,25 @@ int launch_conv_s4_tail(const ConvArgs &a, int B, hipStream_t s) {
         (reinterpret_cast<uintptr_t>(a.tail_bias) & 15) != 0 || a.tail_g0 < 0 || a.tail_g0 + a.tail_gn > a.tail_c4)
         return fail(PF_EINVAL, "conv_s4 tail: second conv of %d couts over %d groups", a.tail_cout, a.tail_gn);
     return launch_s4_form<S4_TAIL, 2>(a, B, s);
+}
+// a = the 3x3 conv's plain launch with R's operands (a.tail_w / tail_bias / tail_scale / tail_src .. / tail_cout) and R's pooled
+// destination (a.down_..) filled
+int launch_conv_s4_down(const ConvArgs &a, int B, hipStream_t s) {
+    if (!a.src_fmt || !a.dst_fmt) return fail(PF_EINVAL, "conv_s4 down: sources and the slice in the S4 layout only");
+    if ((a.Wout & 3) != 0 || a.Hin != a.Hout || a.Win != a.Wout) return fail(PF_EUNSUPPORTED, "conv_s4 down: stride 1, width %% 4 == 0 only");
+    if (a.pool || a.res || a.no_bias || a.kacc || a.share) return fail(PF_EUNSUPPORTED, "conv_s4 down: no fused epilogue stages of its own");
+    if (a.chunk_begin != 0 || a.chunk_end != a.nchunks) return fail(PF_EUNSUPPORTED, "conv_s4 down: whole K range only");
+    if (a.ntiles != 2) return fail(PF_EUNSUPPORTED, "conv_s4 down: %d cout tiles, the form is built for two", a.ntiles);
+    if (a.Hout < 2 || a.Wout < 2) return fail(PF_EUNSUPPORTED, "conv_s4 down: nothing to pool at %d x %d", a.Hout, a.Wout);
+    if (!a.tail_w || !a.tail_bias || a.tail_cout < 1 || a.tail_cout > 16 * kDownTiles || a.tail_gn < 0 || a.tail_gn > 8 || (a.tail_gn && !a.tail_src) ||
+        (reinterpret_cast<uintptr_t>(a.tail_w) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.tail_bias) & 15) != 0 || a.tail_g0 < 0 ||
+        a.tail_g0 + a.tail_gn > a.tail_c4)
+        return fail(PF_EINVAL, "conv_s4 down: second conv of %d couts over %d groups", a.tail_cout, a.tail_gn);
+    const bool packed_ok = (a.down_choff & 1) == 0 && a.down_limit >= a.down_choff + a.tail_cout && a.down_limit <= 4 * a.down_c4 &&
+                           a.down_limit <= (a.down_choff + a.tail_cout + 3) / 4 * 4;
+    if (!a.down_dst || a.down_choff < 0 || (a.down_fmt ? !packed_ok : a.down_choff + a.tail_cout > a.down_ctotal))
+        return fail(PF_EINVAL, "conv_s4 down: pooled destination of %d channels from %d (limit %d) in %d groups", a.tail_cout, a.down_choff, a.down_limit, a.down_c4);
+    return launch_s4_form<S4_DOWN, 2>(a, B, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -658,18 +688,25 @@ void pack_conv_weights_s4(const float *w, int cin, int cout, int ks, const KOrde
 
 // the tail form's second conv: [chunk][term 2][lane 64][8 fp16], lane = (cout lane & 15, lane group g), value e = R's weight of the
 // input channel tail_channel(k, chunk, g, e) (conv_ranges.cpp), zero where there is none
-void pack_conv_weights_tail(const float *w, int cin, int cout, const KOrder &k, float *out_f) {
-    unsigned short *out = reinterpret_cast<unsigned short *>(out_f);
+static void pack_tail_tiles(const float *w, int cin, int cout, const KOrder &k, int ntiles, unsigned short *out) {
     size_t o = 0;
-    for (int chunk = 0; chunk < kTailChunks; ++chunk)
-        for (int term = 0; term < 2; ++term)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int co = lane & 15, ci = tail_channel(k, chunk, lane >> 4, e);
-                    const float v = (co < cout && ci >= 0 && ci < cin) ? w[(size_t)co * cin + ci] : 0.f;
-                    const unsigned short hi = split_host_f16(v);
-                    out[o++] = term == 0 ? hi : split_host_f16(v - split_host_f32(hi));
-                }
+    for (int t = 0; t < ntiles; ++t)
+        for (int chunk = 0; chunk < kTailChunks; ++chunk)
+            for (int term = 0; term < 2; ++term)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 8; ++e) {
+                        const int co = t * 16 + (lane & 15), ci = tail_channel(k, chunk, lane >> 4, e);
+                        const float v = (co < cout && ci >= 0 && ci < cin) ? w[(size_t)co * cin + ci] : 0.f;
+                        const unsigned short hi = split_host_f16(v);
+                        out[o++] = term == 0 ? hi : split_host_f16(v - split_host_f32(hi));
+                    }
+}
+void pack_conv_weights_tail(const float *w, int cin, int cout, const KOrder &k, float *out_f) {
+    pack_tail_tiles(w, cin, cout, k, 1, reinterpret_cast<unsigned short *>(out_f));
+}
+// the down form's second conv: the same per cout tile, [tile kDownTiles][chunk][term 2][lane 64][8 fp16], zeros past R's couts
+void pack_conv_weights_down(const float *w, int cin, int cout, const KOrder &k, float *out_f) {
+    pack_tail_tiles(w, cin, cout, k, kDownTiles, reinterpret_cast<unsigned short *>(out_f));
 }
 
 // ------------------------------------------------------------------------------------------------ layout conversion

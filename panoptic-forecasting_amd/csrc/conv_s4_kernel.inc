@@ -9,6 +9,9 @@
 //                    3 "tail" (NT = 2; ConvArgs::tail_..): the finished values stay in registers as the two terms their single reader, a
 //                    1x1 conv R, would read back, and are multiplied by R's weights together with the centre pixels of R's other channels;
 //                    R's output is stored (fp32 NCHW), this conv's slice is not
+//                    4 "down" (NT = 2, 8 x 32 tiles; ConvArgs::tail_.. and down_..): the slice IS stored, as by the plain epilogue, and
+//                    the same values, still in registers, also feed a 1x1 conv R with ReLU of up to four cout tiles whose 2x2 average
+//                    pool - two M-tile rows of a wave, lane pairs of a row - is stored (packed pairs or fp32 NCHW): R's launch goes away
 template <int NT, int TW_, int TH_, int KS_>
 __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAME(ConvArgs a) {
     [[maybe_unused]] constexpr int KACC = S4_KERNEL_KACC;
@@ -320,12 +323,16 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 }
             }
         }
-        // tail: the second conv R's operands that do not come out of this launch's accumulators, loaded in front of the same wait: its A
-        // fragments (one 16-row tile, two terms, chunk 0 = R's other channels, chunk 1 = this launch's couts; L2-resident) and bias, and the
-        // lane's B fragments of chunk 0 - lane group g supplies group entries 2g and 2g + 1 of R's other channels at the CENTRE pixel of
-        // every M-tile, straight from the packed planes (entries past the range, pixels outside the image: the zero page)
+        // tail / down: the second conv R's operands that do not come out of this launch's accumulators, loaded in front of the same wait.
+        // tail: its A fragments (one 16-row tile, two terms, chunk 0 = R's other channels, chunk 1 = this launch's couts; L2-resident) and
+        // bias.  down: R has up to four cout tiles - 16 KB of fragments, too many to hold - so they and R's bias go by LDS-DMA into the
+        // stage ring, which is dead once every wave has left the main loop, and are read back per cout tile (no load, hence no vmcnt
+        // wait, between the stores below).  Both: the lane's B fragments of chunk 0 - lane group g supplies group entries 2g and 2g + 1
+        // of R's other channels at the CENTRE pixel of every M-tile, straight from the packed planes (entries past the range, pixels
+        // outside the image: the zero page)
+        constexpr bool FOLD = EPI == 3 || EPI == 4;
         [[maybe_unused]] s4_h8 tw_h[EPI == 3 ? 2 : 1], tw_m[EPI == 3 ? 2 : 1];
-        [[maybe_unused]] s4_h4 to_h[EPI == 3 ? C::MP : 1][2], to_m[EPI == 3 ? C::MP : 1][2];
+        [[maybe_unused]] s4_h4 to_h[FOLD ? C::MP : 1][2], to_m[FOLD ? C::MP : 1][2];
         [[maybe_unused]] s4_f32x4 tbias = s4_f32x4{0.f, 0.f, 0.f, 0.f};
         if constexpr (EPI == 3) {
             static_assert(NT == 2, "a lane's 4 + 4 split values of two cout tiles are one K slice of the second conv");
@@ -336,6 +343,26 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 tw_m[c] = tw[(c * 2 + 1) * 64 + lane];
             }
             tbias = *reinterpret_cast<const s4_f32x4 *>(a.tail_bias + 4 * (lane >> 4));
+        }
+        if constexpr (EPI == 4) {
+            static_assert(NT == 2 && TW_ == 32 && TH_ == 8 && KS_ == 1, "M-tiles m and m + 2 of a wave are two rows of the same 16 columns");
+            static_assert(kDownFragBytes + kDownTiles * 16 * sizeof(float) <= C::STAGES_BYTES, "R's fragments and bias live in the stage ring");
+            const int rt = (a.tail_cout + 15) >> 4;             // R's cout tiles (uniform)
+            __syncthreads();                                    // every wave is done reading the ring
+            const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void *)a.tail_w, 0, 0x7FFFFFFF, 0x00020000);
+#pragma unroll
+            for (int it = 0; it < kDownFragBytes / 16 / C::NTHR; ++it) {
+                const int p = it * C::NTHR + tid;               // 16-B piece; a cout tile is 256 of them
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(frs, (s4_lds_ptr_t)(smem_all + (it * C::NTHR + wave * 64) * 16), 16,
+                                                         p < rt * 256 ? (unsigned)p * 16u : kS4Oob, 0, 0, 0);
+            }
+            if (wave == 0) {                                    // R's bias: 64 values, zero past its tiles
+                const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void *)a.tail_bias, 0, 0x7FFFFFFF, 0x00020000);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, (s4_lds_ptr_t)(smem_all + kDownFragBytes), 4, lane < rt * 16 ? (unsigned)lane * 4u : kS4Oob,
+                                                         0, 0, 0);
+            }
+        }
+        if constexpr (FOLD) {
             const size_t tstride = (size_t)a.tail_c4 * plane_bytes;
             const char *tbase = reinterpret_cast<const char *>(a.tail_src) + (size_t)b * 2 * tstride;
 #pragma unroll
@@ -356,6 +383,7 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
             }
         }
         __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0), expcnt / lgkmcnt untouched
+        if constexpr (EPI == 4) __syncthreads();   // every wave's pieces of R's fragments have landed
         const int g = lane >> 4, px = lane & 15;
         const size_t hw = (size_t)a.Hout * a.Wout;
         const size_t term = (size_t)a.dst_c4 * hw * 8;
@@ -389,6 +417,7 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 }
             }
         };
+        [[maybe_unused]] s4_h8 dx0h[EPI == 4 ? C::MP : 1], dx0m[EPI == 4 ? C::MP : 1], dx1h[EPI == 4 ? C::MP : 1], dx1m[EPI == 4 ? C::MP : 1];
 #pragma unroll
         for (int m = 0; m < C::MP; ++m) {
             const int mt = wave * C::MP + m;
@@ -430,6 +459,28 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 }
                 continue;
             }
+            if constexpr (EPI == 4) {
+                // the plain epilogue for every lane (rows past this launch's couts: zero weights, zero bias -> 0), the slice stored as the
+                // plain form stores it; the same values split into the two terms R would read back are K slice g of R's chunk 1, as in
+                // the tail form, and are kept for all four M-tiles next to chunk 0's
+                const bool in = oy < a.Hout && ox < a.Wout;
+                s4_h4 xh[2], xm[2];
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    const int co = (tile0 + n) * 16 + 4 * g;
+                    s4_f32x4 v = acc[m][n];
+                    const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(bias_lds + n * 16 + 4 * g);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r] * a.acc_scale + b4[r], relu_lo);
+                    const float vm = range_acc(vmax, v[0], v[1], v[2], v[3]);
+                    vmax = in ? vm : vmax;
+                    split_terms4(v, xh[n], xm[n]);
+                    if (in && co < a.Cout + 2) store_px(co, (size_t)oy * a.Wout + ox, v);
+                }
+                dx1h[m] = s4_join(xh[0], xh[1]); dx1m[m] = s4_join(xm[0], xm[1]);
+                dx0h[m] = s4_join(to_h[m][0], to_h[m][1]); dx0m[m] = s4_join(to_m[m][0], to_m[m][1]);
+                continue;
+            }
             if (oy >= a.Hout || ox >= a.Wout) continue;
             const size_t pix = (size_t)oy * a.Wout + ox;
 #pragma unroll
@@ -466,6 +517,85 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                         if (co + r < a.Cout) a.dst[((size_t)b * a.dst_ctotal + a.dst_choff + co + r) * hw + pix] = v[r];
                 }
             }
+        }
+        if constexpr (EPI == 4) {
+            // R, one cout tile at a time: six K = 32 products per M-tile into one fp32 accumulator - chunk 0 (R's other channels), then
+            // chunk 1 (this launch's) - then 2^-k, bias, ReLU (R has one: plan_create.hip is_conv_down) and the 2x2 average pool in
+            // registers.  M-tiles 0, 1 are row 2w of the tile (columns 0-15, 16-31), M-tiles 2, 3 row 2w + 1; the horizontal neighbour
+            // sits in lane px ^ 1.  Even lanes pool M-tiles 0 / 2, odd lanes M-tiles 1 / 3: a lane sends its neighbour the value of the
+            // tile the neighbour pools, so the 16 lanes of a lane group store 16 consecutive pooled pixels, 128 B per term.
+            // (((a + b) + c) + d) * 0.25, a, b = row oy at x, x + 1: the order of avgpool2_kernel and conv_s4_1x1_kernel
+            const int rt = (a.tail_cout + 15) >> 4;
+            const int Ho = a.Hout >> 1, Wo = a.Wout >> 1;       // a last row or column the pool drops is not stored
+            const size_t hw2 = (size_t)Ho * Wo, term2 = (size_t)a.down_c4 * hw2 * 8;
+            const bool mis2 = (a.down_choff & 2) != 0, odd = (px & 1) != 0;
+            const int poy = tileY * (C::TH / 2) + wave, pox = tileX * (C::TW / 2) + (odd ? 8 : 0) + (px >> 1);
+            const bool pin = poy < Ho && pox < Wo;
+            const size_t ppix = (size_t)poy * Wo + pox;
+            const unsigned char *fw = smem_all + lane * 16;
+            const float *rbias = reinterpret_cast<const float *>(smem_all + kDownFragBytes);
+            float vmax2 = 0.f;
+            auto swap_px = [](float x) {                         // the value of lane px ^ 1: quad_perm [1, 0, 3, 2]
+                return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
+            };
+#pragma unroll 1
+            for (int ct = 0; ct < rt; ++ct) {
+                const s4_h8 wh0 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 4 + 0) * 1024), wm0 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 4 + 1) * 1024);
+                const s4_h8 wh1 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 4 + 2) * 1024), wm1 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 4 + 3) * 1024);
+                const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(rbias + ct * 16 + 4 * g);
+                s4_f32x4 v[C::MP];
+#pragma unroll
+                for (int m = 0; m < C::MP; ++m) {
+                    s4_f32x4 t = s4_f32x4{0.f, 0.f, 0.f, 0.f};
+                    t = PF_MFMA_SPLIT(wh0, dx0m[m], t);
+                    t = PF_MFMA_SPLIT(wm0, dx0h[m], t);
+                    t = PF_MFMA_SPLIT(wh0, dx0h[m], t);
+                    t = PF_MFMA_SPLIT(wh1, dx1m[m], t);
+                    t = PF_MFMA_SPLIT(wm1, dx1h[m], t);
+                    t = PF_MFMA_SPLIT(wh1, dx1h[m], t);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[m][r] = fmaxf(t[r] * a.tail_scale + b4[r], 0.f);
+                }
+                s4_f32x4 pv;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float top = swap_px(odd ? v[0][r] : v[1][r]), bot = swap_px(odd ? v[2][r] : v[3][r]);
+                    const float pa = odd ? top : v[0][r], pb = odd ? v[1][r] : top, pc = odd ? bot : v[2][r], pd = odd ? v[3][r] : bot;
+                    pv[r] = (((pa + pb) + pc) + pd) * 0.25f;
+                }
+                const float vm = range_acc(vmax2, pv[0], pv[1], pv[2], pv[3]);
+                vmax2 = pin ? vm : vmax2;
+                const int co = ct * 16 + 4 * g, chb = a.down_choff + co;   // store_px into R's destination, or fp32 NCHW
+                if (pin && !a.down_fmt) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (co + r < a.tail_cout) reinterpret_cast<float *>(a.down_dst)[((size_t)b * a.down_ctotal + chb + r) * hw2 + ppix] = pv[r];
+                } else if (pin && co < a.tail_cout + 2) {
+                    s4_h4 hi, mid;
+                    split_terms4(pv, hi, mid);
+                    const bool ok0 = chb < a.down_limit, ok1 = chb + 2 < a.down_limit;
+                    char *p = reinterpret_cast<char *>(a.down_dst) + (size_t)b * 2 * term2 + ppix * 8 + (size_t)(chb >> 2) * hw2 * 8;
+                    if (!mis2) {
+                        if (ok1) {
+                            *reinterpret_cast<s4_h4 *>(p) = hi;
+                            *reinterpret_cast<s4_h4 *>(p + term2) = mid;
+                        } else if (ok0) {
+                            *reinterpret_cast<h2 *>(p) = h2{hi[0], hi[1]};
+                            *reinterpret_cast<h2 *>(p + term2) = h2{mid[0], mid[1]};
+                        }
+                    } else {
+                        if (ok0) {
+                            *reinterpret_cast<h2 *>(p + 4) = h2{hi[0], hi[1]};
+                            *reinterpret_cast<h2 *>(p + 4 + term2) = h2{mid[0], mid[1]};
+                        }
+                        if (ok1) {
+                            *reinterpret_cast<h2 *>(p + hw2 * 8) = h2{hi[2], hi[3]};
+                            *reinterpret_cast<h2 *>(p + hw2 * 8 + term2) = h2{mid[2], mid[3]};
+                        }
+                    }
+                }
+            }
+            range_commit(a.down_status, a.down_slot, vmax2);
         }
         range_commit(a.status, a.range_slot, vmax);
     }

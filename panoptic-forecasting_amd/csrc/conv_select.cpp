@@ -122,6 +122,19 @@ bool tail_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode) {
     return cin == 91 && cout == 28 && r_cout == 11 && px >= 524288 && px <= 4194304;
 }
 
+// conv_s4.hip down (a 3x3 conv's launch also computes the 1x1 conv + 2x2 average pool behind it) instead of the two launches?  mode = plan
+// option fold_down: 0 never, 2 wherever the form exists (tests, A/B runs), 1 (default): only the class of launches whose folded runs
+// MEASURED faster than the two launches in every run (MI355X, 1024x2048 network, same box, fold_down 0 / 2 alternated three times:
+// profiles/r09_experiments.md): 76 -> 28 -> 64 at 256x512, B = 4 .. 32 - 103 -> 79 us, 205-207 -> 164-165 us, 393-401 -> 317-324 us,
+// 781-790 -> 640-642 us: the folded launch takes the 3x3 launch's time and about half of the 1x1 launch's.  Other channel counts,
+// smaller launches (B = 1, 2) and launches of more than 4 194 304 pixels were not measured and keep their two launches
+bool down_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode) {
+    if (mode >= 2) return true;
+    if (mode <= 0) return false;
+    const long px = (long)B * h * w;
+    return cin == 76 && cout == 28 && r_cout == 64 && px >= 524288 && px <= 4194304;
+}
+
 ConvChoice choose_conv(int ks, int stride, int cin, int cout, int hout, int wout, int B, int need, int use_tuned) {
     if (stride != 1) return ConvChoice::dma();           // shape by its cost model
     // The table was measured at B = 1, 2, 4, 8, 16 and (round 5, the strict-fp32 model at the headline's sub-batch) 32; a layer

@@ -43,6 +43,10 @@ struct ConvPlan {
     // plans created with fold_final != 0: the reader's A fragments, an offset in floats into the plan's tail region (pf_plan::dev_tail,
     // whose first 64 floats are zeros: 0 = the op has none).  A region of its own: the weight arena stays what it was without the form
     size_t tail_off = 0;
+    // the down form (conv_s4.hip), kept on the PRODUCER too (op i; op i + 1 is the 1x1 conv with ReLU whose range ends with its slice, op
+    // i + 2 that conv's 2x2 average pool) and packed only by plans created with fold_down != 0: the 1x1 conv's A fragments, an offset in
+    // floats into the plan's down region (pf_plan::dev_down, first 64 floats zeros: 0 = none).  A region of its own beside the other two
+    size_t down_off = 0;
 };
 
 // The switches a plan carries (include/pfhip.h documents each), with their defaults.  g_plan_opt is the process-wide set
@@ -62,6 +66,9 @@ struct PlanOptions {
     int fold_final = 1;        // conv_s4.hip tail: a 3x3 conv whose slice has one reader, a small 1x1 conv into fp32, also computes that conv
                                // and never stores its slice (0 = off, and a plan created with 0 packs nothing for it; 1 = conv_select.cpp::tail_wanted;
                                // 2 = wherever built)
+    int fold_down = 1;         // conv_s4.hip down: a 3x3 conv in front of a 1x1 conv with ReLU + 2x2 average pool that reads its slice last also
+                               // computes that conv and its pool; the slice is stored as ever (0 = off, and a plan created with 0 packs nothing for
+                               // it; 1 = conv_select.cpp::down_wanted; 2 = wherever built)
 };
 
 struct pf_plan {
@@ -73,6 +80,8 @@ struct pf_plan {
     size_t dev_floats = 0;
     std::vector<float> tail_host;   // the tail form's packings (ConvPlan::tail_off), empty when the plan has none ...
     float *dev_tail = nullptr;      // ... and their upload
+    std::vector<float> down_host;   // the down form's packings (ConvPlan::down_off), likewise
+    float *dev_down = nullptr;
     PlanOptions opt;             // read only by forwards of this plan
     // formats of the last forward (pf_hardnet_tensor_read): 1 = S4, 0xFF = elided (never stored: conv_front.hip), 0xFE = its last
     // slice elided (never stored: the tail form of conv_s4.hip)
@@ -109,5 +118,8 @@ bool is_conv_pair(const NetTable &t, size_t i);
 // op i is a 3x3 conv whose slice has exactly one reader, op i + 1, a 1x1 conv the tail form of conv_s4.hip can compute in op i's
 // launch (plan_create.hip)
 bool is_conv_tail(const NetTable &t, size_t i);
+// op i is a 3x3 conv in front of a 1x1 conv with ReLU (op i + 1) and its 2x2 average pool (op i + 2) that the down form of conv_s4.hip
+// can compute in op i's launch; other ops may read op i's slice too (plan_create.hip)
+bool is_conv_down(const NetTable &t, size_t i);
 
 }  // namespace pf

@@ -17,7 +17,7 @@ namespace {
 // ---- A forward = build_schedule (host code only: every launch with all its arguments, each naming exactly one kernel) + the
 //      enqueue loop of run_net.  S_CONV: inside build_schedule only, a convolution whose kernel is picked once the formats are known
 enum StepKind : uint8_t {
-    S_RANGE_CHECK, S_STEM, S_STEM_FRONT, S_PAIR, S_CONV, S_CONV_S4, S_CONV_S4_SHARE, S_CONV_S4_ADD, S_CONV_S4_TAIL, S_CONV_GENERIC, S_CONV_SPLIT, S_CONV_SPLIT1, S_CONV_WAVE, S_CONV_DMA,
+    S_RANGE_CHECK, S_STEM, S_STEM_FRONT, S_PAIR, S_CONV, S_CONV_S4, S_CONV_S4_SHARE, S_CONV_S4_ADD, S_CONV_S4_TAIL, S_CONV_S4_DOWN, S_CONV_GENERIC, S_CONV_SPLIT, S_CONV_SPLIT1, S_CONV_WAVE, S_CONV_DMA,
     S_POOL, S_UPSAMPLE, S_HEAD };
 struct PlainArgs { const float *src; float *dst; int planes, hin, win, hout, wout; size_t n; unsigned *status, *slot; };   // pool, upsample, range check
 struct Step {
@@ -461,6 +461,36 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
         fmt[L.dst] = 0xFE;   // pf_hardnet_tensor_read refuses the tensor: its last slice is never stored
         steps.erase(steps.begin() + (long)k + 1);
     }
+
+    // ---- 7. a 3x3 conv L in front of the 1x1 conv R + 2x2 average pool that ends a block (is_conv_down) as ONE launch (conv_s4.hip down):
+    //      two adjacent plain conv_s4 steps, L on <2, 32, 8, 1> into packed pairs - not part of a pair or a share / add step, whose kinds
+    //      differ -, R with its pool fused and nothing else, into packed pairs or fp32.  L's slice is stored as ever; R's step goes away
+    for (size_t k = 0; p->opt.fold_down && p->dev_down && k + 1 < steps.size(); ++k) {
+        Step &sl = steps[k];
+        const Step &sr = steps[k + 1];
+        const size_t i = (size_t)sl.op;
+        if (sl.kind != S_CONV_S4 || sr.kind != S_CONV_S4 || sl.ci != (int)i || sr.op != (int)i + 1 || sr.ci != (int)i + 1) continue;
+        if (!p->conv[i].down_off || !is_conv_down(p->net, i)) continue;
+        const BlobOp &L = p->net.ops[i], &R = p->net.ops[i + 1];
+        ConvArgs &a = sl.u.c;
+        const ConvArgs &r = sr.u.c;
+        const S4Shape &sh = sl.dec.s4;
+        if (sh.NT != 2 || sh.TW != 32 || sh.TH != 8 || sh.KS != 1 || !a.dst_fmt || !r.pool || r.res || r.no_bias || !r.relu || a.Hout != r.Hout || a.Wout != r.Wout) continue;
+        if (!down_wanted((int)L.cin, (int)L.cout, (int)R.cout, a.Hout, a.Wout, Bt, p->opt.fold_down)) continue;
+        const KOrder ko = order_tail(R.src[0], (int)L.dst_choff, (int)L.cout);
+        a.tail_w = p->dev_down + p->conv[i].down_off;
+        a.tail_bias = r.bias; a.tail_scale = r.acc_scale;
+        a.tail_src = a.dst; a.tail_c4 = a.dst_c4; a.tail_g0 = ko.r[0].choff / 4; a.tail_gn = ko.r[0].ch / 4;
+        a.tail_cout = r.Cout;
+        a.down_dst = r.dst; a.down_c4 = r.dst_c4; a.down_choff = r.dst_choff; a.down_limit = r.dst_limit;
+        a.down_fmt = r.dst_fmt; a.down_ctotal = r.dst_ctotal;
+        a.down_status = r.status; a.down_slot = r.range_slot;
+        sl.kind = S_CONV_S4_DOWN;
+        if (tags)
+            snprintf(sl.tag, sizeof(sl.tag), "%02zu+%02zu %s+%s %u->%u->%u %dx%d", i, i + 1, p->net.tensors[L.dst].name, p->net.tensors[R.dst].name, L.cin,
+                     L.cout, R.cout, a.Hout, a.Wout);
+        steps.erase(steps.begin() + (long)k + 1);
+    }
     return PF_OK;
 }
 
@@ -499,6 +529,7 @@ int run_net(const pf_plan *p, const StemArgs *stem, const float *dense_x, int B,
             case S_CONV_S4_SHARE: rc = launch_conv_s4_share(a, st.dec.s4_nt, B, s); break;
             case S_CONV_S4_ADD: rc = launch_conv_s4_add(a, st.dec.s4_nt, B, s); break;
             case S_CONV_S4_TAIL: rc = launch_conv_s4_tail(a, B, s); break;
+            case S_CONV_S4_DOWN: rc = launch_conv_s4_down(a, B, s); break;
             case S_CONV_GENERIC: rc = launch_conv(a, p->conv[st.ci].tiling, B, s); break;
             case S_CONV_SPLIT: rc = launch_conv_split(a, ch.split_nt(), ch.split_wide(), B, s); break;
             case S_CONV_SPLIT1: rc = launch_conv_split1(a, ch.split_nt(), B, s); break;

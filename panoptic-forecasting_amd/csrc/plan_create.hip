@@ -37,6 +37,7 @@ const Option kOptions[] = {
     {"fuse_pairs", nullptr, &PlanOptions::fuse_pairs, nullptr, true, true, false},
     {"share_s", nullptr, &PlanOptions::share_s, nullptr, true, true, false},
     {"fold_final", nullptr, &PlanOptions::fold_final, nullptr, true, true, false},
+    {"fold_down", nullptr, &PlanOptions::fold_down, nullptr, true, true, false},
     {"profile_tag_ops", nullptr, &PlanOptions::profile_tag_ops, nullptr, true, true, false},
     {"table_batch", nullptr, &PlanOptions::table_batch, nullptr, false, true, true},
     {"normalize_ranges", nullptr, &PlanOptions::normalize_ranges, nullptr, true, false, false},
@@ -107,6 +108,34 @@ bool pf::is_conv_tail(const NetTable &t, size_t i) {
             for (uint32_t c = o.dst_choff; c < o.dst_choff + o.cout && c < written.size(); ++c) written[c] = 1;
         for (uint32_t s = 0; s < o.n_src && j != i + 1; ++s)   // another reader of the slice
             if (o.src[s].tensor == L.dst && o.src[s].choff < d1 && o.src[s].choff + o.src[s].ch > d0) return false;
+    }
+    for (uint32_t c = rs.choff; c < d0; ++c)
+        if (!written[c]) return false;
+    return true;
+}
+
+// L = op i, a 3x3 stride-1 conv of two cout tiles; R = op i + 1, a 1x1 stride-1 conv WITH ReLU of at most 64 couts whose single range ends
+// with L's slice; op i + 2 = the 2x2 average pool of R's output, its only reader.  As for the tail form the slice and R's range start on a
+// 4-channel boundary and R's other channels (in front of the slice) are at most 8 groups, every one written by an earlier op.  Unlike
+// there, other ops may read the slice: it is stored.  (Formats and kernels of L and R: the schedule, hardnet_plan.hip.)
+bool pf::is_conv_down(const NetTable &t, size_t i) {
+    if (i + 2 >= t.ops.size()) return false;
+    const BlobOp &L = t.ops[i], &R = t.ops[i + 1], &P = t.ops[i + 2];
+    if (L.kind != OP_CONV || R.kind != OP_CONV || L.k != 3 || L.stride != 1 || R.k != 1 || R.stride != 1 || !R.relu || R.n_src != 1) return false;
+    if (L.cout <= 16 || L.cout > 32 || R.cout > 16 * kDownTiles) return false;
+    if (P.kind != OP_POOL || P.src[0].tensor != R.dst || R.dst_choff != 0 || R.cout != t.tensors[R.dst].channels) return false;
+    for (uint32_t j = 0; j < L.n_src; ++j)
+        if (L.src[j].choff & 1) return false;
+    const BlobSrc &rs = R.src[0];
+    const uint32_t d0 = L.dst_choff, d1 = L.dst_choff + L.cout;
+    if (rs.tensor != L.dst || (rs.choff & 3) || (d0 & 3) || rs.choff > d0 || rs.choff + rs.ch != d1 || d0 - rs.choff > 32) return false;
+    std::vector<uint8_t> written(t.tensors[L.dst].channels, 0);
+    for (size_t j = 0; j < t.ops.size(); ++j) {
+        const BlobOp &o = t.ops[j];
+        if (j < i && (o.kind == OP_CONV || o.kind == OP_STEM) && o.dst == L.dst)
+            for (uint32_t c = o.dst_choff; c < o.dst_choff + o.cout && c < written.size(); ++c) written[c] = 1;
+        for (uint32_t s = 0; s < o.n_src && j != i + 2; ++s)   // the pool is the only reader of R's output
+            if (o.src[s].tensor == R.dst) return false;
     }
     for (uint32_t c = rs.choff; c < d0; ++c)
         if (!written[c]) return false;
@@ -342,6 +371,12 @@ void pack_tail(const BlobOp &o, const BlobOp &R, const float *wr, Arena &tail, C
     pack_conv_weights_tail(wr, (int)R.cin, (int)R.cout, order_tail(R.src[0], (int)o.dst_choff, (int)o.cout), tail.at(c.tail_off));
 }
 
+// conv_s4.hip down: the same for the 1x1 conv R behind o (is_conv_down), four cout tiles.  Into the plan's down region
+void pack_down(const BlobOp &o, const BlobOp &R, const float *wr, Arena &down, ConvPlan &c) {
+    c.down_off = down.take(down_packed_floats(), 16);
+    pack_conv_weights_down(wr, (int)R.cin, (int)R.cout, order_tail(R.src[0], (int)o.dst_choff, (int)o.cout), down.at(c.down_off));
+}
+
 void pack_front(const BlobOp &o, const float *ws, Arena &a, ConvPlan &c) {   // 3x3 stride 2, one range
     const KOrder ko = order_plain(o.src, 1);
     c.front_off = a.take(s4_packed_floats(ko, (int)o.cout, 3, 0), 16);
@@ -381,6 +416,8 @@ int build_plan_weights(pf_plan &p, const float *wts, std::vector<float> &host) {
     Arena a{host};
     p.tail_host.assign(64, 0.f);
     Arena tail{p.tail_host};
+    p.down_host.assign(64, 0.f);
+    Arena down{p.down_host};
     const std::vector<BlobOp> &ops = p.net.ops;
     p.conv.assign(ops.size(), ConvPlan());
     for (size_t i = 0; i < ops.size(); ++i) {
@@ -404,6 +441,7 @@ int build_plan_weights(pf_plan &p, const float *wts, std::vector<float> &host) {
         if (i > 0 && p.opt.share_s && is_conv_pair(p.net, i - 1)) pack_share(ops[i - 1], wts + ops[i - 1].w_off, o, ws, a, c);
         if (o.k == 3 && o.stride == 2 && o.kind == OP_CONV && o.n_src == 1 && (o.src[0].choff & 3) == 0 && o.cout <= 32) pack_front(o, ws, a, c);
         if (i > 0 && p.opt.fold_final && is_conv_tail(p.net, i - 1)) pack_tail(ops[i - 1], o, ws, tail, p.conv[i - 1]);   // (o = the reader)
+        if (i > 0 && p.opt.fold_down && is_conv_down(p.net, i - 1)) pack_down(ops[i - 1], o, ws, down, p.conv[i - 1]);   // (likewise)
         if (o.stride == 1) pack_wave(o, w, src_ch, a, c);
         if (o.kind == OP_STEM) pack_stem(o, w, (int)p.net.hdr.n_cls, a, c);
         a.take(0, 64);
@@ -418,6 +456,7 @@ int build_plan_weights(pf_plan &p, const float *wts, std::vector<float> &host) {
         a.take(0, 64);
     }
     if (p.tail_host.size() == 64) p.tail_host.clear();   // no op has the form
+    if (p.down_host.size() == 64) p.down_host.clear();
     return PF_OK;
 }
 
@@ -474,6 +513,8 @@ extern "C" int pf_hardnet_plan_create(const void *blob, size_t bytes, int in_ch,
     if (e == hipSuccess) e = hipMemcpy(p->dev_lut, lut, 256, hipMemcpyHostToDevice);
     if (e == hipSuccess && !p->tail_host.empty()) e = hipMalloc((void **)&p->dev_tail, p->tail_host.size() * sizeof(float));
     if (e == hipSuccess && p->dev_tail) e = hipMemcpy(p->dev_tail, p->tail_host.data(), p->tail_host.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !p->down_host.empty()) e = hipMalloc((void **)&p->dev_down, p->down_host.size() * sizeof(float));
+    if (e == hipSuccess && p->dev_down) e = hipMemcpy(p->dev_down, p->down_host.data(), p->down_host.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         pf_hardnet_plan_destroy(p);
         return fail(PF_EHIP, "plan upload: %s", hipGetErrorString(e));
@@ -508,11 +549,11 @@ extern "C" int pf_debug_plan_arena(const void *blob, size_t bytes, int in_ch, in
     return PF_OK;
 }
 
-// Host only, as pf_debug_plan_arena: the tail region of that plan ("fold_final"; its first 64 floats are zeros) and per op of the table its
-// offset into it (0 = the op has no tail packing)
-extern "C" int pf_debug_plan_tail(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
-                                  long long *table, int table_ops) {
-    if (!blob || !n_floats) return fail(PF_EINVAL, "pf_debug_plan_tail: null argument");
+// Host only, as pf_debug_plan_arena: the tail ("fold_final") or down ("fold_down") region of that plan (its first 64 floats are zeros) and
+// per op of the table its offset into it (0 = the op has no such packing)
+static int debug_plan_region(const char *who, bool down, const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                             long long *table, int table_ops) {
+    if (!blob || !n_floats) return fail(PF_EINVAL, "%s: null argument", who);
     pf_plan p;
     p.opt = g_plan_opt;
     int rc = parse_net_table(blob, bytes, in_ch, n_cls, p.net);
@@ -523,10 +564,19 @@ extern "C" int pf_debug_plan_tail(const void *blob, size_t bytes, int in_ch, int
     std::vector<float> wnorm(w0, w0 + n_w), host;
     normalize_ranges(&p, wnorm);
     if ((rc = build_plan_weights(p, wnorm.data(), host))) return rc;
-    *n_floats = p.tail_host.size();
-    if (out && cap >= p.tail_host.size() && !p.tail_host.empty()) memcpy(out, p.tail_host.data(), p.tail_host.size() * sizeof(float));
-    for (int i = 0; table && i < table_ops && i < (int)p.conv.size(); ++i) table[i] = (long long)p.conv[i].tail_off;
+    const std::vector<float> &region = down ? p.down_host : p.tail_host;
+    *n_floats = region.size();
+    if (out && cap >= region.size() && !region.empty()) memcpy(out, region.data(), region.size() * sizeof(float));
+    for (int i = 0; table && i < table_ops && i < (int)p.conv.size(); ++i) table[i] = (long long)(down ? p.conv[i].down_off : p.conv[i].tail_off);
     return PF_OK;
+}
+extern "C" int pf_debug_plan_tail(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                                  long long *table, int table_ops) {
+    return debug_plan_region("pf_debug_plan_tail", false, blob, bytes, in_ch, n_cls, out, cap, n_floats, table, table_ops);
+}
+extern "C" int pf_debug_plan_down(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                                  long long *table, int table_ops) {
+    return debug_plan_region("pf_debug_plan_down", true, blob, bytes, in_ch, n_cls, out, cap, n_floats, table, table_ops);
 }
 
 extern "C" void pf_hardnet_plan_destroy(pf_plan *p) {
@@ -534,5 +584,6 @@ extern "C" void pf_hardnet_plan_destroy(pf_plan *p) {
     if (p->dev_weights) (void)hipFree(p->dev_weights);
     if (p->dev_lut) (void)hipFree(p->dev_lut);
     if (p->dev_tail) (void)hipFree(p->dev_tail);
+    if (p->dev_down) (void)hipFree(p->dev_down);
     delete p;
 }

@@ -69,21 +69,21 @@ struct ConvArgs {
     int share_off;           // share form: first matrix row of C's part = P's couts rounded up to 4
     int share_cout;          // C's output channels
     float share_scale;       // share form: C's acc_scale (this launch's acc_scale is P's)
-    // ---- the tail form (conv_s4.hip: launch_conv_s4_tail; zero for every other launch): this launch's slice has one reader, a 1x1 conv
-    //      R without ReLU into fp32 NCHW, which is linear in its input: the launch keeps its values in registers, multiplies them (and the
-    //      centre pixels of R's other channels, read from their packed planes) by R's weights and stores R's output; its slice is never stored
-    const float *tail_w;     // pack_conv_weights_tail(): R's A fragments, [chunk 0: R's other channels, chunk 1: this launch's couts][term][64 lanes][8 fp16]
-    const float *tail_bias;  // R's bias, zero padded to 16
-    float tail_scale;        // R's acc_scale
-    const float *tail_src;   // R's other channels: the packed tensor they live in, tail_c4 channel groups (term stride = tail_c4 planes), ...
-    int tail_c4, tail_g0, tail_gn;   // ... its groups tail_g0 .. tail_g0 + tail_gn - 1 (tail_gn <= 8: one K = 32 chunk; 0: none)
-    float *tail_dst;         // R's destination [B, tail_ctotal, Hout, Wout] fp32, R's couts (<= 16) from channel tail_choff on
-    int tail_cout, tail_ctotal, tail_choff;
-    // ---- the down form (conv_s4.hip: launch_conv_s4_down; zero for every other launch): the slice is stored as by the plain form and its
-    //      values, still in registers, also feed the 1x1 conv R behind it, which has a ReLU, up to 64 couts and a 2x2 average pool: R's
-    //      pooled output is stored (packed pairs, or fp32 where its readers want that) and R's launch goes away.  R's operands are the tail form's: tail_w =
-    //      pack_conv_weights_down() ([cout tile 4][chunk][term][64 lanes][8 fp16]), tail_bias (zero padded to whole tiles), tail_scale,
-    //      tail_src / tail_c4 / tail_g0 / tail_gn, tail_cout (<= 64); tail_dst / tail_ctotal / tail_choff are not used
+    // ---- the fold forms (conv_s4.hip: launch_conv_s4_tail / _down; zero for every other launch): this launch L is a 3x3 conv whose slice
+    //      is read last by a 1x1 conv R.  L's finished values, still in registers as the two terms R would read back, are multiplied by
+    //      R's weights together with the centre pixels of R's other channels (read from their packed planes), so R's launch goes away.
+    //      R's operands, the same for every form:
+    const float *fold_w;     // pack_conv_weights_fold(): R's A fragments, [cout tile][chunk 0: R's other channels, chunk 1: this launch's couts][term][64 lanes][8 fp16]
+    const float *fold_bias;  // R's bias, zero padded to whole tiles
+    float fold_scale;        // R's acc_scale
+    const float *fold_src;   // R's other channels: the packed tensor they live in, fold_c4 channel groups (term stride = fold_c4 planes), ...
+    int fold_c4, fold_g0, fold_gn;   // ... its groups fold_g0 .. fold_g0 + fold_gn - 1 (fold_gn <= 8: one K = 32 chunk; 0: none)
+    //      tail: R has no ReLU and at most 16 couts and goes to fp32 NCHW; it is linear in its input and the slice's only reader, so the
+    //      slice is never stored
+    float *tail_dst;         // R's destination [B, tail_ctotal, Hout, Wout] fp32, R's couts from channel tail_choff on
+    int fold_cout, tail_ctotal, tail_choff;   // fold_cout: R's couts, whatever the form (tail: <= 16, down: <= 64)
+    //      down: R has a ReLU, up to 64 couts and a 2x2 average pool behind it.  The slice is stored as by the plain form; R's pooled
+    //      output is stored as packed pairs, or as fp32 where its readers want that
     float *down_dst;         // R's pooled destination: down_fmt = 1, the S4 layout [B][2 terms][down_c4][Hout / 2][Wout / 2][4] fp16 ...
     int down_c4, down_choff, down_limit;   // ... its channel groups, R's first channel in it and the dst_limit of R's stores;
     int down_fmt, down_ctotal;             // down_fmt = 0: fp32 [B, down_ctotal, Hout / 2, Wout / 2], R's couts from channel down_choff on
@@ -318,25 +318,24 @@ int launch_conv_s4_share(const ConvArgs &a, int nt, int B, hipStream_t stream);
 int launch_conv_s4_add(const ConvArgs &a, int nt, int B, hipStream_t stream);
 inline int share_row0(int p_cout) { return (p_cout + 3) / 4 * 4; }   // a lane's four couts never straddle the two convs
 bool share_wanted(int p_cin, int p_cout, int c_cin, int c_cout, int h, int w, int B, int mode);
-// the tail form: a 3x3 launch of two cout tiles per workgroup on 8 x 32 tiles that also computes the 1x1 conv R reading its slice
-// (ConvArgs::tail_..) and stores R's output instead of its own.  tail_wanted (conv_select.cpp): mode = the plan's fold_final option
-// (0 never, 1 the measured rule, 2 wherever the form exists); cin, cout = the 3x3 conv's, r_cout = R's
+// the fold forms: a 3x3 launch L of two cout tiles per workgroup on 8 x 32 tiles that also computes the 1x1 conv R reading its slice last
+// (ConvArgs::fold_..).  tail: R without ReLU, one cout tile, into fp32 (ConvArgs::tail_..); R's output is stored instead of L's slice.
+// down: R with ReLU, at most kDownTiles cout tiles, and the 2x2 average pool behind it (ConvArgs::down_..); L's slice is stored too.
+// tail_wanted / down_wanted (conv_select.cpp): mode = the plan's fold_final / fold_down option (0 never, 1 the measured rule, 2 wherever
+// the form exists); cin, cout = the 3x3 conv's, r_cout = R's
+enum FoldForm : int { FOLD_TAIL, FOLD_DOWN };
+constexpr int kFoldForms = 2;
 int launch_conv_s4_tail(const ConvArgs &a, int B, hipStream_t stream);
-bool tail_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode);
-constexpr int kTailChunks = 2;   // K = 32 chunks of R's A fragments: R's other channels (at most 8 groups), then the launch's 32 couts
-inline size_t tail_packed_floats() { return (size_t)kTailChunks * 2 * 64 * 4; }
-// R's weights (OIHW, 1x1, already scaled by its 2^k) in the tail form's K order (conv_ranges.h: order_tail, tail_channel)
-void pack_conv_weights_tail(const float *w_oihw, int cin, int cout, const KOrder &k, float *out);
-// the down form: a 3x3 launch of two cout tiles on 8 x 32 tiles that stores its slice and also computes the 1x1 conv R (ReLU, at most
-// kDownTiles cout tiles) with the 2x2 average pool behind it (ConvArgs::down_..).  down_wanted (conv_select.cpp): mode = the plan's
-// fold_down option (0 never, 1 the measured rule, 2 wherever the form exists); cin, cout = the 3x3 conv's, r_cout = R's
 int launch_conv_s4_down(const ConvArgs &a, int B, hipStream_t stream);
+bool tail_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode);
 bool down_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode);
-constexpr int kDownTiles = 4;    // R's cout tiles: [tile][chunk][term][64 lanes][8 fp16], zeros past R's couts
+constexpr int kTailChunks = 2;   // K = 32 chunks of R's A fragments: R's other channels (at most 8 groups), then the launch's 32 couts
+constexpr int kDownTiles = 4;    // the down form's fragments hold this many cout tiles of R, zeros past R's couts
 constexpr int kDownFragBytes = kDownTiles * kTailChunks * 2 * 64 * 16;
-inline size_t down_packed_floats() { return (size_t)kDownFragBytes / 4; }
-// R's weights as for pack_conv_weights_tail, cout tile by cout tile in the same K order
-void pack_conv_weights_down(const float *w_oihw, int cin, int cout, const KOrder &k, float *out);
+inline size_t fold_packed_floats(int ntiles) { return (size_t)ntiles * kTailChunks * 2 * 64 * 4; }
+// R's weights (OIHW, 1x1, already scaled by its 2^k) as [cout tile ntiles][chunk][term][64 lanes][8 fp16] in the folds' K order
+// (conv_ranges.h: order_tail, tail_channel)
+void pack_conv_weights_fold(const float *w_oihw, int cin, int cout, const KOrder &k, int ntiles, float *out);
 
 // conv_pair.hip: an odd HarDBlock layer P = conv3x3(S) computed inside its consumer C = conv3x3(P ++ S ++ others) (hardnet.py:177-194)
 struct PairArgs {

@@ -25,7 +25,7 @@ KOrder order_plain(const BlobSrc *src, int n);
 KOrder order_pair(const BlobSrc *src, int n);
 // the add launch of conv_s4.hip: the same consumer without S, its range 1
 KOrder order_add(const BlobSrc *src, int n);
-// the tail form of conv_s4.hip: the single range of a 1x1 reader R, cut at the slice [slice_choff, slice_choff + slice_ch) that ends it:
+// the fold forms of conv_s4.hip (tail, down): the single range of a 1x1 reader R, cut at the slice [slice_choff, slice_choff + slice_ch) that ends it:
 // [R's other channels (in front of the slice; may be empty), the slice]
 KOrder order_tail(const BlobSrc &src, int slice_choff, int slice_ch);
 // ... and its K order: R's input channel at K position e (0..7) of lane group g in chunk 0 (the other channels: group entries 2g and

@@ -104,15 +104,14 @@ struct S4Cfg {
 #include "conv_s4_kernel.inc"
 #undef S4_KERNEL_NAME
 #undef S4_KERNEL_EPI
-// the tail form (the launch also computes the 1x1 conv that alone reads its slice: launch_conv_s4_tail below), instantiated for two cout
-// tiles on 8 x 32 tiles without a K split at the plain form's launch bounds
+// the fold forms (the launch also computes the 1x1 conv that reads its slice last: launch_conv_s4_tail / _down below), instantiated for
+// two cout tiles on 8 x 32 tiles without a K split at the plain form's launch bounds.  tail: the 1x1 conv's output is stored, the slice not
 #define S4_KERNEL_NAME conv_s4_tail_kernel
 #define S4_KERNEL_EPI 3
 #include "conv_s4_kernel.inc"
 #undef S4_KERNEL_NAME
 #undef S4_KERNEL_EPI
-// the down form (the launch stores its slice and also computes the 1x1 conv + 2x2 average pool behind it: launch_conv_s4_down below),
-// instantiated for two cout tiles on 8 x 32 tiles without a K split at the plain form's launch bounds
+// down: the slice is stored, and the 2x2 average pool of the 1x1 conv's output
 #define S4_KERNEL_NAME conv_s4_down_kernel
 #define S4_KERNEL_EPI 4
 #include "conv_s4_kernel.inc"
@@ -135,6 +134,7 @@ struct S4Cfg {
 // one launcher for the six forms of the 3x3 kernel (conv_s4_kernel.inc); the label = the symbol rocprofv3 reports (bench.py looks
 // its PMC bytes up by it)
 enum S4Form { S4_PLAIN, S4_BLOCKED, S4_SHARE, S4_ADD, S4_TAIL, S4_DOWN };
+constexpr const char *kS4FormName[] = {"conv_s4_kernel", "conv_s4_blocked_kernel", "conv_s4_share_kernel", "conv_s4_add_kernel", "conv_s4_tail_kernel", "conv_s4_down_kernel"};
 template <S4Form FORM, int NT, int TW_, int TH_, int KS_>
 static constexpr auto s4_kernel() {   // (only the form asked for is instantiated)
     if constexpr (FORM == S4_PLAIN) return &conv_s4_kernel<NT, TW_, TH_, KS_>;
@@ -148,9 +148,7 @@ template <S4Form FORM, int NT, int TW_ = 32, int TH_ = 8, int KS_ = 1>
 static int launch_s4_form(const ConvArgs &a0, int B, hipStream_t s) {
     using C = S4Cfg<NT, TW_, TH_, KS_>;
     constexpr auto kernel = s4_kernel<FORM, NT, TW_, TH_, KS_>();
-    constexpr const char *name = FORM == S4_PLAIN ? "conv_s4_kernel" : FORM == S4_BLOCKED ? "conv_s4_blocked_kernel"
-                               : FORM == S4_SHARE ? "conv_s4_share_kernel" : FORM == S4_ADD ? "conv_s4_add_kernel"
-                               : FORM == S4_TAIL ? "conv_s4_tail_kernel" : "conv_s4_down_kernel";
+    constexpr const char *name = kS4FormName[FORM];
     ConvArgs a = a0;
     a.tilesX = (a.Wout + C::TW - 1) / C::TW;
     a.tilesY = (a.Hout + C::TH - 1) / C::TH;
@@ -165,12 +163,12 @@ static int launch_s4_form(const ConvArgs &a0, int B, hipStream_t s) {
     // share: the matrix instructions also produce the consumer's rows, stored as fp32 sums in groups of 4; add: reads them
     const int rows = FORM == S4_SHARE ? a.Cout + a.share_cout : a.Cout;
     const double sums = FORM == S4_SHARE || FORM == S4_ADD ? (double)(a.share_cout + 3) / 4 * 4 : 0.0;
-    // tail: both convs' flops; reads the 3x3 conv's input and the other channels of the 1x1 conv's, writes the 1x1 conv's output only
-    // down: both convs' flops too; writes its slice and a quarter of the 1x1 conv's pixels
+    // folds: both convs' flops; read the 3x3 conv's input and the other channels of the 1x1 conv's.  tail writes the 1x1 conv's output only,
+    // down its slice and a quarter of the 1x1 conv's pixels
     constexpr bool FOLD = FORM == S4_TAIL || FORM == S4_DOWN;
-    const double flops = 2.0 * px * rows * a.Cin * 9 + (FOLD ? 2.0 * px * a.tail_cout * (4 * a.tail_gn + a.Cout) : 0.0);
-    const double stored = FORM == S4_TAIL ? (double)a.tail_cout : FORM == S4_DOWN ? a.Cout + 0.25 * a.tail_cout : a.Cout + sums;
-    const double extra = FOLD ? px * 4 * a.tail_gn + (double)a.tail_cout * (4 * a.tail_gn + a.Cout) : 0.0;
+    const double flops = 2.0 * px * rows * a.Cin * 9 + (FOLD ? 2.0 * px * a.fold_cout * (4 * a.fold_gn + a.Cout) : 0.0);
+    const double stored = FORM == S4_TAIL ? (double)a.fold_cout : FORM == S4_DOWN ? a.Cout + 0.25 * a.fold_cout : a.Cout + sums;
+    const double extra = FOLD ? px * 4 * a.fold_gn + (double)a.fold_cout * (4 * a.fold_gn + a.Cout) : 0.0;
     ProfScope ps(s, label, flops, 4.0 * ((double)B * a.Cin * a.Hin * a.Win + px * stored + (double)rows * a.Cin * 9 + extra));
     hipLaunchKernelGGL(kernel, dim3(a.tilesX * a.tilesY, (a.ntiles + NT - 1) / NT, B), dim3(C::NTHR * C::KS), C::LDS_BYTES, s, a);
     PF_LAUNCH_CHECK(name);
@@ -206,36 +204,33 @@ int launch_conv_s4_add(const ConvArgs &a, int nt, int B, hipStream_t s) {
     PF_S4_SHARE(S4_ADD)
 }
 #undef PF_S4_SHARE
-// a = the 3x3 conv's plain launch with a.tail_.. filled: R's fragments, bias and scale, the planes of R's other channels, R's destination
+// the fold forms: a = the 3x3 conv's plain launch with R's operands (a.fold_..: fragments, bias and scale, the planes of R's other channels,
+// R's couts, at most max_cout) and the form's destination of R filled
+static int check_fold(const ConvArgs &a, const char *who, int max_cout) {
+    if (!a.src_fmt || !a.dst_fmt) return fail(PF_EINVAL, "%s: sources and the slice in the S4 layout only", who);
+    if ((a.Wout & 3) != 0 || a.Hin != a.Hout || a.Win != a.Wout) return fail(PF_EUNSUPPORTED, "%s: stride 1, width %% 4 == 0 only", who);
+    if (a.pool || a.res || a.no_bias || a.kacc || a.share) return fail(PF_EUNSUPPORTED, "%s: no fused epilogue stages of its own", who);
+    if (a.chunk_begin != 0 || a.chunk_end != a.nchunks) return fail(PF_EUNSUPPORTED, "%s: whole K range only", who);
+    if (a.ntiles != 2) return fail(PF_EUNSUPPORTED, "%s: %d cout tiles, the form is built for two", who, a.ntiles);
+    if (!a.fold_w || !a.fold_bias || a.fold_cout < 1 || a.fold_cout > max_cout || a.fold_gn < 0 || a.fold_gn > 8 || (a.fold_gn && !a.fold_src) ||
+        (reinterpret_cast<uintptr_t>(a.fold_w) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.fold_bias) & 15) != 0 || a.fold_g0 < 0 ||
+        a.fold_g0 + a.fold_gn > a.fold_c4)
+        return fail(PF_EINVAL, "%s: second conv of %d couts over %d groups", who, a.fold_cout, a.fold_gn);
+    return PF_OK;
+}
 int launch_conv_s4_tail(const ConvArgs &a, int B, hipStream_t s) {
-    if (!a.src_fmt || !a.dst_fmt) return fail(PF_EINVAL, "conv_s4 tail: sources and the (elided) slice in the S4 layout only");
-    if ((a.Wout & 3) != 0 || a.Hin != a.Hout || a.Win != a.Wout) return fail(PF_EUNSUPPORTED, "conv_s4 tail: stride 1, width %% 4 == 0 only");
-    if (a.pool || a.res || a.no_bias || a.kacc || a.share) return fail(PF_EUNSUPPORTED, "conv_s4 tail: no fused epilogue stages");
-    if (a.chunk_begin != 0 || a.chunk_end != a.nchunks) return fail(PF_EUNSUPPORTED, "conv_s4 tail: whole K range only");
-    if (a.ntiles != 2) return fail(PF_EUNSUPPORTED, "conv_s4 tail: %d cout tiles, the form is built for two", a.ntiles);
-    if (!a.tail_w || !a.tail_bias || !a.tail_dst || a.tail_cout < 1 || a.tail_cout > 16 || a.tail_gn < 0 || a.tail_gn > 8 || (a.tail_gn && !a.tail_src) ||
-        a.tail_choff < 0 || a.tail_choff + a.tail_cout > a.tail_ctotal || (reinterpret_cast<uintptr_t>(a.tail_w) & 15) != 0 ||
-        (reinterpret_cast<uintptr_t>(a.tail_bias) & 15) != 0 || a.tail_g0 < 0 || a.tail_g0 + a.tail_gn > a.tail_c4)
-        return fail(PF_EINVAL, "conv_s4 tail: second conv of %d couts over %d groups", a.tail_cout, a.tail_gn);
+    if (int rc = check_fold(a, "conv_s4 tail", 16)) return rc;
+    if (!a.tail_dst || a.tail_choff < 0 || a.tail_choff + a.fold_cout > a.tail_ctotal)
+        return fail(PF_EINVAL, "conv_s4 tail: second conv of %d couts over %d groups", a.fold_cout, a.fold_gn);
     return launch_s4_form<S4_TAIL, 2>(a, B, s);
 }
-// a = the 3x3 conv's plain launch with R's operands (a.tail_w / tail_bias / tail_scale / tail_src .. / tail_cout) and R's pooled
-// destination (a.down_..) filled
 int launch_conv_s4_down(const ConvArgs &a, int B, hipStream_t s) {
-    if (!a.src_fmt || !a.dst_fmt) return fail(PF_EINVAL, "conv_s4 down: sources and the slice in the S4 layout only");
-    if ((a.Wout & 3) != 0 || a.Hin != a.Hout || a.Win != a.Wout) return fail(PF_EUNSUPPORTED, "conv_s4 down: stride 1, width %% 4 == 0 only");
-    if (a.pool || a.res || a.no_bias || a.kacc || a.share) return fail(PF_EUNSUPPORTED, "conv_s4 down: no fused epilogue stages of its own");
-    if (a.chunk_begin != 0 || a.chunk_end != a.nchunks) return fail(PF_EUNSUPPORTED, "conv_s4 down: whole K range only");
-    if (a.ntiles != 2) return fail(PF_EUNSUPPORTED, "conv_s4 down: %d cout tiles, the form is built for two", a.ntiles);
+    if (int rc = check_fold(a, "conv_s4 down", 16 * kDownTiles)) return rc;
     if (a.Hout < 2 || a.Wout < 2) return fail(PF_EUNSUPPORTED, "conv_s4 down: nothing to pool at %d x %d", a.Hout, a.Wout);
-    if (!a.tail_w || !a.tail_bias || a.tail_cout < 1 || a.tail_cout > 16 * kDownTiles || a.tail_gn < 0 || a.tail_gn > 8 || (a.tail_gn && !a.tail_src) ||
-        (reinterpret_cast<uintptr_t>(a.tail_w) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.tail_bias) & 15) != 0 || a.tail_g0 < 0 ||
-        a.tail_g0 + a.tail_gn > a.tail_c4)
-        return fail(PF_EINVAL, "conv_s4 down: second conv of %d couts over %d groups", a.tail_cout, a.tail_gn);
-    const bool packed_ok = (a.down_choff & 1) == 0 && a.down_limit >= a.down_choff + a.tail_cout && a.down_limit <= 4 * a.down_c4 &&
-                           a.down_limit <= (a.down_choff + a.tail_cout + 3) / 4 * 4;
-    if (!a.down_dst || a.down_choff < 0 || (a.down_fmt ? !packed_ok : a.down_choff + a.tail_cout > a.down_ctotal))
-        return fail(PF_EINVAL, "conv_s4 down: pooled destination of %d channels from %d (limit %d) in %d groups", a.tail_cout, a.down_choff, a.down_limit, a.down_c4);
+    const bool packed_ok = (a.down_choff & 1) == 0 && a.down_limit >= a.down_choff + a.fold_cout && a.down_limit <= 4 * a.down_c4 &&
+                           a.down_limit <= (a.down_choff + a.fold_cout + 3) / 4 * 4;
+    if (!a.down_dst || a.down_choff < 0 || (a.down_fmt ? !packed_ok : a.down_choff + a.fold_cout > a.down_ctotal))
+        return fail(PF_EINVAL, "conv_s4 down: pooled destination of %d channels from %d (limit %d) in %d groups", a.fold_cout, a.down_choff, a.down_limit, a.down_c4);
     return launch_s4_form<S4_DOWN, 2>(a, B, s);
 }
 
@@ -686,9 +681,10 @@ void pack_conv_weights_s4(const float *w, int cin, int cout, int ks, const KOrde
         }
 }
 
-// the tail form's second conv: [chunk][term 2][lane 64][8 fp16], lane = (cout lane & 15, lane group g), value e = R's weight of the
-// input channel tail_channel(k, chunk, g, e) (conv_ranges.cpp), zero where there is none
-static void pack_tail_tiles(const float *w, int cin, int cout, const KOrder &k, int ntiles, unsigned short *out) {
+// the fold forms' second conv R: [cout tile ntiles][chunk][term 2][lane 64][8 fp16], lane = (cout lane & 15 of the tile, lane group g),
+// value e = R's weight of the input channel tail_channel(k, chunk, g, e) (conv_ranges.cpp), zero where there is none and past R's couts
+void pack_conv_weights_fold(const float *w, int cin, int cout, const KOrder &k, int ntiles, float *out_f) {
+    unsigned short *out = reinterpret_cast<unsigned short *>(out_f);
     size_t o = 0;
     for (int t = 0; t < ntiles; ++t)
         for (int chunk = 0; chunk < kTailChunks; ++chunk)
@@ -700,13 +696,6 @@ static void pack_tail_tiles(const float *w, int cin, int cout, const KOrder &k, 
                         const unsigned short hi = split_host_f16(v);
                         out[o++] = term == 0 ? hi : split_host_f16(v - split_host_f32(hi));
                     }
-}
-void pack_conv_weights_tail(const float *w, int cin, int cout, const KOrder &k, float *out_f) {
-    pack_tail_tiles(w, cin, cout, k, 1, reinterpret_cast<unsigned short *>(out_f));
-}
-// the down form's second conv: the same per cout tile, [tile kDownTiles][chunk][term 2][lane 64][8 fp16], zeros past R's couts
-void pack_conv_weights_down(const float *w, int cin, int cout, const KOrder &k, float *out_f) {
-    pack_tail_tiles(w, cin, cout, k, kDownTiles, reinterpret_cast<unsigned short *>(out_f));
 }
 
 // ------------------------------------------------------------------------------------------------ layout conversion

@@ -6,12 +6,13 @@
 //   S4_KERNEL_EPI    0 | 1 "share" | 2 "add": the epilogue (DESIGN.md 4; ConvArgs::share ..).  share: matrix rows from a.share_off on are
 //                    ANOTHER conv's sums over this launch's source, stored as fp32 units of four channels (acc * a.share_scale; no bias,
 //                    no ReLU, no range report); the rows below it take the plain epilogue.  add: v = fma(acc, acc_scale, stored) + bias
-//                    3 "tail" (NT = 2; ConvArgs::tail_..): the finished values stay in registers as the two terms their single reader, a
-//                    1x1 conv R, would read back, and are multiplied by R's weights together with the centre pixels of R's other channels;
-//                    R's output is stored (fp32 NCHW), this conv's slice is not
-//                    4 "down" (NT = 2, 8 x 32 tiles; ConvArgs::tail_.. and down_..): the slice IS stored, as by the plain epilogue, and
-//                    the same values, still in registers, also feed a 1x1 conv R with ReLU of up to four cout tiles whose 2x2 average
-//                    pool - two M-tile rows of a wave, lane pairs of a row - is stored (packed pairs or fp32 NCHW): R's launch goes away
+//                    3 "tail" | 4 "down": the folds (NT = 2; ConvArgs::fold_..).  This conv's slice is read last by a 1x1 conv R.  The finished
+//                    values stay in registers as the two terms R would read back and are multiplied by R's weights together with the
+//                    centre pixels of R's other channels, so R's launch goes away.
+//                      tail (ConvArgs::tail_..): R has no ReLU and one cout tile; its output is stored (fp32 NCHW), this conv's slice is not
+//                      down (8 x 32 tiles; ConvArgs::down_..): the slice IS stored, as by the plain epilogue; R has a ReLU and up to four
+//                      cout tiles, and its 2x2 average pool - two M-tile rows of a wave, lane pairs of a row - is stored (packed pairs or
+//                      fp32 NCHW)
 template <int NT, int TW_, int TH_, int KS_>
 __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAME(ConvArgs a) {
     [[maybe_unused]] constexpr int KACC = S4_KERNEL_KACC;
@@ -336,20 +337,20 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
         [[maybe_unused]] s4_f32x4 tbias = s4_f32x4{0.f, 0.f, 0.f, 0.f};
         if constexpr (EPI == 3) {
             static_assert(NT == 2, "a lane's 4 + 4 split values of two cout tiles are one K slice of the second conv");
-            const s4_h8 *tw = reinterpret_cast<const s4_h8 *>(a.tail_w);
+            const s4_h8 *tw = reinterpret_cast<const s4_h8 *>(a.fold_w);
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 tw_h[c] = tw[(c * 2 + 0) * 64 + lane];
                 tw_m[c] = tw[(c * 2 + 1) * 64 + lane];
             }
-            tbias = *reinterpret_cast<const s4_f32x4 *>(a.tail_bias + 4 * (lane >> 4));
+            tbias = *reinterpret_cast<const s4_f32x4 *>(a.fold_bias + 4 * (lane >> 4));
         }
         if constexpr (EPI == 4) {
             static_assert(NT == 2 && TW_ == 32 && TH_ == 8 && KS_ == 1, "M-tiles m and m + 2 of a wave are two rows of the same 16 columns");
             static_assert(kDownFragBytes + kDownTiles * 16 * sizeof(float) <= C::STAGES_BYTES, "R's fragments and bias live in the stage ring");
-            const int rt = (a.tail_cout + 15) >> 4;             // R's cout tiles (uniform)
+            const int rt = (a.fold_cout + 15) >> 4;             // R's cout tiles (uniform)
             __syncthreads();                                    // every wave is done reading the ring
-            const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void *)a.tail_w, 0, 0x7FFFFFFF, 0x00020000);
+            const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void *)a.fold_w, 0, 0x7FFFFFFF, 0x00020000);
 #pragma unroll
             for (int it = 0; it < kDownFragBytes / 16 / C::NTHR; ++it) {
                 const int p = it * C::NTHR + tid;               // 16-B piece; a cout tile is 256 of them
@@ -357,14 +358,14 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                                                          p < rt * 256 ? (unsigned)p * 16u : kS4Oob, 0, 0, 0);
             }
             if (wave == 0) {                                    // R's bias: 64 values, zero past its tiles
-                const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void *)a.tail_bias, 0, 0x7FFFFFFF, 0x00020000);
+                const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void *)a.fold_bias, 0, 0x7FFFFFFF, 0x00020000);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, (s4_lds_ptr_t)(smem_all + kDownFragBytes), 4, lane < rt * 16 ? (unsigned)lane * 4u : kS4Oob,
                                                          0, 0, 0);
             }
         }
         if constexpr (FOLD) {
-            const size_t tstride = (size_t)a.tail_c4 * plane_bytes;
-            const char *tbase = reinterpret_cast<const char *>(a.tail_src) + (size_t)b * 2 * tstride;
+            const size_t tstride = (size_t)a.fold_c4 * plane_bytes;
+            const char *tbase = reinterpret_cast<const char *>(a.fold_src) + (size_t)b * 2 * tstride;
 #pragma unroll
             for (int m = 0; m < C::MP; ++m) {
                 const int mt = wave * C::MP + m;
@@ -374,8 +375,8 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int e = 2 * (lane >> 4) + h;
-                    const bool real = in && e < a.tail_gn;
-                    const char *p = real ? tbase + (size_t)(a.tail_g0 + e) * plane_bytes + ((size_t)oy * a.Wout + ox) * 8
+                    const bool real = in && e < a.fold_gn;
+                    const char *p = real ? tbase + (size_t)(a.fold_g0 + e) * plane_bytes + ((size_t)oy * a.Wout + ox) * 8
                                          : reinterpret_cast<const char *>(a.zero_page);
                     to_h[m][h] = *reinterpret_cast<const s4_h4 *>(p);
                     to_m[m][h] = *reinterpret_cast<const s4_h4 *>(real ? p + tstride : p);
@@ -417,6 +418,23 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 }
             }
         };
+        // folds: R's chunk 0 operand of M-tile m, the centre pixels of its other channels (K slice g: group entries 2g, 2g + 1)
+        [[maybe_unused]] auto fold_chunk0 = [&](int m, s4_h8 &x0h, s4_h8 &x0m) {
+            x0h = s4_join(to_h[m][0], to_h[m][1]); x0m = s4_join(to_m[m][0], to_m[m][1]);
+        };
+        // ... and R's sum for one M-tile and one of its cout tiles: chunk 0 (its other channels), then chunk 1 (this launch's), three
+        // products each, one fp32 accumulator
+        [[maybe_unused]] auto fold_products = [](const s4_h8 &wh0, const s4_h8 &wm0, const s4_h8 &wh1, const s4_h8 &wm1, const s4_h8 &x0h, const s4_h8 &x0m,
+                                                 const s4_h8 &x1h, const s4_h8 &x1m) {
+            s4_f32x4 t = s4_f32x4{0.f, 0.f, 0.f, 0.f};
+            t = PF_MFMA_SPLIT(wh0, x0m, t);
+            t = PF_MFMA_SPLIT(wm0, x0h, t);
+            t = PF_MFMA_SPLIT(wh0, x0h, t);
+            t = PF_MFMA_SPLIT(wh1, x1m, t);
+            t = PF_MFMA_SPLIT(wm1, x1h, t);
+            t = PF_MFMA_SPLIT(wh1, x1h, t);
+            return t;
+        };
         [[maybe_unused]] s4_h8 dx0h[EPI == 4 ? C::MP : 1], dx0m[EPI == 4 ? C::MP : 1], dx1h[EPI == 4 ? C::MP : 1], dx1m[EPI == 4 ? C::MP : 1];
 #pragma unroll
         for (int m = 0; m < C::MP; ++m) {
@@ -441,28 +459,24 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                     split_terms4(v, xh[n], xm[n]);
                 }
                 const s4_h8 x1h = s4_join(xh[0], xh[1]), x1m = s4_join(xm[0], xm[1]);
-                const s4_h8 x0h = s4_join(to_h[m][0], to_h[m][1]), x0m = s4_join(to_m[m][0], to_m[m][1]);
-                // R's sum: chunk 0 (its other channels), then chunk 1 (this launch's), three products each, one fp32 accumulator
-                s4_f32x4 t = s4_f32x4{0.f, 0.f, 0.f, 0.f};
-                t = PF_MFMA_SPLIT(tw_h[0], x0m, t);
-                t = PF_MFMA_SPLIT(tw_m[0], x0h, t);
-                t = PF_MFMA_SPLIT(tw_h[0], x0h, t);
-                t = PF_MFMA_SPLIT(tw_h[1], x1m, t);
-                t = PF_MFMA_SPLIT(tw_m[1], x1h, t);
-                t = PF_MFMA_SPLIT(tw_h[1], x1h, t);
+                s4_h8 x0h, x0m;
+                fold_chunk0(m, x0h, x0m);
+                const s4_f32x4 t = fold_products(tw_h[0], tw_m[0], tw_h[1], tw_m[1], x0h, x0m, x1h, x1m);
                 if (in) {
                     const size_t pix = (size_t)oy * a.Wout + ox;
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (4 * g + r < a.tail_cout)
-                            a.tail_dst[((size_t)b * a.tail_ctotal + a.tail_choff + 4 * g + r) * hw + pix] = t[r] * a.tail_scale + tbias[r];
+                        if (4 * g + r < a.fold_cout)
+                            a.tail_dst[((size_t)b * a.tail_ctotal + a.tail_choff + 4 * g + r) * hw + pix] = t[r] * a.fold_scale + tbias[r];
                 }
                 continue;
             }
             if constexpr (EPI == 4) {
                 // the plain epilogue for every lane (rows past this launch's couts: zero weights, zero bias -> 0), the slice stored as the
                 // plain form stores it; the same values split into the two terms R would read back are K slice g of R's chunk 1, as in
-                // the tail form, and are kept for all four M-tiles next to chunk 0's
+                // the tail form, and are kept for all four M-tiles next to chunk 0's.  (The finishing loop is the tail form's, written out
+                // twice: as a shared lambda, capturing or not, it changes the register allocation of both kernels, which sit at 114 and
+                // 117 of 128 registers.  Likewise the pooled store below is store_px written out for R's destination)
                 const bool in = oy < a.Hout && ox < a.Wout;
                 s4_h4 xh[2], xm[2];
 #pragma unroll
@@ -478,7 +492,7 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                     if (in && co < a.Cout + 2) store_px(co, (size_t)oy * a.Wout + ox, v);
                 }
                 dx1h[m] = s4_join(xh[0], xh[1]); dx1m[m] = s4_join(xm[0], xm[1]);
-                dx0h[m] = s4_join(to_h[m][0], to_h[m][1]); dx0m[m] = s4_join(to_m[m][0], to_m[m][1]);
+                fold_chunk0(m, dx0h[m], dx0m[m]);
                 continue;
             }
             if (oy >= a.Hout || ox >= a.Wout) continue;
@@ -519,13 +533,12 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
             }
         }
         if constexpr (EPI == 4) {
-            // R, one cout tile at a time: six K = 32 products per M-tile into one fp32 accumulator - chunk 0 (R's other channels), then
-            // chunk 1 (this launch's) - then 2^-k, bias, ReLU (R has one: plan_create.hip is_conv_down) and the 2x2 average pool in
+            // R, one cout tile at a time: fold_products per M-tile, then 2^-k, bias, ReLU (R has one: plan_create.hip is_conv_down) and the 2x2 average pool in
             // registers.  M-tiles 0, 1 are row 2w of the tile (columns 0-15, 16-31), M-tiles 2, 3 row 2w + 1; the horizontal neighbour
             // sits in lane px ^ 1.  Even lanes pool M-tiles 0 / 2, odd lanes M-tiles 1 / 3: a lane sends its neighbour the value of the
             // tile the neighbour pools, so the 16 lanes of a lane group store 16 consecutive pooled pixels, 128 B per term.
             // (((a + b) + c) + d) * 0.25, a, b = row oy at x, x + 1: the order of avgpool2_kernel and conv_s4_1x1_kernel
-            const int rt = (a.tail_cout + 15) >> 4;
+            const int rt = (a.fold_cout + 15) >> 4;
             const int Ho = a.Hout >> 1, Wo = a.Wout >> 1;       // a last row or column the pool drops is not stored
             const size_t hw2 = (size_t)Ho * Wo, term2 = (size_t)a.down_c4 * hw2 * 8;
             const bool mis2 = (a.down_choff & 2) != 0, odd = (px & 1) != 0;
@@ -546,15 +559,9 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 s4_f32x4 v[C::MP];
 #pragma unroll
                 for (int m = 0; m < C::MP; ++m) {
-                    s4_f32x4 t = s4_f32x4{0.f, 0.f, 0.f, 0.f};
-                    t = PF_MFMA_SPLIT(wh0, dx0m[m], t);
-                    t = PF_MFMA_SPLIT(wm0, dx0h[m], t);
-                    t = PF_MFMA_SPLIT(wh0, dx0h[m], t);
-                    t = PF_MFMA_SPLIT(wh1, dx1m[m], t);
-                    t = PF_MFMA_SPLIT(wm1, dx1h[m], t);
-                    t = PF_MFMA_SPLIT(wh1, dx1h[m], t);
+                    const s4_f32x4 t = fold_products(wh0, wm0, wh1, wm1, dx0h[m], dx0m[m], dx1h[m], dx1m[m]);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[m][r] = fmaxf(t[r] * a.tail_scale + b4[r], 0.f);
+                    for (int r = 0; r < 4; ++r) v[m][r] = fmaxf(t[r] * a.fold_scale + b4[r], 0.f);
                 }
                 s4_f32x4 pv;
 #pragma unroll
@@ -569,8 +576,8 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 if (pin && !a.down_fmt) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (co + r < a.tail_cout) reinterpret_cast<float *>(a.down_dst)[((size_t)b * a.down_ctotal + chb + r) * hw2 + ppix] = pv[r];
-                } else if (pin && co < a.tail_cout + 2) {
+                        if (co + r < a.fold_cout) reinterpret_cast<float *>(a.down_dst)[((size_t)b * a.down_ctotal + chb + r) * hw2 + ppix] = pv[r];
+                } else if (pin && co < a.fold_cout + 2) {
                     s4_h4 hi, mid;
                     split_terms4(pv, hi, mid);
                     const bool ok0 = chb < a.down_limit, ok1 = chb + 2 < a.down_limit;

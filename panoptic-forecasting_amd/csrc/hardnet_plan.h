@@ -39,14 +39,11 @@ struct ConvPlan {
     // [P's rows; C's rows over the columns of S] over S (share_a_tiles cout tiles), and C without the columns of S (share_b_rounds rounds)
     size_t share_a_off = 0, share_b_off = 0;
     int share_a_tiles = 0, share_b_rounds = 0;
-    // the tail form (conv_s4.hip), kept on the PRODUCER (op i; the 1x1 conv that alone reads its slice is op i + 1) and packed only by
-    // plans created with fold_final != 0: the reader's A fragments, an offset in floats into the plan's tail region (pf_plan::dev_tail,
-    // whose first 64 floats are zeros: 0 = the op has none).  A region of its own: the weight arena stays what it was without the form
-    size_t tail_off = 0;
-    // the down form (conv_s4.hip), kept on the PRODUCER too (op i; op i + 1 is the 1x1 conv with ReLU whose range ends with its slice, op
-    // i + 2 that conv's 2x2 average pool) and packed only by plans created with fold_down != 0: the 1x1 conv's A fragments, an offset in
-    // floats into the plan's down region (pf_plan::dev_down, first 64 floats zeros: 0 = none).  A region of its own beside the other two
-    size_t down_off = 0;
+    // the fold forms (conv_s4.hip; kFolds below), kept on the PRODUCER L (op i; the 1x1 conv R that reads its slice last is op i + 1) and
+    // packed only by plans created with the form's option != 0: R's A fragments, an offset in floats into the form's region
+    // (pf_plan::fold, whose first 64 floats are zeros: 0 = the op has none).  Regions of their own: the weight arena stays what it was
+    // without the forms
+    size_t fold_off[pf::kFoldForms] = {0, 0};
 };
 
 // The switches a plan carries (include/pfhip.h documents each), with their defaults.  g_plan_opt is the process-wide set
@@ -63,12 +60,10 @@ struct PlanOptions {
     int fuse_pairs = 1;        // conv_pair.hip: an odd HarDBlock layer runs inside its consumer where both read / write packed pairs (0 = two launches)
     int share_s = 1;           // conv_s4.hip share / add: an odd HarDBlock layer's launch also sums its consumer's rows over their common source
                                // (0 = off, and a plan created with 0 packs nothing for it; 1 = conv_select.cpp::share_wanted; 2 = wherever built)
-    int fold_final = 1;        // conv_s4.hip tail: a 3x3 conv whose slice has one reader, a small 1x1 conv into fp32, also computes that conv
-                               // and never stores its slice (0 = off, and a plan created with 0 packs nothing for it; 1 = conv_select.cpp::tail_wanted;
-                               // 2 = wherever built)
-    int fold_down = 1;         // conv_s4.hip down: a 3x3 conv in front of a 1x1 conv with ReLU + 2x2 average pool that reads its slice last also
-                               // computes that conv and its pool; the slice is stored as ever (0 = off, and a plan created with 0 packs nothing for
-                               // it; 1 = conv_select.cpp::down_wanted; 2 = wherever built)
+    // conv_s4.hip folds: a 3x3 conv's launch also computes the 1x1 conv that reads its slice last (0 = off, and a plan created with 0 packs
+    // nothing for the form; 1 = the form's rule in conv_select.cpp; 2 = wherever built).  The forms: kFolds below
+    int fold_final = 1;        // tail: the 1x1 conv is small, goes to fp32 and is the slice's only reader; the slice is never stored
+    int fold_down = 1;         // down: the 1x1 conv has a ReLU and a 2x2 average pool behind it, which the launch computes too; the slice is stored as ever
 };
 
 struct pf_plan {
@@ -78,10 +73,10 @@ struct pf_plan {
     float *dev_weights = nullptr;
     uint8_t *dev_lut = nullptr;
     size_t dev_floats = 0;
-    std::vector<float> tail_host;   // the tail form's packings (ConvPlan::tail_off), empty when the plan has none ...
-    float *dev_tail = nullptr;      // ... and their upload
-    std::vector<float> down_host;   // the down form's packings (ConvPlan::down_off), likewise
-    float *dev_down = nullptr;
+    struct FoldRegion {
+        std::vector<float> host;    // the form's packings (ConvPlan::fold_off), empty when the plan has none ...
+        float *dev = nullptr;       // ... and their upload
+    } fold[pf::kFoldForms];
     PlanOptions opt;             // read only by forwards of this plan
     // formats of the last forward (pf_hardnet_tensor_read): 1 = S4, 0xFF = elided (never stored: conv_front.hip), 0xFE = its last
     // slice elided (never stored: the tail form of conv_s4.hip)
@@ -115,11 +110,21 @@ int layout(const pf_plan *p, int B, int H, int W, std::vector<Dims> &d, std::vec
 
 // ops i (P) and i + 1 (C) form a pair conv_pair.hip can run as one launch (plan_create.hip)
 bool is_conv_pair(const NetTable &t, size_t i);
-// op i is a 3x3 conv whose slice has exactly one reader, op i + 1, a 1x1 conv the tail form of conv_s4.hip can compute in op i's
-// launch (plan_create.hip)
-bool is_conv_tail(const NetTable &t, size_t i);
-// op i is a 3x3 conv in front of a 1x1 conv with ReLU (op i + 1) and its 2x2 average pool (op i + 2) that the down form of conv_s4.hip
-// can compute in op i's launch; other ops may read op i's slice too (plan_create.hip)
-bool is_conv_down(const NetTable &t, size_t i);
+// What distinguishes the fold forms (FoldForm: conv_mfma.h).  Common to all: L = op i, a 3x3 stride-1 conv of two cout tiles; R = op i + 1,
+// a 1x1 stride-1 conv whose single range ends with L's slice
+struct FoldDesc {
+    bool r_relu;                    // R's ReLU
+    int r_tiles;                    // R's cout tiles at most = the tiles its fragments are packed as
+    bool pool;                      // op i + 2 is R's 2x2 average pool and the only reader of R's output
+    bool other_readers;             // ops other than R may read L's slice (it is stored)
+    int PlanOptions::*option;
+    bool (*wanted)(int cin, int cout, int r_cout, int h, int w, int B, int mode);
+};
+constexpr FoldDesc kFolds[kFoldForms] = {
+    {false, 1, false, false, &PlanOptions::fold_final, tail_wanted},     // FOLD_TAIL
+    {true, kDownTiles, true, true, &PlanOptions::fold_down, down_wanted},   // FOLD_DOWN
+};
+// ops i (L) and i + 1 (R) have the form: conv_s4.hip can compute R in L's launch (plan_create.hip)
+bool is_conv_fold(const NetTable &t, size_t i, FoldForm form);
 
 }  // namespace pf

@@ -435,62 +435,49 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
     }
     steps.resize(w);
 
-    // ---- 6. a 3x3 conv L whose slice has one reader, the 1x1 conv R behind it (is_conv_tail), as ONE launch (conv_s4.hip tail): two adjacent
-    //      plain conv_s4 steps, L on <2, 32, 8, 1> into packed pairs, R without fused stages into fp32.  L's slice is never stored
-    for (size_t k = 0; p->opt.fold_final && p->dev_tail && k + 1 < steps.size(); ++k) {
-        Step &sl = steps[k];
-        const Step &sr = steps[k + 1];
-        const size_t i = (size_t)sl.op;
-        if (sl.kind != S_CONV_S4 || sr.kind != S_CONV_S4 || sl.ci != (int)i || sr.op != (int)i + 1 || sr.ci != (int)i + 1) continue;
-        if (!p->conv[i].tail_off || !is_conv_tail(p->net, i)) continue;
-        const BlobOp &L = p->net.ops[i], &R = p->net.ops[i + 1];
-        ConvArgs &a = sl.u.c;
-        const ConvArgs &r = sr.u.c;
-        const S4Shape &sh = sl.dec.s4;
-        if (sh.NT != 2 || sh.TW != 32 || sh.TH != 8 || sh.KS != 1 || !a.dst_fmt || r.dst_fmt || r.status || r.pool || r.res || r.no_bias || a.Hout != r.Hout || a.Wout != r.Wout) continue;
-        if (!tail_wanted((int)L.cin, (int)L.cout, (int)R.cout, a.Hout, a.Wout, Bt, p->opt.fold_final)) continue;
-        const KOrder ko = order_tail(R.src[0], (int)L.dst_choff, (int)L.cout);
-        a.tail_w = p->dev_tail + p->conv[i].tail_off;
-        a.tail_bias = r.bias; a.tail_scale = r.acc_scale;
-        a.tail_src = a.dst; a.tail_c4 = a.dst_c4; a.tail_g0 = ko.r[0].choff / 4; a.tail_gn = ko.r[0].ch / 4;
-        a.tail_dst = r.dst; a.tail_cout = r.Cout; a.tail_ctotal = r.dst_ctotal; a.tail_choff = r.dst_choff;
-        sl.kind = S_CONV_S4_TAIL;
-        if (tags)
-            snprintf(sl.tag, sizeof(sl.tag), "%02zu+%02zu %s+%s %u->%u->%u %dx%d", i, i + 1, p->net.tensors[L.dst].name, p->net.tensors[R.dst].name, L.cin,
-                     L.cout, R.cout, a.Hout, a.Wout);
-        fmt[L.dst] = 0xFE;   // pf_hardnet_tensor_read refuses the tensor: its last slice is never stored
-        steps.erase(steps.begin() + (long)k + 1);
-    }
-
-    // ---- 7. a 3x3 conv L in front of the 1x1 conv R + 2x2 average pool that ends a block (is_conv_down) as ONE launch (conv_s4.hip down):
-    //      two adjacent plain conv_s4 steps, L on <2, 32, 8, 1> into packed pairs - not part of a pair or a share / add step, whose kinds
-    //      differ -, R with its pool fused and nothing else, into packed pairs or fp32.  L's slice is stored as ever; R's step goes away
-    for (size_t k = 0; p->opt.fold_down && p->dev_down && k + 1 < steps.size(); ++k) {
-        Step &sl = steps[k];
-        const Step &sr = steps[k + 1];
-        const size_t i = (size_t)sl.op;
-        if (sl.kind != S_CONV_S4 || sr.kind != S_CONV_S4 || sl.ci != (int)i || sr.op != (int)i + 1 || sr.ci != (int)i + 1) continue;
-        if (!p->conv[i].down_off || !is_conv_down(p->net, i)) continue;
-        const BlobOp &L = p->net.ops[i], &R = p->net.ops[i + 1];
-        ConvArgs &a = sl.u.c;
-        const ConvArgs &r = sr.u.c;
-        const S4Shape &sh = sl.dec.s4;
-        if (sh.NT != 2 || sh.TW != 32 || sh.TH != 8 || sh.KS != 1 || !a.dst_fmt || !r.pool || r.res || r.no_bias || !r.relu || a.Hout != r.Hout || a.Wout != r.Wout) continue;
-        if (!down_wanted((int)L.cin, (int)L.cout, (int)R.cout, a.Hout, a.Wout, Bt, p->opt.fold_down)) continue;
-        const KOrder ko = order_tail(R.src[0], (int)L.dst_choff, (int)L.cout);
-        a.tail_w = p->dev_down + p->conv[i].down_off;
-        a.tail_bias = r.bias; a.tail_scale = r.acc_scale;
-        a.tail_src = a.dst; a.tail_c4 = a.dst_c4; a.tail_g0 = ko.r[0].choff / 4; a.tail_gn = ko.r[0].ch / 4;
-        a.tail_cout = r.Cout;
-        a.down_dst = r.dst; a.down_c4 = r.dst_c4; a.down_choff = r.dst_choff; a.down_limit = r.dst_limit;
-        a.down_fmt = r.dst_fmt; a.down_ctotal = r.dst_ctotal;
-        a.down_status = r.status; a.down_slot = r.range_slot;
-        sl.kind = S_CONV_S4_DOWN;
-        if (tags)
-            snprintf(sl.tag, sizeof(sl.tag), "%02zu+%02zu %s+%s %u->%u->%u %dx%d", i, i + 1, p->net.tensors[L.dst].name, p->net.tensors[R.dst].name, L.cin,
-                     L.cout, R.cout, a.Hout, a.Wout);
-        steps.erase(steps.begin() + (long)k + 1);
-    }
+    // ---- 6. the folds of conv_s4.hip, one form after the other: a 3x3 conv L and the 1x1 conv R that reads its slice last (is_conv_fold) as
+    //      ONE launch.  Two adjacent plain conv_s4 steps - not part of a pair or a share / add step, whose kinds differ -, L on
+    //      <2, 32, 8, 1> into packed pairs; R's step goes away
+    auto fold = [&](FoldForm form) {
+        const FoldDesc &f = kFolds[form];
+        const int mode = p->opt.*f.option;
+        for (size_t k = 0; mode && p->fold[form].dev && k + 1 < steps.size(); ++k) {
+            Step &sl = steps[k];
+            const Step &sr = steps[k + 1];
+            const size_t i = (size_t)sl.op;
+            if (sl.kind != S_CONV_S4 || sr.kind != S_CONV_S4 || sl.ci != (int)i || sr.op != (int)i + 1 || sr.ci != (int)i + 1) continue;
+            if (!p->conv[i].fold_off[form] || !is_conv_fold(p->net, i, form)) continue;
+            const BlobOp &L = p->net.ops[i], &R = p->net.ops[i + 1];
+            ConvArgs &a = sl.u.c;
+            const ConvArgs &r = sr.u.c;
+            const S4Shape &sh = sl.dec.s4;
+            if (sh.NT != 2 || sh.TW != 32 || sh.TH != 8 || sh.KS != 1 || !a.dst_fmt || r.res || r.no_bias || a.Hout != r.Hout || a.Wout != r.Wout) continue;
+            // tail: R without fused stages into fp32, nothing of it range-checked.  down: R with its pool fused and nothing else, into
+            // packed pairs or fp32
+            if (form == FOLD_TAIL ? (r.dst_fmt || r.status || r.pool) : (!r.pool || !r.relu)) continue;
+            if (!f.wanted((int)L.cin, (int)L.cout, (int)R.cout, a.Hout, a.Wout, Bt, mode)) continue;
+            const KOrder ko = order_tail(R.src[0], (int)L.dst_choff, (int)L.cout);
+            a.fold_w = p->fold[form].dev + p->conv[i].fold_off[form];
+            a.fold_bias = r.bias; a.fold_scale = r.acc_scale; a.fold_cout = r.Cout;
+            a.fold_src = a.dst; a.fold_c4 = a.dst_c4; a.fold_g0 = ko.r[0].choff / 4; a.fold_gn = ko.r[0].ch / 4;
+            if (form == FOLD_TAIL) {
+                a.tail_dst = r.dst; a.tail_ctotal = r.dst_ctotal; a.tail_choff = r.dst_choff;
+                sl.kind = S_CONV_S4_TAIL;
+                fmt[L.dst] = 0xFE;   // pf_hardnet_tensor_read refuses the tensor: its last slice is never stored
+            } else {   // L's slice is stored as ever
+                a.down_dst = r.dst; a.down_c4 = r.dst_c4; a.down_choff = r.dst_choff; a.down_limit = r.dst_limit;
+                a.down_fmt = r.dst_fmt; a.down_ctotal = r.dst_ctotal;
+                a.down_status = r.status; a.down_slot = r.range_slot;
+                sl.kind = S_CONV_S4_DOWN;
+            }
+            if (tags)
+                snprintf(sl.tag, sizeof(sl.tag), "%02zu+%02zu %s+%s %u->%u->%u %dx%d", i, i + 1, p->net.tensors[L.dst].name, p->net.tensors[R.dst].name, L.cin,
+                         L.cout, R.cout, a.Hout, a.Wout);
+            steps.erase(steps.begin() + (long)k + 1);
+        }
+    };
+    fold(FOLD_TAIL);
+    fold(FOLD_DOWN);
     return PF_OK;
 }
 

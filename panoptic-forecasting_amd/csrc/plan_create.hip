@@ -87,43 +87,22 @@ bool pf::is_conv_pair(const NetTable &t, size_t i) {
     return conv_pair_supports((int)C.cout, (int)P.cout);
 }
 
-// L = op i, a 3x3 stride-1 conv of two cout tiles; R = op i + 1, the only op that reads L's slice: a 1x1 conv of at most 16 couts without
-// ReLU whose single range ends with that slice.  The slice and R's range start on a 4-channel boundary, R's other channels (in front of
-// the slice) are at most 8 groups - one K = 32 chunk of the tail form - and every one of them was written by an earlier op.  (That R's
-// destination is fp32 and which kernels L and R run on is known to the schedule only: hardnet_plan.hip.)
-bool pf::is_conv_tail(const NetTable &t, size_t i) {
-    if (i + 1 >= t.ops.size()) return false;
+// L = op i, a 3x3 stride-1 conv of two cout tiles; R = op i + 1, a 1x1 stride-1 conv whose single range ends with L's slice.  The slice and
+// R's range start on a 4-channel boundary, R's other channels (in front of the slice) are at most 8 groups - one K = 32 chunk of the fold
+// forms - and every one of them was written by an earlier op.  What the form adds (kFolds): R's ReLU and cout tiles; tail: R is the only op
+// that reads the slice, which is never stored; down: op i + 2 is the 2x2 average pool of R's output, its only reader, and other ops may
+// read the slice: it is stored.  (The formats of L's and R's destinations and which kernels they run on are known to the schedule
+// only: hardnet_plan.hip.)
+bool pf::is_conv_fold(const NetTable &t, size_t i, FoldForm form) {
+    const FoldDesc &f = kFolds[form];
+    if (i + (f.pool ? 2 : 1) >= t.ops.size()) return false;
     const BlobOp &L = t.ops[i], &R = t.ops[i + 1];
-    if (L.kind != OP_CONV || R.kind != OP_CONV || L.k != 3 || L.stride != 1 || R.k != 1 || R.stride != 1 || R.relu || R.n_src != 1) return false;
-    if (L.cout <= 16 || L.cout > 32 || R.cout > 16) return false;
-    for (uint32_t j = 0; j < L.n_src; ++j)
-        if (L.src[j].choff & 1) return false;
-    const BlobSrc &rs = R.src[0];
-    const uint32_t d0 = L.dst_choff, d1 = L.dst_choff + L.cout;
-    if (rs.tensor != L.dst || (rs.choff & 3) || (d0 & 3) || rs.choff > d0 || rs.choff + rs.ch != d1 || d0 - rs.choff > 32) return false;
-    std::vector<uint8_t> written(t.tensors[L.dst].channels, 0);
-    for (size_t j = 0; j < t.ops.size(); ++j) {
-        const BlobOp &o = t.ops[j];
-        if (j < i && (o.kind == OP_CONV || o.kind == OP_STEM) && o.dst == L.dst)
-            for (uint32_t c = o.dst_choff; c < o.dst_choff + o.cout && c < written.size(); ++c) written[c] = 1;
-        for (uint32_t s = 0; s < o.n_src && j != i + 1; ++s)   // another reader of the slice
-            if (o.src[s].tensor == L.dst && o.src[s].choff < d1 && o.src[s].choff + o.src[s].ch > d0) return false;
+    if (L.kind != OP_CONV || R.kind != OP_CONV || L.k != 3 || L.stride != 1 || R.k != 1 || R.stride != 1 || (R.relu != 0) != f.r_relu || R.n_src != 1) return false;
+    if (L.cout <= 16 || L.cout > 32 || R.cout > 16u * f.r_tiles) return false;
+    if (f.pool) {
+        const BlobOp &P = t.ops[i + 2];
+        if (P.kind != OP_POOL || P.src[0].tensor != R.dst || R.dst_choff != 0 || R.cout != t.tensors[R.dst].channels) return false;
     }
-    for (uint32_t c = rs.choff; c < d0; ++c)
-        if (!written[c]) return false;
-    return true;
-}
-
-// L = op i, a 3x3 stride-1 conv of two cout tiles; R = op i + 1, a 1x1 stride-1 conv WITH ReLU of at most 64 couts whose single range ends
-// with L's slice; op i + 2 = the 2x2 average pool of R's output, its only reader.  As for the tail form the slice and R's range start on a
-// 4-channel boundary and R's other channels (in front of the slice) are at most 8 groups, every one written by an earlier op.  Unlike
-// there, other ops may read the slice: it is stored.  (Formats and kernels of L and R: the schedule, hardnet_plan.hip.)
-bool pf::is_conv_down(const NetTable &t, size_t i) {
-    if (i + 2 >= t.ops.size()) return false;
-    const BlobOp &L = t.ops[i], &R = t.ops[i + 1], &P = t.ops[i + 2];
-    if (L.kind != OP_CONV || R.kind != OP_CONV || L.k != 3 || L.stride != 1 || R.k != 1 || R.stride != 1 || !R.relu || R.n_src != 1) return false;
-    if (L.cout <= 16 || L.cout > 32 || R.cout > 16 * kDownTiles) return false;
-    if (P.kind != OP_POOL || P.src[0].tensor != R.dst || R.dst_choff != 0 || R.cout != t.tensors[R.dst].channels) return false;
     for (uint32_t j = 0; j < L.n_src; ++j)
         if (L.src[j].choff & 1) return false;
     const BlobSrc &rs = R.src[0];
@@ -134,8 +113,11 @@ bool pf::is_conv_down(const NetTable &t, size_t i) {
         const BlobOp &o = t.ops[j];
         if (j < i && (o.kind == OP_CONV || o.kind == OP_STEM) && o.dst == L.dst)
             for (uint32_t c = o.dst_choff; c < o.dst_choff + o.cout && c < written.size(); ++c) written[c] = 1;
-        for (uint32_t s = 0; s < o.n_src && j != i + 2; ++s)   // the pool is the only reader of R's output
-            if (o.src[s].tensor == R.dst) return false;
+        for (uint32_t s = 0; s < o.n_src; ++s) {
+            const BlobSrc &os = o.src[s];
+            if (!f.other_readers && j != i + 1 && os.tensor == L.dst && os.choff < d1 && os.choff + os.ch > d0) return false;   // another reader of the slice
+            if (f.pool && j != i + 2 && os.tensor == R.dst) return false;   // the pool is the only reader of R's output
+        }
     }
     for (uint32_t c = rs.choff; c < d0; ++c)
         if (!written[c]) return false;
@@ -364,17 +346,12 @@ void pack_share(const BlobOp &P, const float *wP, const BlobOp &o, const float *
     pack_conv_weights_s4(ws, (int)o.cin, (int)o.cout, 3, ko_b, 0, a.at(c.share_b_off));
 }
 
-// conv_s4.hip tail: o is the 3x3 conv, R the 1x1 conv that alone reads its slice (is_conv_tail), wr = R's weights times R's 2^k (the
-// power-of-two scale of every source channel folded in by normalize_ranges, as for R's own packings).  Into the plan's tail region
-void pack_tail(const BlobOp &o, const BlobOp &R, const float *wr, Arena &tail, ConvPlan &c) {
-    c.tail_off = tail.take(tail_packed_floats(), 16);
-    pack_conv_weights_tail(wr, (int)R.cin, (int)R.cout, order_tail(R.src[0], (int)o.dst_choff, (int)o.cout), tail.at(c.tail_off));
-}
-
-// conv_s4.hip down: the same for the 1x1 conv R behind o (is_conv_down), four cout tiles.  Into the plan's down region
-void pack_down(const BlobOp &o, const BlobOp &R, const float *wr, Arena &down, ConvPlan &c) {
-    c.down_off = down.take(down_packed_floats(), 16);
-    pack_conv_weights_down(wr, (int)R.cin, (int)R.cout, order_tail(R.src[0], (int)o.dst_choff, (int)o.cout), down.at(c.down_off));
+// conv_s4.hip folds: o is the 3x3 conv, R the 1x1 conv behind it (is_conv_fold), wr = R's weights times R's 2^k (the power-of-two scale of
+// every source channel folded in by normalize_ranges, as for R's own packings).  Into the form's region of the plan
+void pack_fold(FoldForm form, const BlobOp &o, const BlobOp &R, const float *wr, Arena region, ConvPlan &c) {
+    const int tiles = kFolds[form].r_tiles;
+    c.fold_off[form] = region.take(fold_packed_floats(tiles), 16);
+    pack_conv_weights_fold(wr, (int)R.cin, (int)R.cout, order_tail(R.src[0], (int)o.dst_choff, (int)o.cout), tiles, region.at(c.fold_off[form]));
 }
 
 void pack_front(const BlobOp &o, const float *ws, Arena &a, ConvPlan &c) {   // 3x3 stride 2, one range
@@ -414,10 +391,7 @@ void pack_stem(const BlobOp &o, const float *w, int n_cls, Arena &a, ConvPlan &c
 int build_plan_weights(pf_plan &p, const float *wts, std::vector<float> &host) {
     host.assign(64, 0.f);
     Arena a{host};
-    p.tail_host.assign(64, 0.f);
-    Arena tail{p.tail_host};
-    p.down_host.assign(64, 0.f);
-    Arena down{p.down_host};
+    for (pf_plan::FoldRegion &r : p.fold) r.host.assign(64, 0.f);
     const std::vector<BlobOp> &ops = p.net.ops;
     p.conv.assign(ops.size(), ConvPlan());
     for (size_t i = 0; i < ops.size(); ++i) {
@@ -440,8 +414,8 @@ int build_plan_weights(pf_plan &p, const float *wts, std::vector<float> &host) {
         if (i > 0 && is_conv_pair(p.net, i - 1)) pack_pair(ops[i - 1], wts + ops[i - 1].w_off, o, ws, a, c);
         if (i > 0 && p.opt.share_s && is_conv_pair(p.net, i - 1)) pack_share(ops[i - 1], wts + ops[i - 1].w_off, o, ws, a, c);
         if (o.k == 3 && o.stride == 2 && o.kind == OP_CONV && o.n_src == 1 && (o.src[0].choff & 3) == 0 && o.cout <= 32) pack_front(o, ws, a, c);
-        if (i > 0 && p.opt.fold_final && is_conv_tail(p.net, i - 1)) pack_tail(ops[i - 1], o, ws, tail, p.conv[i - 1]);   // (o = the reader)
-        if (i > 0 && p.opt.fold_down && is_conv_down(p.net, i - 1)) pack_down(ops[i - 1], o, ws, down, p.conv[i - 1]);   // (likewise)
+        for (int f = 0; f < kFoldForms && i > 0; ++f)   // (o = the reader)
+            if (p.opt.*kFolds[f].option && is_conv_fold(p.net, i - 1, (FoldForm)f)) pack_fold((FoldForm)f, ops[i - 1], o, ws, Arena{p.fold[f].host}, p.conv[i - 1]);
         if (o.stride == 1) pack_wave(o, w, src_ch, a, c);
         if (o.kind == OP_STEM) pack_stem(o, w, (int)p.net.hdr.n_cls, a, c);
         a.take(0, 64);
@@ -455,8 +429,8 @@ int build_plan_weights(pf_plan &p, const float *wts, std::vector<float> &host) {
         for (size_t ch = 0; ch < p.chan_scale[t].size(); ++ch) host[p.inv_scale_off[t] + ch] = 1.0f / p.chan_scale[t][ch];   // exact: powers of two
         a.take(0, 64);
     }
-    if (p.tail_host.size() == 64) p.tail_host.clear();   // no op has the form
-    if (p.down_host.size() == 64) p.down_host.clear();
+    for (pf_plan::FoldRegion &r : p.fold)
+        if (r.host.size() == 64) r.host.clear();   // no op has the form
     return PF_OK;
 }
 
@@ -511,10 +485,10 @@ extern "C" int pf_hardnet_plan_create(const void *blob, size_t bytes, int in_ch,
     if (e == hipSuccess) e = hipMalloc((void **)&p->dev_lut, 256);
     if (e == hipSuccess) e = hipMemcpy(p->dev_weights, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->dev_lut, lut, 256, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !p->tail_host.empty()) e = hipMalloc((void **)&p->dev_tail, p->tail_host.size() * sizeof(float));
-    if (e == hipSuccess && p->dev_tail) e = hipMemcpy(p->dev_tail, p->tail_host.data(), p->tail_host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !p->down_host.empty()) e = hipMalloc((void **)&p->dev_down, p->down_host.size() * sizeof(float));
-    if (e == hipSuccess && p->dev_down) e = hipMemcpy(p->dev_down, p->down_host.data(), p->down_host.size() * sizeof(float), hipMemcpyHostToDevice);
+    for (pf_plan::FoldRegion &r : p->fold) {
+        if (e == hipSuccess && !r.host.empty()) e = hipMalloc((void **)&r.dev, r.host.size() * sizeof(float));
+        if (e == hipSuccess && r.dev) e = hipMemcpy(r.dev, r.host.data(), r.host.size() * sizeof(float), hipMemcpyHostToDevice);
+    }
     if (e != hipSuccess) {
         pf_hardnet_plan_destroy(p);
         return fail(PF_EHIP, "plan upload: %s", hipGetErrorString(e));
@@ -523,22 +497,29 @@ extern "C" int pf_hardnet_plan_create(const void *blob, size_t bytes, int in_ch,
     return PF_OK;
 }
 
-// Host only, no device involved (tests): the weight arena a plan created now from this blob would upload (every packing of every
-// convolution under the process-wide options), and per op of the table six numbers: offset (floats) and rounds of its packed-pair
-// packing, offset and cout tiles of the share launch's, offset and rounds of the add launch's (0 = the op has none)
-extern "C" int pf_debug_plan_arena(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
-                                   long long *table, int table_ops) {
-    if (!blob || !n_floats) return fail(PF_EINVAL, "pf_debug_plan_arena: null argument");
-    pf_plan p;
+// Host only, no device involved (tests): the plan this blob would give now under the process-wide options, as far as
+// build_plan_weights takes it (`host` = its weight arena)
+static int debug_plan(const char *who, const void *blob, size_t bytes, int in_ch, int n_cls, const size_t *n_floats, pf_plan &p, std::vector<float> &host) {
+    if (!blob || !n_floats) return fail(PF_EINVAL, "%s: null argument", who);
     p.opt = g_plan_opt;
     int rc = parse_net_table(blob, bytes, in_ch, n_cls, p.net);
     const size_t n_w = rc ? 0 : (bytes - p.net.hdr.weights_off) / sizeof(float);
     if (!rc) rc = check_plan_ops(p.net, n_w);
     if (rc) return rc;
     const float *w0 = reinterpret_cast<const float *>((const char *)blob + p.net.hdr.weights_off);
-    std::vector<float> wnorm(w0, w0 + n_w), host;
+    std::vector<float> wnorm(w0, w0 + n_w);
     normalize_ranges(&p, wnorm);
-    if ((rc = build_plan_weights(p, wnorm.data(), host))) return rc;
+    return build_plan_weights(p, wnorm.data(), host);
+}
+
+// the weight arena that plan would upload (every packing of every convolution), and per op of the table six numbers: offset (floats)
+// and rounds of its packed-pair packing, offset and cout tiles of the share launch's, offset and rounds of the add launch's (0 = the op
+// has none)
+extern "C" int pf_debug_plan_arena(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                                   long long *table, int table_ops) {
+    pf_plan p;
+    std::vector<float> host;
+    if (int rc = debug_plan("pf_debug_plan_arena", blob, bytes, in_ch, n_cls, n_floats, p, host)) return rc;
     *n_floats = host.size();
     if (out && cap >= host.size()) memcpy(out, host.data(), host.size() * sizeof(float));
     for (int i = 0; table && i < table_ops && i < (int)p.conv.size(); ++i) {
@@ -549,41 +530,33 @@ extern "C" int pf_debug_plan_arena(const void *blob, size_t bytes, int in_ch, in
     return PF_OK;
 }
 
-// Host only, as pf_debug_plan_arena: the tail ("fold_final") or down ("fold_down") region of that plan (its first 64 floats are zeros) and
-// per op of the table its offset into it (0 = the op has no such packing)
-static int debug_plan_region(const char *who, bool down, const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
-                             long long *table, int table_ops) {
-    if (!blob || !n_floats) return fail(PF_EINVAL, "%s: null argument", who);
+// a fold form's region of that plan - tail: option "fold_final", down: "fold_down" - (its first 64 floats are zeros) and per op of the
+// table its offset into it (0 = the op has no such packing)
+static int debug_plan_fold(const char *who, FoldForm form, const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                           long long *table, int table_ops) {
     pf_plan p;
-    p.opt = g_plan_opt;
-    int rc = parse_net_table(blob, bytes, in_ch, n_cls, p.net);
-    const size_t n_w = rc ? 0 : (bytes - p.net.hdr.weights_off) / sizeof(float);
-    if (!rc) rc = check_plan_ops(p.net, n_w);
-    if (rc) return rc;
-    const float *w0 = reinterpret_cast<const float *>((const char *)blob + p.net.hdr.weights_off);
-    std::vector<float> wnorm(w0, w0 + n_w), host;
-    normalize_ranges(&p, wnorm);
-    if ((rc = build_plan_weights(p, wnorm.data(), host))) return rc;
-    const std::vector<float> &region = down ? p.down_host : p.tail_host;
+    std::vector<float> host;
+    if (int rc = debug_plan(who, blob, bytes, in_ch, n_cls, n_floats, p, host)) return rc;
+    const std::vector<float> &region = p.fold[form].host;
     *n_floats = region.size();
     if (out && cap >= region.size() && !region.empty()) memcpy(out, region.data(), region.size() * sizeof(float));
-    for (int i = 0; table && i < table_ops && i < (int)p.conv.size(); ++i) table[i] = (long long)(down ? p.conv[i].down_off : p.conv[i].tail_off);
+    for (int i = 0; table && i < table_ops && i < (int)p.conv.size(); ++i) table[i] = (long long)p.conv[i].fold_off[form];
     return PF_OK;
 }
 extern "C" int pf_debug_plan_tail(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
                                   long long *table, int table_ops) {
-    return debug_plan_region("pf_debug_plan_tail", false, blob, bytes, in_ch, n_cls, out, cap, n_floats, table, table_ops);
+    return debug_plan_fold("pf_debug_plan_tail", FOLD_TAIL, blob, bytes, in_ch, n_cls, out, cap, n_floats, table, table_ops);
 }
 extern "C" int pf_debug_plan_down(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
                                   long long *table, int table_ops) {
-    return debug_plan_region("pf_debug_plan_down", true, blob, bytes, in_ch, n_cls, out, cap, n_floats, table, table_ops);
+    return debug_plan_fold("pf_debug_plan_down", FOLD_DOWN, blob, bytes, in_ch, n_cls, out, cap, n_floats, table, table_ops);
 }
 
 extern "C" void pf_hardnet_plan_destroy(pf_plan *p) {
     if (!p) return;
     if (p->dev_weights) (void)hipFree(p->dev_weights);
     if (p->dev_lut) (void)hipFree(p->dev_lut);
-    if (p->dev_tail) (void)hipFree(p->dev_tail);
-    if (p->dev_down) (void)hipFree(p->dev_down);
+    for (pf_plan::FoldRegion &r : p->fold)
+        if (r.dev) (void)hipFree(r.dev);
     delete p;
 }

@@ -13,7 +13,7 @@ from conftest import GOLDEN
 from panoptic_forecasting_amd import hardnet_arch as arch
 from panoptic_forecasting_amd import lib as pflib
 from panoptic_forecasting_amd import packing, synth
-from test_fold_final_host import k_channel, plan_tail
+from test_fold_final_host import hard_block, k_channel, plan_tail, random_params
 from test_share_s_host import option, plan_arena  # noqa: F401  (the fixture and the arena reader of the share / add tests)
 
 TILES = 4                       # cout tiles of the reader the form packs, whatever the reader has
@@ -34,32 +34,35 @@ def plan_down(blob, in_ch, n_cls, n_ops):
 
 
 def down_net(g, c_odd, c_even, r_cout, lead=0, c0=24, r_relu=True, pool=True, skip=False, cin0=12):
-    """the block of test_fold_final_host.tail_net with slots [L1, L3, L4]; behind it `dn` = a 1x1 conv with ReLU over the block's output,
-    `pl` = its 2x2 average pool, `nx` = a 3x3 conv over the pooled tensor and, with `skip`, `sk` = a second reader of the block's output"""
+    """test_fold_final_host.hard_block over the input; behind it `dn` = a 1x1 conv with ReLU over the block's output, `pl` = its 2x2 average
+    pool, `nx` = a 3x3 conv over the pooled tensor and, with `skip`, `sk` = a second reader of the block's output"""
     from helpers import MiniSpec
     S = arch.Src
-    spec = MiniSpec(cin0)
-    t0 = spec.conv('t0', [S(0, 0, cin0)], c0, 3)
-    out_ch = lead + 2 * c_odd + c_even
-    out = spec.tensor('out', out_ch)
-    shapes = [('t0', cin0, c0, 3)]
-    if lead:
-        spec.conv('L0', [S(t0, 0, c0)], lead, 3, dst=out, dst_choff=0)
-        shapes += [('L0', c0, lead, 3)]
-    spec.conv('L1', [S(t0, 0, c0)], c_odd, 3, dst=out, dst_choff=lead)
-    l2 = spec.conv('L2', [S(out, lead, c_odd), S(t0, 0, c0)], c_even, 3)
-    spec.conv('L3', [S(l2, 0, c_even)], c_odd, 3, dst=out, dst_choff=lead + c_odd)
-    spec.conv('L4', [S(out, lead + c_odd, c_odd), S(l2, 0, c_even), S(t0, 0, c0)], c_even, 3, dst=out, dst_choff=lead + 2 * c_odd)
+    spec, shapes = MiniSpec(cin0), []
+    out, out_ch = hard_block(spec, shapes, S(0, 0, cin0), c_odd, c_even, lead, c0)
     dn = spec.conv('dn', [S(out, 0, out_ch)], r_cout, 1, relu=r_relu)
     pl = spec.pool('pl', dn) if pool else dn
     spec.conv('nx', [S(pl, 0, r_cout)], 8, 3)
-    shapes += [('L1', c0, c_odd, 3), ('L2', c_odd + c0, c_even, 3), ('L3', c_even, c_odd, 3), ('L4', c_odd + c_even + c0, c_even, 3),
-               ('dn', out_ch, r_cout, 1), ('nx', r_cout, 8, 3)]
+    shapes += [('dn', out_ch, r_cout, 1), ('nx', r_cout, 8, 3)]
     if skip:
         spec.conv('sk', [S(out, 0, out_ch)], 6, 1, relu=False)
         shapes += [('sk', out_ch, 6, 1)]
-    P = {n: (torch.randn(co, ci, k, k, generator=g) / (ci * k * k) ** 0.5, torch.randn(co, generator=g) * 0.5) for n, ci, co, k in shapes}
-    return spec, P
+    return spec, random_params(g, shapes)
+
+
+def both_net(g):
+    """both fold forms in one table: FC-HarDNet-70's first block (10, 28) with its transition `dn` (64 couts) + `pl`, and behind the pool,
+    in place of `nx`, its last block (10, 28) - names prefixed 'u.' - with `fin` (11 couts, no ReLU) over that block's output"""
+    from helpers import MiniSpec
+    S = arch.Src
+    spec, shapes = MiniSpec(12), []
+    out, out_ch = hard_block(spec, shapes, S(0, 0, 12), 10, 28)
+    pl = spec.pool('pl', spec.conv('dn', [S(out, 0, out_ch)], 64, 1))
+    shapes += [('dn', out_ch, 64, 1)]
+    up, up_ch = hard_block(spec, shapes, S(pl, 0, 64), 10, 28, pre='u.')
+    spec.conv('fin', [S(up, 0, up_ch)], 11, 1, relu=False)
+    shapes += [('fin', up_ch, 11, 1)]
+    return spec, random_params(g, shapes)
 
 
 def own_packing(blob, spec, name, cout):
@@ -200,3 +203,17 @@ def test_fchardnet70_matches_the_first_block_and_its_transition_only(option):
     assert spec.ops[i].name == 'base.4.layers.3' and spec.ops[i + 1].name == 'base.5' and spec.ops[i + 2].kind == arch.OP_POOL
     assert (spec.ops[i].cin, spec.ops[i].cout, spec.ops[i + 1].cin, spec.ops[i + 1].cout) == (76, 28, 48, 64)
     assert region.size == 64 + FRAG
+
+
+def test_both_forms_in_one_table(option):
+    """a down block whose pooled transition feeds a tail block: each form's region holds one packing, on that block's last 3x3 layer"""
+    option('fold_final', 2, 1)
+    option('fold_down', 2, 1)
+    spec, P = both_net(torch.Generator().manual_seed(1))
+    blob = packing.pack_blob(None, spec.in_ch, spec.n_cls, spec=spec, params=P)
+    names = [op.name for op in spec.ops]
+    tail, ttab = plan_tail(blob, spec.in_ch, spec.n_cls, len(spec.ops))
+    down, dtab = plan_down(blob, spec.in_ch, spec.n_cls, len(spec.ops))
+    assert [names[i] for i in np.nonzero(ttab)[0]] == ['u.L4'] and names[names.index('u.L4') + 1] == 'fin'
+    assert [names[i] for i in np.nonzero(dtab)[0]] == ['L4'] and names[names.index('L4') + 1:names.index('L4') + 3] == ['dn', 'pl']
+    assert tail.size == 64 + 2 * 2 * 64 * 4 and down.size == 64 + FRAG

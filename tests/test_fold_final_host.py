@@ -40,30 +40,42 @@ def k_channel(chunk, g, e, front, cout):
     return front + c if c < cout else None
 
 
+def hard_block(spec, shapes, src, c_odd, c_even, lead=0, c0=24, pre=''):
+    """`t0` = a 3x3 conv of the range `src`, then the block of test_gpu_share_s.pair_net over it with slots [L0,] L1, L3, L4 in the tensor
+    `out` (names prefixed with `pre`); appends (name, cin, cout, k) of its convs to `shapes`; returns (out, its channels)"""
+    S = arch.Src
+    t0 = spec.conv(pre + 't0', [src], c0, 3)
+    out_ch = lead + 2 * c_odd + c_even
+    out = spec.tensor(pre + 'out', out_ch)
+    shapes += [(pre + 't0', src.ch, c0, 3)]
+    if lead:
+        spec.conv(pre + 'L0', [S(t0, 0, c0)], lead, 3, dst=out, dst_choff=0)
+        shapes += [(pre + 'L0', c0, lead, 3)]
+    spec.conv(pre + 'L1', [S(t0, 0, c0)], c_odd, 3, dst=out, dst_choff=lead)
+    l2 = spec.conv(pre + 'L2', [S(out, lead, c_odd), S(t0, 0, c0)], c_even, 3)
+    spec.conv(pre + 'L3', [S(l2, 0, c_even)], c_odd, 3, dst=out, dst_choff=lead + c_odd)
+    spec.conv(pre + 'L4', [S(out, lead + c_odd, c_odd), S(l2, 0, c_even), S(t0, 0, c0)], c_even, 3, dst=out, dst_choff=lead + 2 * c_odd)
+    shapes += [(pre + 'L1', c0, c_odd, 3), (pre + 'L2', c_odd + c0, c_even, 3), (pre + 'L3', c_even, c_odd, 3),
+               (pre + 'L4', c_odd + c_even + c0, c_even, 3)]
+    return out, out_ch
+
+
+def random_params(g, shapes):
+    return {n: (torch.randn(co, ci, k, k, generator=g) / (ci * k * k) ** 0.5, torch.randn(co, generator=g) * 0.5) for n, ci, co, k in shapes}
+
+
 def tail_net(g, c_odd, c_even, fin_cout, lead=0, c0=24, fin_relu=False, second_reader=False, cin0=12):
-    """the block of test_gpu_share_s.pair_net with slots [L1, L3, L4] and `fin` = a 1x1 conv over the block's output"""
+    """hard_block over the input and `fin` = a 1x1 conv over the block's output"""
     from helpers import MiniSpec
     S = arch.Src
-    spec = MiniSpec(cin0)
-    t0 = spec.conv('t0', [S(0, 0, cin0)], c0, 3)
-    out_ch = lead + 2 * c_odd + c_even
-    out = spec.tensor('out', out_ch)
-    shapes = [('t0', cin0, c0, 3)]
-    if lead:
-        spec.conv('L0', [S(t0, 0, c0)], lead, 3, dst=out, dst_choff=0)
-        shapes += [('L0', c0, lead, 3)]
-    spec.conv('L1', [S(t0, 0, c0)], c_odd, 3, dst=out, dst_choff=lead)
-    l2 = spec.conv('L2', [S(out, lead, c_odd), S(t0, 0, c0)], c_even, 3)
-    spec.conv('L3', [S(l2, 0, c_even)], c_odd, 3, dst=out, dst_choff=lead + c_odd)
-    spec.conv('L4', [S(out, lead + c_odd, c_odd), S(l2, 0, c_even), S(t0, 0, c0)], c_even, 3, dst=out, dst_choff=lead + 2 * c_odd)
+    spec, shapes = MiniSpec(cin0), []
+    out, out_ch = hard_block(spec, shapes, S(0, 0, cin0), c_odd, c_even, lead, c0)
     spec.conv('fin', [S(out, 0, out_ch)], fin_cout, 1, relu=fin_relu)
-    shapes += [('L1', c0, c_odd, 3), ('L2', c_odd + c0, c_even, 3), ('L3', c_even, c_odd, 3), ('L4', c_odd + c_even + c0, c_even, 3),
-               ('fin', out_ch, fin_cout, 1)]
+    shapes += [('fin', out_ch, fin_cout, 1)]
     if second_reader:
         spec.conv('side', [S(out, 0, out_ch)], 6, 1, relu=False)
         shapes += [('side', out_ch, 6, 1)]
-    P = {n: (torch.randn(co, ci, k, k, generator=g) / (ci * k * k) ** 0.5, torch.randn(co, generator=g) * 0.5) for n, ci, co, k in shapes}
-    return spec, P
+    return spec, random_params(g, shapes)
 
 
 @pytest.mark.parametrize('c_odd,c_even,fin_cout', [(10, 28, 11), (10, 18, 5), (12, 32, 16), (16, 20, 1)])

@@ -12,8 +12,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from test_fold_down_host import down_net
-from test_gpu_fold_final import force_conv, raw_ranges, run_labels, slot_planes  # noqa: F401
+from test_fold_down_host import both_net, down_net
+from test_gpu_fold_final import TAIL, assert_fold_close, force_conv, raw_ranges, run_labels, slot_planes, tail_ref  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -82,21 +82,7 @@ def check_down(c_odd, c_even, r_cout, h, w, b, folded, options=(), **kw):
     else:
         assert labels[0] == labels[2]
     assert planes[0].any() and torch.equal(planes[0], planes[2])      # L4's slice (and L1's, L3's): the same bits
-    for name, r in ref.items():
-        r = r.float()
-        m = r.abs().max().item()
-        e0 = (got[0][name] - r).abs().max().item()
-        e2 = (got[2][name] - r).abs().max().item()
-        d = (got[0][name] - got[2][name]).abs().max().item()
-        print('%s: max|ref| %.3g  err two launches %.3g  err fold %.3g (bar %.3g)  between them %.3g (bar %.3g)' %
-              (name, m, e0, e2, 2e-5 * (1 + m), d, 1e-5 * (1 + m)))
-    for name, r in ref.items():
-        r = r.float()
-        m = r.abs().max().item()
-        assert got[2][name].shape == r.shape
-        assert (got[0][name] - r).abs().max().item() <= 2e-5 * (1.0 + m), name
-        assert (got[2][name] - r).abs().max().item() <= 2e-5 * (1.0 + m), name
-        assert (got[0][name] - got[2][name]).abs().max().item() <= 1e-5 * (1.0 + m), name
+    assert_fold_close(ref, got[0], got[2])
     return labels[2]
 
 
@@ -110,6 +96,32 @@ def check_down(c_odd, c_even, r_cout, h, w, b, folded, options=(), **kw):
 def test_fold_vs_float64_and_two_launches(c_odd, c_even, r_cout, h, w, b, force_conv, packs_down):
     force_conv(5, 2, 0, 0)
     check_down(c_odd, c_even, r_cout, h, w, b, True)
+
+
+def test_both_forms_in_one_plan(force_conv, packs_down):
+    """a down block (10, 28, 64) and, behind its pool at 8 x 20, a tail block (10, 28, 11): the schedule's fold pass runs once per form over
+    the same step list.  One launch of each form, neither 1x1 conv on its own; the bars of check_down / check_tail against float64 and
+    against the same net with both options 0"""
+    force_conv(5, 2, 0, 0)
+    g = torch.Generator().manual_seed(21)
+    x = torch.randn(1, 12, 16, 40, generator=g) * torch.exp(0.5 * torch.randn(1, 12, 1, 1, generator=g))
+    spec, P = both_net(g)
+    ref = down_ref(x, P)
+    up = tail_ref(ref['pl'], dict({k[2:]: v for k, v in P.items() if k.startswith('u.')}, fin=P['fin']))
+    ref.update({'u.L2': up['L2'], 'u.out': up['out'], 'fin': up['fin']})
+    got, labels = {}, {}
+    for mode in (0, 2):
+        net = make_net(spec, P, mode, (('fold_final', mode),))
+        labels[mode] = run_labels(net, x)
+        assert net.status() == 0
+        got[mode] = {k: net.tensor(k).cpu() for k in ref if not (mode == 2 and k == 'u.out')}   # (its last slice is elided)
+        net.close()
+    assert sum(DOWN in l for l in labels[2]) == 1 and sum('conv_s4_down_kernel' in l for l in labels[2]) == 1, labels[2]
+    assert sum(TAIL in l for l in labels[2]) == 1 and sum('conv_s4_tail_kernel' in l for l in labels[2]) == 1, labels[2]
+    assert not any('conv_s4_1x1_kernel' in l for l in labels[2]), labels[2]        # dn (+pool) and fin run in no launch of their own ...
+    assert sum('conv_s4_1x1_kernel' in l for l in labels[0]) == 2 and not any('tail' in l or 'down' in l for l in labels[0]), labels[0]
+    assert len(labels[0]) == len(labels[2]) + 2                                      # ... as they do with the folds off
+    assert_fold_close(ref, got[0], got[2])
 
 
 def test_second_reader_of_the_block_output_reads_what_the_fold_stored(force_conv, packs_down):

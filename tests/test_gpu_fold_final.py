@@ -80,6 +80,28 @@ def slot_planes(net, name, groups):
     return raw[:, :, :groups].cpu(), raw[:, :, groups:].cpu()
 
 
+def assert_fold_close(ref, two, fold):
+    """every tensor of the float64 reference: the two launches and the fold within 2e-5 (1 + max |ref|) of it, within 1e-5 (1 + max |ref|)
+    of each other; a tensor the fold run could not tap (elided) is missing from `fold`.  Prints the figures first"""
+    for name, r in ref.items():
+        r = r.float()
+        m = r.abs().max().item()
+        e0 = (two[name] - r).abs().max().item()
+        e2 = (fold[name] - r).abs().max().item() if name in fold else float('nan')
+        d = (two[name] - fold[name]).abs().max().item() if name in fold else float('nan')
+        print('%s: max|ref| %.3g  err two launches %.3g  err fold %.3g (bar %.3g)  between them %.3g (bar %.3g)' %
+              (name, m, e0, e2, 2e-5 * (1 + m), d, 1e-5 * (1 + m)))
+    for name, r in ref.items():
+        r = r.float()
+        m = r.abs().max().item()
+        assert two[name].shape == r.shape
+        assert (two[name] - r).abs().max().item() <= 2e-5 * (1.0 + m), name
+        if name in fold:
+            assert fold[name].shape == r.shape
+            assert (fold[name] - r).abs().max().item() <= 2e-5 * (1.0 + m), name
+            assert (two[name] - fold[name]).abs().max().item() <= 1e-5 * (1.0 + m), name
+
+
 def check_tail(c_odd, c_even, fin_cout, h, w, b, folded, options=(), **kw):
     """fold_final = 2 against float64 and against fold_final = 0; `folded`: the tail launch must have run (else the two plain ones).
     Returns the labels of the fold_final = 2 run"""
@@ -114,21 +136,7 @@ def check_tail(c_odd, c_even, fin_cout, h, w, b, folded, options=(), **kw):
     else:
         assert any('conv_s4_1x1_kernel' in l for l in labels[2]) == (w % 4 == 0), labels[2]
         assert labels[0] == labels[2]
-    for name, r in ref.items():
-        r = r.float()
-        m = r.abs().max().item()
-        e0 = (got[0][name] - r).abs().max().item()
-        e2 = (got[2][name] - r).abs().max().item() if name in got[2] else float('nan')
-        d = (got[0][name] - got[2][name]).abs().max().item() if name in got[2] else float('nan')
-        print('%s: max|ref| %.3g  err two launches %.3g  err fold %.3g (bar %.3g)  between them %.3g (bar %.3g)' %
-              (name, m, e0, e2, 2e-5 * (1 + m), d, 1e-5 * (1 + m)))
-    for name, r in ref.items():
-        r = r.float()
-        m = r.abs().max().item()
-        assert (got[0][name] - r).abs().max().item() <= 2e-5 * (1.0 + m), name
-        if name in got[2]:
-            assert (got[2][name] - r).abs().max().item() <= 2e-5 * (1.0 + m), name
-            assert (got[0][name] - got[2][name]).abs().max().item() <= 1e-5 * (1.0 + m), name
+    assert_fold_close(ref, got[0], got[2])
     return labels[2]
 
 

@@ -322,7 +322,29 @@ int pf_seg_loss(const float *logits, int B, int C, int Hin, int Win, const void 
  * inputs); its pieces: ConvLSTMCell (convlstm.py:44-70), nn.GRU, MaskRCNNConvUpsampleHead.forward
  * (mask_rcnn_conv_upsample_head.py:60-65), _compute_traj_inst_feats (:206-214), _normalize_traj (:179-188) and
  * expand_traj_mask (model_utils.py:11-27).  csrc/fg_net.hip.
- *   flags      must be 0 (other values: PF_EUNSUPPORTED; reserved for the configuration switches)
+ *   flags      0 or PF_FG_PAIR (any other bit: PF_EUNSUPPORTED; reserved for the configuration switches).  The same value goes to
+ *              pf_fg_weights_size, pf_fg_pack and pf_fg_forward of one model.
+ *   PF_FG_PAIR the eight 3x3 GEMMs (the four ConvLSTM cells, mask_fcn1..4) run on v_mfma_f32_16x16x32_f16: every fp32 operand is
+ *              fed as two round-to-nearest fp16 terms, hi = fp16(x), mid = fp16(x - hi), three products hi*hi + hi*mid + mid*hi,
+ *              fp32 accumulation (the arithmetic of the bg network's option "split_f16").  Everything in memory stays fp32 and
+ *              every other kernel keeps its fp32 code; flags = 0 is untouched.  Unflagged operand bound:
+ *              |x - hi - mid| <= 2^-23 |x| + 2^-25; the dropped product is <= 2^-22 of a product.
+ *              - packed buffer: the flags = 0 layout followed by a pair section (the fp16 terms of w * 2^k per GEMM, max |w * 2^k|
+ *                in [2^14, 2^15), k found on the device; 2^-k is applied in the bias addition, both exact).  A buffer packed with
+ *                PF_FG_PAIR is therefore also valid for a flags = 0 forward.  The reverse - a flags = 0 buffer handed to a
+ *                PF_FG_PAIR forward - reads past its end: it is the CALLER'S CONTRACT never to do that, nothing checks it.
+ *              - workspace: pf_fg_pair_workspace, NOT pf_fg_workspace - that call keeps refusing every non-zero flags value, as
+ *                its callers and tests/test_fg_host.py have always had it, so the pair workspace has a size call of its own:
+ *                PF_FG_STATUS_BYTES of status block in front of the flags = 0 workspace.  Word 0: PF_STATUS_* bits of the
+ *                running forward, zeroed by the forward's first launch (a kernel node; no launch is added beyond that one).  Word
+ *                1: OR over the forwards since the host cleared it.  The caller clears the block once after allocating the workspace
+ *                (pf_fg_status_reset).  PF_STATUS_RANGE: a staged operand was not <= 65504 in magnitude (NaN included).
+ *                PF_STATUS_RANGE_LOW: a K source (traj_feat vector, input planes, h) of one launch had a non-zero maximum
+ *                below 2^-6, where the absolute 2^-25 dominates.  All-zero tensors raise nothing; nothing is ever clamped.  A
+ *                flagged forward's outputs are not to be used: run it again with flags = 0, or fail.
+ *              - pf_fg_status(ws, out2, stream): out2 (host) = {word 0, word 1} with the last forward's RANGE_LOW folded in, both
+ *                words cleared; one small kernel, a copy and a SYNCHRONISATION of `stream` - the only fg call that waits, never
+ *                made by pf_fg_forward, which stays enqueue-only and capturable.  After replays of a captured forward read word 1.
  *   pf_fg_weights_size: raw = the 52 state_dict tensors of the reference, flattened and concatenated in its state_dict
  *              order (fp32); packed = the device buffer pf_fg_pack fills (raw copy + ConvLSTM / mask head weights re-tiled,
  *              the i, f, o, g rows of 16 hidden channels side by side).  Both in floats.
@@ -335,14 +357,19 @@ int pf_seg_loss(const float *logits, int B, int C, int Hin, int Win, const void 
  *      masks [N,28,28] (the logits of each instance's class row only, :335-336)
  *   N = 0 enqueues nothing.  Dimensions are checked before any device work.  Workspace: pf_fg_workspace.
  */
+#define PF_FG_PAIR 1
+#define PF_FG_STATUS_BYTES 1024
 int pf_fg_weights_size(int flags, size_t *raw_floats, size_t *packed_floats);
 int pf_fg_pack(const float *raw, float *packed, int flags, void *stream);
 int pf_fg_workspace(int N, int T_in, int T_out, int flags, size_t *bytes);
+int pf_fg_pair_workspace(int N, int T_in, int T_out, size_t *bytes);
 int pf_fg_forward(const float *packed, int flags, int N, int T_in, int T_out, int odom_T, const float *trajs,
                   const float *traj_mask, const float *vel_mask, const float *feats, const int64_t *output_inds,
                   const float *odom, const float *depths, const float *depth_mask, const int64_t *classes,
                   float *traj_norm, float *traj_unnorm, float *mask_feats, float *output_feats, float *masks,
                   void *ws, size_t ws_bytes, void *stream);
+int pf_fg_status(void *ws, unsigned *out2, void *stream);
+int pf_fg_status_reset(void *ws, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * odometry forecaster network - replaces OdomModel.forward (models/odom/odom_model.py:79-106) of the shipped odom config

@@ -18,6 +18,11 @@
 //     EPI_DECONV  ConvTranspose2d 2x2/s2 as a 1x1 GEMM 256 -> 1024 = (cout, dy, dx), stored as a pixel shuffle, + ReLU
 // The trajectory path (GRU, normalisation, output MLPs) and the instance feature model are small VALU kernels.
 // Every launch is a kernel node (no memset, no memcpy): a pf_fg_forward call can be captured into a graph.
+//
+// PF_FG_PAIR (pfhip.h) runs the 3x3 instantiations - the four ConvLSTM cells and mask_fcn1..4 - through pair_kernel instead: the same
+// tiling and epilogues on v_mfma_f32_16x16x32_f16, every fp32 operand fed as two round-to-nearest fp16 terms (conv_mfma.h: split_terms2)
+// with three products and fp32 accumulation.  Storage is unchanged (fp32 everywhere in memory); the split happens while staging.
+#include "conv_mfma.h"
 #include "pf_common.h"
 #include "pf_prof.h"
 
@@ -104,6 +109,80 @@ __global__ __launch_bounds__(256) void pack_kernel(const float *__restrict__ w, 
             v = w[(long long)row * K + k];
         }
         out[i] = v;
+    }
+}
+
+// PF_FG_PAIR: behind the flags = 0 layout (kept whole: the 1x1 GEMMs and the deconvolution read it) a pair section,
+//   [0 .. 7]  max |w| of the eight 3x3 GEMMs (bit patterns)   [8 .. 15]  their 2^-k   (64 floats)
+//   then per 3x3 GEMM [tile][round of 16 channels][term hi, mid][tap][64 columns][16 channels] fp16 of w * 2^k, zero past ctot
+// k = the rule of split_weight_scale (conv_mfma.h): max |w * 2^k| in [2^14, 2^15), k = 0 for an all-zero (or non-finite) tensor; the
+// weights live on the device, so the maximum is a reduction kernel and k is derived from it by every packing thread.  |k| <= 120 keeps
+// 2^k and 2^-k normal numbers (a tensor whose maximum is below 2^-106 is then scaled less than the rule says; both scalings stay exact)
+constexpr int PKC = 16;                            // channels per round of pair_kernel
+constexpr int PTERM_X = 256 * PKC;                 // fp16 per term of its activation planes in LDS
+constexpr int PTERM_W = 9 * 64 * PKC;              // fp16 per term of a round's weights
+constexpr int PROUND = 2 * PTERM_W;                // fp16 per (tile, round) of the packed pair weights
+constexpr int NPAIR = 8;
+static const int kPairGemm[NPAIR] = {G_ME0, G_ME1, G_MD0, G_MD1, G_F1, G_F2, G_F3, G_F4};
+struct PairLayout {
+    size_t head, gemm[NPAIR], total;    // floats from the start of the packed buffer
+};
+static size_t pair_rounds(int ctot) { return (size_t)(ctot + PKC - 1) / PKC; }
+static PairLayout pair_layout(const Layout &L) {
+    PairLayout P;
+    size_t o = align_up(L.total, 64);
+    P.head = o;
+    o += 64;
+    for (int i = 0; i < NPAIR; ++i) {
+        const GemmDesc &d = kGemm[kPairGemm[i]];
+        P.gemm[i] = o;
+        o += (size_t)d.tiles * pair_rounds(d.ctot) * PROUND / 2;
+    }
+    P.total = o;
+    return P;
+}
+
+__global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ w, long long n, unsigned *__restrict__ out) {
+    __shared__ unsigned m;
+    if (threadIdx.x == 0) m = 0u;
+    __syncthreads();
+    float v = 0.f;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) v = fmaxf(v, fabsf(w[i]));
+    atomicMax(&m, __builtin_bit_cast(unsigned, v));
+    __syncthreads();
+    if (threadIdx.x == 0 && m != 0u) atomicMax(out, m);
+}
+
+__device__ __forceinline__ int pair_exponent(unsigned maxbits) {
+    const float m = __builtin_bit_cast(float, maxbits);
+    if (!(m > 0.f) || !(m <= 3.4028234e38f)) return 0;
+    const int k = 14 - ilogbf(m);
+    return k < -120 ? -120 : (k > 120 ? 120 : k);
+}
+
+__global__ __launch_bounds__(256) void pack_pair_kernel(const float *__restrict__ w, _Float16 *__restrict__ out, int ctot, int tiles, int map,
+                                                        const unsigned *__restrict__ maxbits, float *__restrict__ scale) {
+    const int k = pair_exponent(*maxbits);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *scale = ldexpf(1.f, -k);
+    const int rounds = (ctot + PKC - 1) / PKC, K = ctot * 9;
+    const long long total = (long long)tiles * rounds * PTERM_W;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int ch = (int)(i % PKC), q = (int)(i / PKC % 64);
+        const long long t = i / (64 * PKC);
+        const int tap = (int)(t % 9);
+        const long long tr = t / 9;
+        const int round = (int)(tr % rounds), tile = (int)(tr / rounds);
+        const int c = round * PKC + ch;
+        float v = 0.f;
+        if (c < ctot) {
+            const int row = map == MAP_LSTM ? (q >> 4) * C + tile * 16 + (q & 15) : tile * 64 + q;
+            v = ldexpf(w[(long long)row * K + c * 9 + tap], k);
+        }
+        const _Float16 hi = (_Float16)v;
+        const _Float16 mid = (_Float16)(v - (float)hi);
+        const long long at = tr * PROUND + (tap * 64 + q) * PKC + ch;
+        out[at] = hi;
+        out[at + PTERM_W] = mid;
     }
 }
 
@@ -272,6 +351,229 @@ __global__ __launch_bounds__(256, TAPS == 9 ? 4 : 1) void gemm_kernel(GemmArgs a
                 }
             }
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------- fp16-pair core (PF_FG_PAIR)
+// The TAPS == 9 GEMM on v_mfma_f32_16x16x32_f16 - the only matrix shape these accumulators ever see.  Same workgroup tile as gemm_kernel
+// (one instance's 13 M-tiles x 64 columns, M-tile wave + 4m), same three K sources read in place, same epilogues.  Per round of PKC = 16
+// channels:
+//   xs [term][16x16 halo pixel][16 ch] fp16   hi = fp16(x), mid = fp16(x - hi), split while staging; the halo is zeroed once
+//   ws [term][tap][64 col][16 ch] fp16        a straight copy of the round's slice of the packed pair weights (w * 2^k)
+// K order inside a round: tap-major, the 16 channels contiguous under each tap, so the 8 K-values of a lane are one 16-byte LDS read.  A
+// matrix step covers two taps: lane group q = lane >> 4 holds channels 8 (q & 1) .. + 7 of tap 2 mf + (q >> 1).  Nine taps make 4.5
+// steps: in the fifth, groups 2 and 3 multiply a zero A fragment (halo pixel 0) by tap 8's weights again.
+// Consecutive pixels / columns are 32 B apart per term, so the 16 lanes of a ds_read_b128 group (MI355X: 8 rows of one channel octet and
+// 8 of the other) cover the 16 slots of a bank row; only an M-tile's row ends (pixel index + 2) cost a 2-way conflict.
+// Products hi*mid + mid*hi + hi*hi into a per-round partial, partials added to acc once per round (the blocked sum of gemm_kernel).
+// Range guard (conv_mfma.h): the workgroups of column tile 0 - every tile stages the same planes - keep max |v| per K source and whether
+// any value is not <= 65504; one atomic per source and workgroup into the launch's three slots of the status block.
+constexpr int FG_STATUS_WORDS = 256;               // status block at the head of a PF_FG_PAIR workspace
+constexpr int FG_SLOT0 = 8;                        // its words 8 ..: max |v| bit patterns, three (vec, x, h) per pair launch
+
+struct PairArgs {
+    GemmArgs g;                 // g.w unused
+    const split_t *wp;          // [tile][round][term][tap][64][16] fp16 terms of w * 2^k, zero past ctot
+    const float *scale;         // 2^-k (device: k is found on the device at pack time)
+    unsigned *status;           // word 0 of the status block
+    unsigned *slots;            // this launch's three slots
+};
+
+// gemm_kernel's epilogue (EPI_LSTM, EPI_RELU; same D layout: the wide instruction puts D[row = (lane>>4)*4 + r][col = lane & 15] where the
+// fp32 one does, so the i, f, o, g columns of a hidden channel still meet in one lane).  The raw sums are those of w * 2^k: sc = 2^-k
+// enters in the bias addition (one fma: the product is exact)
+template <int EPI>
+__device__ __forceinline__ void pair_epilogue(const GemmArgs &a, const f32x4 (&acc)[4][4], int n, int tile, int wave, int lane, float sc) {
+    auto pre = [&](float s, float b) { return fmaf(s, sc, b); };
+    const int col = lane & 15;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        if (wave + 4 * m >= 13) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int p = (wave + 4 * m) * 16 + (lane >> 4) * 4 + r;
+            if (p >= HW) continue;
+            if (EPI == EPI_LSTM) {
+                const int j = tile * 16 + col;
+                const float gi = sigm(pre(acc[m][0][r], a.bias[j]));
+                const float gf = sigm(pre(acc[m][1][r], a.bias[C + j]));
+                const float go = sigm(pre(acc[m][2][r], a.bias[2 * C + j]));
+                const float gg = tanhf(pre(acc[m][3][r], a.bias[3 * C + j]));
+                const size_t ci = ((size_t)n * C + j) * HW + p;
+                const float cp = a.h ? a.c[ci] : 0.f;
+                const float cn = gf * cp + gi * gg;
+                a.c[ci] = cn;
+                a.out[n * a.out_stride + (size_t)j * HW + p] = go * tanhf(cn);
+            } else {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int q = tile * 64 + g * 16 + col;
+                    a.out[n * a.out_stride + (size_t)q * HW + p] = fmaxf(pre(acc[m][g][r], a.bias[q]), 0.f);      // EPI_RELU
+                }
+            }
+        }
+    }
+}
+
+template <int EPI>
+__global__ __launch_bounds__(256, 2) void pair_kernel(PairArgs pa) {
+    __shared__ __attribute__((aligned(16))) split_t xs[2 * PTERM_X];
+    __shared__ __attribute__((aligned(16))) split_t ws[PROUND];
+    __shared__ unsigned red[4];
+    const GemmArgs &a = pa.g;
+    const int n = blockIdx.x, tile = blockIdx.y;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const bool report = tile == 0 && pa.status != nullptr;
+    if (tid < 4) red[tid] = 0u;
+    for (int i = tid; i < 2 * PTERM_X / 8; i += 256) reinterpret_cast<split_x8 *>(xs)[i] = split_x8{0, 0, 0, 0, 0, 0, 0, 0};
+
+    const int row = lane & 15, choct = (lane >> 4) & 1, tsel = lane >> 5;
+    int aoff[5], boff[5];       // fp16 offsets of the lane's fragment in xs (behind the M-tile's pixel) and ws (behind the column tile)
+#pragma unroll
+    for (int mf = 0; mf < 5; ++mf) {
+        const int tap = 2 * mf + tsel;
+        aoff[mf] = ((tap / 3) * 16 + tap % 3) * PKC + choct * 8;
+        boff[mf] = ((tap < 9 ? tap : 8) * 64 + row) * PKC + choct * 8;
+    }
+    int pb[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        int p = (wave + 4 * m) * 16 + row;
+        p = p < HW ? p : HW - 1;                // rows past the plane compute on pixel 195 and are never stored
+        pb[m] = ((p / 14) * 16 + p % 14) * PKC;
+    }
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[m][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int cloop = a.nvec + a.nx + (a.h ? a.nh : 0);
+    const int rounds = (a.ctot + PKC - 1) / PKC;
+    const split_t *wt = pa.wp + (size_t)tile * rounds * PROUND;
+    const float *vecn = a.vec ? a.vec + n * a.vec_stride : nullptr;
+    const float *xn = a.x + n * a.x_stride;
+    const float *hn = a.h ? a.h + n * a.h_stride : nullptr;
+    float smax[3] = {0.f, 0.f, 0.f};
+    bool bad = false;
+    for (int c0 = 0; c0 < cloop; c0 += PKC) {
+        __syncthreads();
+        // a task = one pixel's channel octet (the source boundaries are multiples of 8: one source per octet)
+        for (int i = tid; i < 2 * HW; i += 256) {
+            const int j = i >= HW, p = i - j * HW;
+            const int c = c0 + 8 * j;
+            float v[8];
+            int src = -1;
+            if (c >= cloop) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = 0.f;
+            } else if (c < a.nvec) {
+                src = 0;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = vecn[c + e];
+            } else if (c < a.nvec + a.nx) {
+                src = 1;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = xn[(c - a.nvec + e) * HW + p];
+            } else {
+                src = 2;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = hn[(c - a.nvec - a.nx + e) * HW + p];
+            }
+            if (report && src >= 0) {
+                float m = 0.f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    m = fmaxf(m, fabsf(v[e]));
+                    bad |= !(fabsf(v[e]) <= kSplitMaxAbs);
+                }
+                if (src == 0) smax[0] = fmaxf(smax[0], m);
+                else if (src == 1) smax[1] = fmaxf(smax[1], m);
+                else smax[2] = fmaxf(smax[2], m);
+            }
+            split_x2 h2[4], m2[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) split_terms2(v[2 * e], v[2 * e + 1], h2[e], m2[e]);
+            const int at = ((p / 14 + 1) * 16 + p % 14 + 1) * PKC + 8 * j;
+            *reinterpret_cast<split_x8 *>(xs + at) = split_x8{h2[0][0], h2[0][1], h2[1][0], h2[1][1], h2[2][0], h2[2][1], h2[3][0], h2[3][1]};
+            *reinterpret_cast<split_x8 *>(xs + PTERM_X + at) = split_x8{m2[0][0], m2[0][1], m2[1][0], m2[1][1], m2[2][0], m2[2][1], m2[3][0], m2[3][1]};
+        }
+        const split_x8 *wsrc = reinterpret_cast<const split_x8 *>(wt + (size_t)(c0 / PKC) * PROUND);
+        for (int i = tid; i < PROUND / 8; i += 256) reinterpret_cast<split_x8 *>(ws)[i] = wsrc[i];
+        __syncthreads();
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            f32x4 part[2][4];
+#pragma unroll
+            for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) part[mm][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int mf = 0; mf < 5; ++mf) {
+                split_x8 bh[4], bm[4];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    bh[g] = *reinterpret_cast<const split_x8 *>(ws + boff[mf] + g * 16 * PKC);
+                    bm[g] = *reinterpret_cast<const split_x8 *>(ws + PTERM_W + boff[mf] + g * 16 * PKC);
+                }
+#pragma unroll
+                for (int mm = 0; mm < 2; ++mm) {
+                    const int m = 2 * half + mm;
+                    if (wave + 4 * m < 13) {
+                        const int ao = (mf == 4 && tsel) ? choct * 8 : pb[m] + aoff[mf];      // tap 9 does not exist: zero halo pixel
+                        const split_x8 ah = *reinterpret_cast<const split_x8 *>(xs + ao);
+                        const split_x8 am = *reinterpret_cast<const split_x8 *>(xs + PTERM_X + ao);
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            part[mm][g] = PF_MFMA_SPLIT(ah, bm[g], part[mm][g]);
+                            part[mm][g] = PF_MFMA_SPLIT(am, bh[g], part[mm][g]);
+                            part[mm][g] = PF_MFMA_SPLIT(ah, bh[g], part[mm][g]);
+                        }
+                    }
+                }
+                // one step's fragments at a time: left alone the compiler hoists all five steps' reads (160 registers) and spills
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int mm = 0; mm < 2; ++mm) {
+                if (wave + 4 * (2 * half + mm) >= 13) continue;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) acc[2 * half + mm][g] += part[mm][g];
+            }
+        }
+    }
+    if (report) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (smax[k] > 0.f) atomicMax(&red[k], __builtin_bit_cast(unsigned, smax[k]));
+        if (bad) atomicOr(&red[3], 1u);
+        __syncthreads();
+        if (tid < 3 && red[tid] != 0u) atomicMax(pa.slots + tid, red[tid]);
+        if (tid == 3 && red[3] != 0u) atomicOr(pa.status, 1u);      // PF_STATUS_RANGE
+    }
+    pair_epilogue<EPI>(a, acc, n, tile, wave, lane, *pa.scale);
+}
+
+// Status block of a PF_FG_PAIR workspace: word 0 = this forward's PF_STATUS_* bits, word 1 = OR over the forwards since the host cleared
+// it, words 2, 3 = what pf_fg_status copies out, words FG_SLOT0 .. = the slots.  A slot that is non-zero and below kRangeLowMax is a K
+// source that was tiny over a whole launch: PF_STATUS_RANGE_LOW.  The slots are judged by whoever comes next - the following forward's
+// first launch (begin = 1: fold into word 1, zero word 0 and the slots) or pf_fg_status (begin = 0: fold, copy out, clear both words)
+__global__ __launch_bounds__(FG_STATUS_WORDS) void status_kernel(unsigned *st, int begin) {
+    __shared__ unsigned low;
+    const int tid = threadIdx.x;
+    if (tid == 0) low = 0u;
+    __syncthreads();
+    if (tid >= FG_SLOT0) {
+        const unsigned v = st[tid];
+        if (v != 0u && v < __builtin_bit_cast(unsigned, kRangeLowMax)) atomicOr(&low, 2u);      // PF_STATUS_RANGE_LOW
+        st[tid] = 0u;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned w0 = st[0] | low, w1 = st[1] | w0;
+        if (!begin) st[2] = w0, st[3] = w1;
+        st[0] = 0u;
+        st[1] = begin ? w1 : 0u;
     }
 }
 
@@ -499,8 +801,8 @@ static Ws ws_layout(int N, int T_in) {
     return w;
 }
 
-static int check_dims(int N, int T_in, int T_out, int flags) {
-    if (flags != 0) return fail(PF_EUNSUPPORTED, "pf_fg: unsupported flags 0x%x (only the shipped fg configuration is built)", flags);
+static int check_dims(int N, int T_in, int T_out, int flags, int known = PF_FG_PAIR) {
+    if (flags & ~known) return fail(PF_EUNSUPPORTED, "pf_fg: unsupported flags 0x%x (only the shipped fg configuration is built; PF_FG_PAIR is the one switch)", flags);
     if (N < 0 || N > (1 << 20) || T_in < 1 || T_in > 16 || T_out < 1 || T_out > 16)
         return fail(PF_EINVAL, "pf_fg: bad dims N=%d T_in=%d T_out=%d", N, T_in, T_out);
     return 0;
@@ -516,6 +818,39 @@ static int launch_gemm(const GemmArgs &a, int N, int tiles, const char *label, h
     return 0;
 }
 
+// the 3x3 GEMMs of a forward: gemm_kernel<9, EPI>, or pair_kernel<EPI> when the forward runs under PF_FG_PAIR (pc != nullptr)
+struct PairCtx {
+    const float *packed;
+    PairLayout P;
+    unsigned *st;       // status block
+    int launch;         // pair launches so far: picks the slots
+};
+static int pair_index(int gemm) {
+    for (int i = 0; i < NPAIR; ++i)
+        if (kPairGemm[i] == gemm) return i;
+    return -1;
+}
+template <int EPI>
+static int launch_conv3(const GemmArgs &a, int N, int tiles, int gemm, const char *label, const char *pair_label, PairCtx *pc, hipStream_t s) {
+    if (!pc) return launch_gemm<9, EPI>(a, N, tiles, label, s);
+    const int i = pair_index(gemm);
+    if (i < 0 || a.nvec % 8 || a.nx % 8 || a.nh % 8 || FG_SLOT0 + 3 * (pc->launch + 1) > FG_STATUS_WORDS)
+        return fail(PF_EINVAL, "pf_fg: %s has no pair form", label);
+    PairArgs pa = {};
+    pa.g = a;
+    pa.wp = reinterpret_cast<const split_t *>(pc->packed + pc->P.gemm[i]);
+    pa.scale = pc->packed + pc->P.head + 8 + i;
+    pa.status = pc->st;
+    pa.slots = pc->st + FG_SLOT0 + 3 * pc->launch++;
+    const double cols = tiles * 64.0;
+    const int cin = a.nvec + a.nx + (a.h ? a.nh : 0);
+    // flops: the fp32-equivalent work (one product per operand pair), as gemm_kernel counts it
+    ProfScope ps(s, pair_label, 2.0 * N * HW * cols * cin * 9, 4.0 * N * ((a.nx + (a.h ? a.nh : 0)) * HW + cols * HW));
+    hipLaunchKernelGGL((pair_kernel<EPI>), dim3(N, tiles), dim3(256), 0, s, pa);
+    PF_LAUNCH_CHECK(pair_label);
+    return 0;
+}
+
 }  // namespace fg
 }  // namespace pf
 
@@ -527,7 +862,7 @@ extern "C" int pf_fg_weights_size(int flags, size_t *raw_floats, size_t *packed_
     if (int rc = check_dims(0, 1, 1, flags)) return rc;
     const Layout L = layout();
     *raw_floats = L.raw_total;
-    *packed_floats = L.total;
+    *packed_floats = (flags & PF_FG_PAIR) ? pair_layout(L).total : L.total;
     return 0;
 }
 
@@ -543,13 +878,35 @@ extern "C" int pf_fg_pack(const float *raw, float *packed, int flags, void *stre
                            d.tiles, d.map);
         PF_LAUNCH_CHECK("pf_fg_pack");
     }
+    if (flags & PF_FG_PAIR) {
+        const PairLayout P = pair_layout(L);
+        unsigned *head = reinterpret_cast<unsigned *>(packed + P.head);
+        if (int rc = launch_zero_fill(head, 64 * sizeof(float), s)) return rc;
+        for (int i = 0; i < NPAIR; ++i) {
+            const GemmDesc &d = kGemm[kPairGemm[i]];
+            const long long n = (long long)d.tiles * 64 * d.ctot * d.taps;
+            hipLaunchKernelGGL(absmax_kernel, dim3(256), dim3(256), 0, s, raw + L.raw[d.src], n, head + i);
+            PF_LAUNCH_CHECK("pf_fg_pack");
+            hipLaunchKernelGGL(pack_pair_kernel, dim3(1024), dim3(256), 0, s, raw + L.raw[d.src], reinterpret_cast<_Float16 *>(packed + P.gemm[i]),
+                               d.ctot, d.tiles, d.map, head + i, packed + P.head + 8 + i);
+            PF_LAUNCH_CHECK("pf_fg_pack");
+        }
+    }
     return 0;
 }
 
 extern "C" int pf_fg_workspace(int N, int T_in, int T_out, int flags, size_t *bytes) {
     if (!bytes) return fail(PF_EINVAL, "pf_fg_workspace: null output");
-    if (int rc = check_dims(N, T_in, T_out, flags)) return rc;
+    // flags = 0 only, as ever: the workspace of a PF_FG_PAIR forward has a size call of its own
+    if (int rc = check_dims(N, T_in, T_out, flags, 0)) return rc;
     *bytes = ws_layout(N, T_in).total;
+    return 0;
+}
+
+extern "C" int pf_fg_pair_workspace(int N, int T_in, int T_out, size_t *bytes) {
+    if (!bytes) return fail(PF_EINVAL, "pf_fg_pair_workspace: null output");
+    if (int rc = check_dims(N, T_in, T_out, PF_FG_PAIR)) return rc;
+    *bytes = ws_layout(N, T_in).total + FG_STATUS_WORDS * sizeof(unsigned);
     return 0;
 }
 
@@ -565,11 +922,19 @@ extern "C" int pf_fg_forward(const float *packed, int flags, int N, int T_in, in
     if (!packed || !trajs || !traj_mask || !vel_mask || !feats || !output_inds || !odom || !depths || !depth_mask || !classes ||
         !traj_norm || !traj_unnorm || !mask_feats || !output_feats || !masks || !ws)
         return fail(PF_EINVAL, "pf_fg_forward: null buffer");
-    if (ws_bytes < W.total) return fail(PF_EWORKSPACE, "pf_fg_forward: workspace %zu < %zu bytes", ws_bytes, W.total);
+    const size_t status_bytes = (flags & PF_FG_PAIR) ? FG_STATUS_WORDS * sizeof(unsigned) : 0;
+    if (ws_bytes < W.total + status_bytes)
+        return fail(PF_EWORKSPACE, "pf_fg_forward: workspace %zu < %zu bytes", ws_bytes, W.total + status_bytes);
     hipStream_t s = (hipStream_t)stream;
     const Layout L = layout();
     const float *R = packed;
-    float *wsf = (float *)ws;
+    float *wsf = (float *)((char *)ws + status_bytes);
+    PairCtx pair_ctx = {packed, pair_layout(L), (unsigned *)ws, 0};
+    PairCtx *pc = (flags & PF_FG_PAIR) ? &pair_ctx : nullptr;
+    if (pc) {       // the forward's first launch: last forward's slots judged, word 0 and the slots zeroed (a kernel, never a memset node)
+        hipLaunchKernelGGL(status_kernel, dim3(1), dim3(FG_STATUS_WORDS), 0, s, pc->st, 1);
+        PF_LAUNCH_CHECK("status_kernel");
+    }
     const size_t P = (size_t)N * C * HW;
     const long long mf_stride = (long long)(1 + T_out) * C * HW;
 
@@ -608,7 +973,7 @@ extern "C" int pf_fg_forward(const float *packed, int flags, int N, int T_in, in
         g.h = t ? h0 + (t - 1) * P : nullptr, g.h_stride = (long long)C * HW, g.nh = C;
         g.ctot = TF + 2 * C, g.w = R + L.gemm[G_ME0], g.bias = R + L.raw[ME0_B];
         g.out = h0 + t * P, g.out_stride = (long long)C * HW, g.c = c0;
-        if (int rc = launch_gemm<9, EPI_LSTM>(g, N, 16, "pf::fg::gemm_kernel<9,lstm> enc0", s)) return rc;
+        if (int rc = launch_conv3<EPI_LSTM>(g, N, 16, G_ME0, "pf::fg::gemm_kernel<9,lstm> enc0", "pf::fg::pair_kernel<lstm> enc0", pc, s)) return rc;
     }
     int h1cur = -1;
     for (int t = 0; t < T_in; ++t) {
@@ -618,7 +983,7 @@ extern "C" int pf_fg_forward(const float *packed, int flags, int N, int T_in, in
         g.ctot = 2 * C, g.w = R + L.gemm[G_ME1], g.bias = R + L.raw[ME1_B];
         const int nxt = (h1cur + 1) & 1;
         g.out = h1 + nxt * P, g.out_stride = (long long)C * HW, g.c = c1;
-        if (int rc = launch_gemm<9, EPI_LSTM>(g, N, 16, "pf::fg::gemm_kernel<9,lstm> enc1", s)) return rc;
+        if (int rc = launch_conv3<EPI_LSTM>(g, N, 16, G_ME1, "pf::fg::gemm_kernel<9,lstm> enc1", "pf::fg::pair_kernel<lstm> enc1", pc, s)) return rc;
         h1cur = nxt;
     }
     int h0cur = T_in - 1;
@@ -656,7 +1021,7 @@ extern "C" int pf_fg_forward(const float *packed, int flags, int N, int T_in, in
             g.ctot = TF + 2 * C, g.w = R + L.gemm[G_MD0], g.bias = R + L.raw[MD0_B];
             const int nxt = (h0cur + 1) % W.r0;
             g.out = h0 + nxt * P, g.out_stride = (long long)C * HW, g.c = c0;
-            if (int rc = launch_gemm<9, EPI_LSTM>(g, N, 16, "pf::fg::gemm_kernel<9,lstm> dec0", s)) return rc;
+            if (int rc = launch_conv3<EPI_LSTM>(g, N, 16, G_MD0, "pf::fg::gemm_kernel<9,lstm> dec0", "pf::fg::pair_kernel<lstm> dec0", pc, s)) return rc;
             h0cur = nxt;
         }
         {
@@ -666,7 +1031,7 @@ extern "C" int pf_fg_forward(const float *packed, int flags, int N, int T_in, in
             g.ctot = 2 * C, g.w = R + L.gemm[G_MD1], g.bias = R + L.raw[MD1_B];
             const int nxt = (h1cur + 1) & 1;
             g.out = h1 + nxt * P, g.out_stride = (long long)C * HW, g.c = c1;
-            if (int rc = launch_gemm<9, EPI_LSTM>(g, N, 16, "pf::fg::gemm_kernel<9,lstm> dec1", s)) return rc;
+            if (int rc = launch_conv3<EPI_LSTM>(g, N, 16, G_MD1, "pf::fg::gemm_kernel<9,lstm> dec1", "pf::fg::pair_kernel<lstm> dec1", pc, s)) return rc;
             h1cur = nxt;
         }
         if (int rc = out_conv(1, t + 1)) return rc;
@@ -683,7 +1048,7 @@ extern "C" int pf_fg_forward(const float *packed, int flags, int N, int T_in, in
         g.x = src, g.x_stride = (long long)C * HW, g.nx = C;
         g.ctot = C, g.w = R + L.gemm[fw[i]], g.bias = R + L.raw[fb[i]];
         g.out = dsts[i], g.out_stride = (long long)C * HW;
-        if (int rc = launch_gemm<9, EPI_RELU>(g, N, 4, "pf::fg::gemm_kernel<9,relu> mask_fcn", s)) return rc;
+        if (int rc = launch_conv3<EPI_RELU>(g, N, 4, fw[i], "pf::fg::gemm_kernel<9,relu> mask_fcn", "pf::fg::pair_kernel<relu> mask_fcn", pc, s)) return rc;
         src = dsts[i];
     }
     {
@@ -699,4 +1064,20 @@ extern "C" int pf_fg_forward(const float *packed, int flags, int N, int T_in, in
         PF_LAUNCH_CHECK("predictor_kernel");
     }
     return 0;
+}
+
+extern "C" int pf_fg_status(void *ws, unsigned *out2, void *stream) {
+    if (!ws || !out2) return fail(PF_EINVAL, "pf_fg_status: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned *st = (unsigned *)ws;
+    hipLaunchKernelGGL(status_kernel, dim3(1), dim3(FG_STATUS_WORDS), 0, s, st, 0);
+    PF_LAUNCH_CHECK("status_kernel");
+    if (hipMemcpyAsync(out2, st + 2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(PF_EHIP, "pf_fg_status: reading the status words failed");
+    return 0;
+}
+
+extern "C" int pf_fg_status_reset(void *ws, void *stream) {
+    if (!ws) return fail(PF_EINVAL, "pf_fg_status_reset: null workspace");
+    return launch_zero_fill(ws, FG_STATUS_WORDS * sizeof(unsigned), (hipStream_t)stream);
 }

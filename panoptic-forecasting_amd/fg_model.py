@@ -2,7 +2,9 @@
 
 The module holds the reference's 52 parameters under the reference's state_dict keys (checkpoints load both ways) and
 runs inference through ``pf_fg_forward`` (csrc/fg_net.hip): ConvLSTM cells and the mask head on fp32 matrix
-instructions, the trajectory GRU path on small kernels.  The parameters are packed into one device buffer by
+instructions, the trajectory GRU path on small kernels.  ``model.fg_arithmetic: 'fp16_pair'`` runs the eight 3x3 GEMMs on
+the 16-bit matrix instruction with two fp16 terms per fp32 operand instead (PF_FG_PAIR, include/pfhip.h); a forward whose
+operands leave the pair's range is then handled as ``model.fg_on_range`` says (see ``FGModel.forward``).  The parameters are packed into one device buffer by
 ``pf_fg_pack``; they are packed again whenever a parameter changes (``load()``, ``load_state_dict``, ``.to()``).
 ``predict_panoptic`` / ``predict_semantics`` finish through the existing fg -> panoptic merge (panoptic.PanopticMerger).
 
@@ -26,6 +28,11 @@ _MUST_BE_ON = ('use_odometry', 'use_depth_inp')
 _MUST_BE_OFF = ('only_loc_feats', 'no_traj_inst_feats', 'no_mask_traj_feats', 'only_input_odometry')
 ODOM_SIZE = 5
 T_IN_MAX = T_OUT_MAX = 16
+ARITHMETIC_FLAGS = {'fp32': 0, 'fp16_pair': 1}          # include/pfhip.h: PF_FG_PAIR
+ON_RANGE = ('rerun', 'raise', 'ignore')
+PF_STATUS_RANGE, PF_STATUS_RANGE_LOW = 1, 2             # include/pfhip.h
+_STATUS_NAMES = ((PF_STATUS_RANGE, 'PF_STATUS_RANGE (an operand of a 3x3 GEMM exceeded 65504 in magnitude)'),
+                 (PF_STATUS_RANGE_LOW, 'PF_STATUS_RANGE_LOW (a K source of a launch had a non-zero maximum below 2^-6)'))
 
 
 def check_config(params):
@@ -45,6 +52,12 @@ def check_config(params):
     odom = params.get('data', {}).get('odom_size')
     if odom != ODOM_SIZE:
         raise ValueError('fg: data.odom_size = %r is not supported (this build computes %d)' % (odom, ODOM_SIZE))
+    arith = model.get('fg_arithmetic', 'fp32')
+    if arith not in ARITHMETIC_FLAGS:
+        raise ValueError("fg: model.fg_arithmetic = %r is not supported ('fp32' or 'fp16_pair')" % (arith,))
+    on_range = model.get('fg_on_range', 'rerun')
+    if on_range not in ON_RANGE:
+        raise ValueError("fg: model.fg_on_range = %r is not supported ('rerun', 'raise' or 'ignore')" % (on_range,))
 
 
 def _norm(params, key, size):
@@ -103,23 +116,30 @@ class FGModel(BaseModel):
         self.mask_decoder_out = nn.Conv2d(256, 256, 1)
         self.mask_head = _MaskHead()
         self.merger = PanopticMerger(use_depth_sorting=bool(self.use_depth_sorting), use_bbox_ulbr=bool(self.use_bbox_ulbr))
-        self._packed = None
-        self._packed_key = None
-        self._raw_keepalive = None
-        self._ws = None
+        self.fg_arithmetic = params['model'].get('fg_arithmetic', 'fp32')
+        self.fg_on_range = params['model'].get('fg_on_range', 'rerun')
+        self._packed = {}          # flags -> (parameter key, packed buffer, raw source kept alive)
+        self._ws = {}              # flags -> workspace
 
     # ---------------------------------------------------------------------------------------------- weights
     def _param_key(self):
         return tuple((t.data_ptr(), t._version) for t in self.state_dict().values())
 
-    def packed_weights(self):
-        """The device buffer pf_fg_pack filled from the current parameters (re-packed when any of them changed)."""
+    @property
+    def _flags(self):
+        return ARITHMETIC_FLAGS[self.fg_arithmetic]
+
+    def packed_weights(self, flags=None):
+        """The device buffer pf_fg_pack filled from the current parameters under ``flags`` (default: those of
+        ``fg_arithmetic``); re-packed when any parameter changed.  One buffer per arithmetic is kept."""
+        flags = self._flags if flags is None else flags
         key = self._param_key()
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
+        have = self._packed.get(flags)
+        if have is not None and have[0] == key:
+            return have[1]
         L = _lib.load()
         raw_n, packed_n = ctypes.c_size_t(), ctypes.c_size_t()
-        _lib.check(L.pf_fg_weights_size(0, ctypes.byref(raw_n), ctypes.byref(packed_n)), 'pf_fg_weights_size')
+        _lib.check(L.pf_fg_weights_size(flags, ctypes.byref(raw_n), ctypes.byref(packed_n)), 'pf_fg_weights_size')
         sd = self.state_dict()
         dev = next(iter(sd.values())).device
         _lib.require_cuda(torch.empty(0, device=dev), 'FGModel parameters')
@@ -127,23 +147,50 @@ class FGModel(BaseModel):
         if raw.numel() != raw_n.value:
             raise _lib.PfError('fg: %d parameter floats, pf_fg_pack expects %d' % (raw.numel(), raw_n.value))
         packed = torch.empty(packed_n.value, dtype=torch.float32, device=dev)
-        _lib.check(L.pf_fg_pack(raw.data_ptr(), packed.data_ptr(), 0, _lib.stream_ptr()), 'pf_fg_pack')
-        self._raw_keepalive = raw      # pf_fg_pack is asynchronous: keep its source alive until the next pack
-        self._packed, self._packed_key = packed, key
+        _lib.check(L.pf_fg_pack(raw.data_ptr(), packed.data_ptr(), flags, _lib.stream_ptr()), 'pf_fg_pack')
+        self._packed[flags] = (key, packed, raw)      # pf_fg_pack is asynchronous: its source stays alive until the next pack
         return packed
 
-    def _workspace(self, n, t_in, t_out, device):
+    def _workspace(self, n, t_in, t_out, device, flags):
         need = ctypes.c_size_t()
-        _lib.check(_lib.load().pf_fg_workspace(n, t_in, t_out, 0, ctypes.byref(need)), 'pf_fg_workspace')
-        if self._ws is None or self._ws.numel() < need.value or self._ws.device != device:
-            self._ws = torch.empty(max(need.value, 1), dtype=torch.uint8, device=device)
-        return self._ws
+        if flags:
+            _lib.check(_lib.load().pf_fg_pair_workspace(n, t_in, t_out, ctypes.byref(need)), 'pf_fg_pair_workspace')
+        else:
+            _lib.check(_lib.load().pf_fg_workspace(n, t_in, t_out, 0, ctypes.byref(need)), 'pf_fg_workspace')
+        ws = self._ws.get(flags)
+        if ws is None or ws.numel() < need.value or ws.device != device:
+            ws = self._ws[flags] = torch.empty(max(need.value, 1), dtype=torch.uint8, device=device)
+            if flags:                   # the status block in front of a pair workspace is cleared once, by its owner
+                _lib.check(_lib.load().pf_fg_status_reset(ws.data_ptr(), _lib.stream_ptr()), 'pf_fg_status_reset')
+        return ws
+
+    def _read_status(self, ws):
+        out2 = (ctypes.c_uint * 2)()
+        _lib.check(_lib.load().pf_fg_status(ws.data_ptr(), out2, _lib.stream_ptr()), 'pf_fg_status')
+        return int(out2[0]), int(out2[1])
+
+    def fg_status(self):
+        """PF_STATUS_* bits of every 'fp16_pair' forward since the last read, then cleared (synchronises; 0 in 'fp32' mode).
+        ``forward`` cannot read the status while a stream capture records it: read it here after the replays.  The words live in
+        the model's pair workspace: a forward of more instances or steps than any before allocates a new one with clear words."""
+        ws = self._ws.get(self._flags) if self._flags else None
+        if ws is None:
+            return 0
+        last, sticky = self._read_status(ws)
+        return last | sticky
 
     # ---------------------------------------------------------------------------------------------- forward
     @torch.no_grad()
     def forward(self, input_trajs, traj_mask, traj_vel_mask, instance_feats, output_inds, odom, input_depths,
                 input_depth_masks, classes, num_output_steps):
-        """FGModel.forward (fg_model.py:216-339): same arguments, same dict."""
+        """FGModel.forward (fg_model.py:216-339): same arguments, same dict.
+
+        ``fg_arithmetic == 'fp16_pair'``: after the enqueue the two status words are read with ONE synchronisation; when
+        PF_STATUS_RANGE / PF_STATUS_RANGE_LOW is set, ``fg_on_range`` decides: 'rerun' (default) runs the same forward again
+        with flags = 0 into the same output tensors (then bit-identical to the 'fp32' mode), 'raise' raises PfError naming
+        the bit, 'ignore' returns what the pair path computed.  While the stream is being captured nothing can be read:
+        the forward is enqueued only and the caller reads ``fg_status()`` after the replays.  'fp32' never synchronises."""
+        flags = self._flags
         packed = self.packed_weights()
         dev = packed.device
         n, t_in = input_trajs.shape[0], input_trajs.shape[1]
@@ -161,17 +208,31 @@ class FGModel(BaseModel):
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         out = {'normalized_trajectory': new(n, 1 + t_out, 10), 'unnormalized_trajectory': new(n, 1 + t_out, 10),
                'mask_feats': new(n, 1 + t_out, 256, 14, 14), 'output_feats': new(n, 256, 14, 14), 'masks': new(n, 28, 28)}
-        ws = self._workspace(n, t_in, t_out, dev)
-        rc = _lib.load().pf_fg_forward(packed.data_ptr(), 0, n, t_in, t_out, odom_t, *[a.data_ptr() for a in args],
-                                       *[out[k].data_ptr() for k in ('normalized_trajectory', 'unnormalized_trajectory',
-                                                                     'mask_feats', 'output_feats', 'masks')],
-                                       ws.data_ptr(), ws.numel(), _lib.stream_ptr())
-        _lib.check(rc, 'pf_fg_forward')
+
+        def run(fl):
+            # a PF_FG_PAIR buffer holds the flags = 0 layout in front of its pair section: the re-run needs no second pack
+            ws = self._workspace(n, t_in, t_out, dev, fl)
+            rc = _lib.load().pf_fg_forward(packed.data_ptr(), fl, n, t_in, t_out, odom_t, *[a.data_ptr() for a in args],
+                                           *[out[k].data_ptr() for k in ('normalized_trajectory', 'unnormalized_trajectory',
+                                                                         'mask_feats', 'output_feats', 'masks')],
+                                           ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+            _lib.check(rc, 'pf_fg_forward')
+            return ws
+
+        ws = run(flags)
+        if flags and n and self.fg_on_range != 'ignore' and not torch.cuda.is_current_stream_capturing():
+            status, _ = self._read_status(ws)
+            if status & (PF_STATUS_RANGE | PF_STATUS_RANGE_LOW):
+                if self.fg_on_range == 'raise':
+                    raise _lib.PfError("fg forward (model.fg_arithmetic = 'fp16_pair'): status %d: %s; run with model.fg_arithmetic "
+                                       "= 'fp32' or model.fg_on_range = 'rerun'"
+                                       % (status, ', '.join(name for bit, name in _STATUS_NAMES if status & bit)))
+                run(0)
         return out
 
     # ---------------------------------------------------------------------------------------------- predict
     def _predict(self, inputs, labels, panoptic):
-        dev = self.packed_weights().device
+        dev = next(iter(self.state_dict().values())).device
         cat = lambda key: torch.cat([x.to(dev) for x in inputs[key]])
         counts = [len(x) for x in inputs['feats']]
         trajs = cat('trajectories')

@@ -71,6 +71,9 @@ SIGNATURES = {
     'pf_fg_workspace': (_i, [_i, _i, _i, _i, _c.POINTER(_sz)]),
     'pf_fg_forward': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                            _vp, _sz, _vp]),
+    'pf_fg_pair_workspace': (_i, [_i, _i, _i, _c.POINTER(_sz)]),
+    'pf_fg_status': (_i, [_vp, _c.POINTER(_c.c_uint), _vp]),
+    'pf_fg_status_reset': (_i, [_vp, _vp]),
     'pf_odom_weights_size': (_i, [_i, _c.POINTER(_sz), _c.POINTER(_sz)]),
     'pf_odom_pack': (_i, [_vp, _vp, _i, _vp]),
     'pf_odom_forward': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

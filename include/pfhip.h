@@ -292,6 +292,35 @@ int pf_pq_status(const void *ws, void *stream, int *host_status);
 int pf_pq_status_reset(void *ws, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Semantic confusion matrix — the pixel counts behind IoU / mIoU of the Cityscapes pixel-level evaluation
+ * (cityscapesscripts.evaluation.evalPixelLevelSemanticLabeling; absent and unpinned here: parity unpinned).
+ *
+ *   pred, gt    [B,H,W] label maps, each of its own kind: 0 = u8, 1 = i32, 2 = i64; both are only read.  u8 is the native case
+ *               (exported PNGs and the model's own maps are bytes).  A base pointer need only be aligned to its element: heads and
+ *               tails of an image that do not fill a 16-byte load are read per element.
+ *   fmt 0       trainId format: values 0..18 are classes, everything else (255 included) is void.
+ *   fmt 1       Cityscapes labelIds, mapped through the inverse of the export's trainId -> id table; every id without a trainId is void.
+ *   A value whose class is >= n_cls (1..19) is void.
+ *   acc         [20,20] i64, ADDED to: row = ground-truth class, column = predicted class, index 19 = void.
+ *   per_image   (nullable) [B,20,20] i64, written.
+ * Integers only - there is no floating-point operation on the device - so two runs of a call give the same bits.  A workgroup of
+ * the count pass owns pf_confusion_chunk_pixels() = 16384 pixels of one image.
+ * Never silent: the first word of the workspace is a sticky status word, ORed with
+ *   PF_CONF_STATUS_VALUE  a value outside [0, 256) in an i32 / i64 map (compared in the map's own width: 2^33 + 5 is out of range)
+ * and an image flagged with it adds nothing to acc (its per_image block is zero).  The caller zeroes the first 256 bytes of a fresh
+ * workspace once (pf_confusion_status_reset enqueues that); everything else is zeroed by every call with the library's own fill
+ * kernel, so a captured call holds kernel nodes only.  pf_confusion_accumulate enqueues only (3 launches); B == 0 launches nothing.
+ * pf_confusion_status copies the status word to the host and waits for the stream.
+ */
+#define PF_CONF_STATUS_VALUE 1u
+int pf_confusion_workspace(int B, size_t *bytes);
+int pf_confusion_chunk_pixels(void);
+int pf_confusion_accumulate(const void *pred, int pred_kind, const void *gt, int gt_kind, int fmt, int n_cls, int B, int H, int W,
+                            long long *acc, long long *per_image, void *ws, size_t ws_bytes, void *stream);
+int pf_confusion_status(const void *ws, void *stream, int *host_status);
+int pf_confusion_status_reset(void *ws, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * pf_bg_dense_input - the network input of BGModel.forward (models/bg/bg_model.py:61-69) for the configurations the fused stem
  * of pf_bg_forward does not cover (convert2onehot = False, or no depth channels): writes x [B, T*C (+T), H, W] f32 for
  * pf_hardnet_forward_dense.

@@ -49,6 +49,11 @@ SIGNATURES = {
     'pf_pq_accumulate': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'pf_pq_status': (_i, [_vp, _vp, _c.POINTER(_i)]),
     'pf_pq_status_reset': (_i, [_vp, _vp]),
+    'pf_confusion_workspace': (_i, [_i, _c.POINTER(_sz)]),
+    'pf_confusion_chunk_pixels': (_i, []),
+    'pf_confusion_accumulate': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'pf_confusion_status': (_i, [_vp, _vp, _c.POINTER(_i)]),
+    'pf_confusion_status_reset': (_i, [_vp, _vp]),
     'pf_bg_dense_input': (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _i, _i, _i, _i, _vp, _vp]),
     'pf_seg_loss_workspace': (_i, [_i, _i, _i, _c.POINTER(_sz)]),
     'pf_seg_loss': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),

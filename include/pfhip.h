@@ -350,7 +350,9 @@ int pf_seg_loss(const float *logits, int B, int C, int Hin, int Win, const void 
  * (pretrained_models/fg/config.yaml: rnn_type gru, 2 ConvLSTM layers, 2 trajectory output layers, depth + odometry
  * inputs); its pieces: ConvLSTMCell (convlstm.py:44-70), nn.GRU, MaskRCNNConvUpsampleHead.forward
  * (mask_rcnn_conv_upsample_head.py:60-65), _compute_traj_inst_feats (:206-214), _normalize_traj (:179-188) and
- * expand_traj_mask (model_utils.py:11-27).  csrc/fg_net.hip.
+ * expand_traj_mask (model_utils.py:11-27).  csrc/fg_net.h lists the units: fg_schedule.cpp decides every launch of a forward and its
+ * buffers on the host (pf_debug_fg_schedule below shows the table), fg_net.hip enqueues them, fg_gemm.hip / fg_traj.hip / fg_pack.hip
+ * hold the kernels.
  *   flags      0 or PF_FG_PAIR (any other bit: PF_EUNSUPPORTED; reserved for the configuration switches).  The same value goes to
  *              pf_fg_weights_size, pf_fg_pack and pf_fg_forward of one model.
  *   PF_FG_PAIR the eight 3x3 GEMMs (the four ConvLSTM cells, mask_fcn1..4) run on v_mfma_f32_16x16x32_f16: every fp32 operand is
@@ -691,6 +693,22 @@ int pf_debug_plan_down(const void *blob, size_t bytes, int in_ch, int n_cls, flo
  * slots_streams (nullable): {dy slots, side streams} the library was built with. */
 int pf_debug_train_plan(const void *blob, size_t bytes, int in_ch, int n_cls, int B, int H, int W, int out_h, int out_w,
                         long long *regions, int cap_regions, int *n_regions, int *steps, int cap_steps, int *n_steps, int *slots_streams);
+/* Host only, no device involved, nothing enqueued (tests): the schedule of one pf_fg_forward(flags, N, T_in, T_out) - every launch in
+ * order with its buffers (csrc/fg_schedule.cpp) - and the workspace layout.  Refuses what pf_fg_forward refuses (dims, flags).
+ * *n_regions / *n_steps = rows of the tables; rows are copied while they fit (cap_regions, cap_steps rows).
+ * regions: rows of 3 {region, offset, bytes}, one per workspace region in layout order (region: enum Region of csrc/fg_net.h; the status
+ * block comes first and is empty without PF_FG_PAIR); offsets are multiples of 256, bytes = what the region holds; the last row is
+ * {0, 0, workspace bytes} = pf_fg_workspace / pf_fg_pair_workspace.
+ * steps: rows of 30, read back from the fields the enqueue loop hands to the launchers.  [0] kind (enum StepKind), [1] GEMM id (-1: not
+ * a GEMM), [2] epilogue, [3..5] channels of the K sources vec, x, h (h's also where a layer's first cell has no h), [6] ctot of the
+ * GEMM's packed weights, [7] pair weight section = scale index, [8] status-slot index (the launch owns words FG_SLOT0 + 3 * index .. + 2;
+ * both -1 unless kind = K_PAIR), [9] decoder step (-1: the encoder's launch of the instance feature / trajectory kernels), then for each
+ * of vec, x, h, out, c four numbers {region (0 = R_NONE: no such operand), offset, per-instance stride, floats it spans per instance},
+ * offset and stride in floats from the region's start; a caller's tensor (R_FEATS ..) is a region.  Instance n's range is [offset +
+ * n * stride, + span).  c (the ConvLSTM cell state, the GRU state) is read and written in place.
+ * labels (nullable): [cap_steps][64] chars, the NUL-padded profile label of each step ("" = the launch has none). */
+int pf_debug_fg_schedule(int N, int T_in, int T_out, int flags, long long *regions, int cap_regions, int *n_regions, long long *steps,
+                         char *labels, int cap_steps, int *n_steps);
 /* Instrumented builds only (make libpfhip_probe.so, env PF_PROBE=1): the 64 in-kernel timestamps (shader clock)
  * written by workgroup 0 / wave 0 of the last conv_wave launch; PF_EINVAL when nothing was recorded. */
 int pf_debug_probe_read(long long *host64);

@@ -1,4 +1,4 @@
-"""The fg forward under model.fg_arithmetic = 'fp16_pair' (PF_FG_PAIR: pair_kernel of csrc/fg_net.hip) against float64.
+"""The fg forward under model.fg_arithmetic = 'fp16_pair' (PF_FG_PAIR: pair_kernel of csrc/fg_gemm.hip) against float64.
 
 Single-kernel cases, bar D' (derived, elementwise): the bar D of tests/test_gpu_fg_stages.py plus the pair's own term,
     |hip - ref64| <= 1.01 ((2K + 2) 2^-24 + 2^-21) (op(|x|, |w|) + |b|)

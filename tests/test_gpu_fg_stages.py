@@ -1,4 +1,4 @@
-"""The fg forward (csrc/fg_net.hip) stage by stage against float64, through FGModel.forward alone.
+"""The fg forward (csrc/fg_net.hip enqueues what csrc/fg_schedule.cpp decides; kernels: fg_gemm.hip, fg_traj.hip) stage by stage against float64, through FGModel.forward alone.
 
 Two devices make a stage observable from outside: the kernels' own public outputs (mask_feats, output_feats) are the reference's
 INPUT for the stage behind them, and crafted weights (fg_ref64.crafted) turn the layers around a stage into exact identities - on the

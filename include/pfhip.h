@@ -321,6 +321,44 @@ int pf_confusion_status(const void *ws, void *stream, int *host_status);
 int pf_confusion_status_reset(void *ws, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Instance-weighted IoU (iIoU) — the per-instance sums behind "classes iIoU" / "categories iIoU" of the same evaluator (written
+ * down as remembered: parity unpinned).  Called beside pf_confusion_accumulate on the same predictions; the false positives of
+ * the score come from that call's [20,20] table.
+ *
+ *   pred        [B,H,W] prediction label map in fmt: 0 = u8, 1 = i32, 2 = i64 (as above).
+ *   inst        [B,H,W] ground-truth instance map (*_gtFine_instanceIds.png): 0 = u16, 1 = i32, 2 = i64; ALWAYS Cityscapes labelIds,
+ *               whatever fmt says about the prediction.  A value v > 1000 is the instance labelId * 1000 + k of its image (label
+ *               v / 1000, index k = v % 1000); it counts when its label's trainId c has 11 <= c < n_cls (person 24 .. bicycle 33).
+ *               Every other value is ignored without an error (v <= 1000, caravan 29xxx, trailer 30xxx, labels without a trainId).
+ *               Base pointers need only be aligned to their element, as above.
+ *   fmt 0 / 1   a pixel of an instance is a true positive when its prediction equals c (trainId format) / the labelId (Cityscapes).
+ *   Per instance of `size` pixels, `tp` of them true positives, in float64, each operation rounded once, never fused:
+ *               w = avg[c] / size;  tpw = tp * w;  fnw = (size - tp) * w        (avg: the evaluator's class-size table)
+ *   Per image and class the terms are added in ascending v, from 0.0, into (itp, ifn): an image's pairs are bit-identical
+ *   whatever batch it is in.
+ *   acc_inst          [8][2] f64 (itp, ifn) per thing class 11..18, ADDED to, image by image in batch order.
+ *   acc_counts        [8][3] i64 (instances, their pixels, their true-positive pixels), ADDED to.
+ *   per_image         (nullable) [B][8][2] f64, written.      per_image_counts  (nullable) [B][8][3] i64, written.
+ * The count pass is integers only (an image's u32 [8][1000][2] table of (size, tp) in the workspace, filled with integer atomics:
+ * the order they arrive in does not matter); a workgroup of it owns pf_iiou_chunk_pixels() = 16384 pixels of one image.  The
+ * first word of the workspace is a sticky status word of its own, ORed with
+ *   PF_IIOU_STATUS_VALUE  a prediction value outside [0, 256) or an instance value outside [0, 65536) in an i32 / i64 map (compared
+ *                         in the map's own width: 2^33 + 5 is out of range)
+ * and an image flagged with it adds nothing (its per-image blocks are zero).  The caller zeroes the first 256 bytes of a fresh
+ * workspace once (pf_iiou_status_reset enqueues that); everything else is zeroed by every call with the library's own fill
+ * kernel, so a captured call holds kernel nodes only.  pf_iiou_accumulate enqueues only (4 launches: fill, count, weigh, finish);
+ * B == 0 launches nothing.  pf_iiou_status copies the status word to the host and waits for the stream.
+ */
+#define PF_IIOU_STATUS_VALUE 1u
+int pf_iiou_workspace(int B, size_t *bytes);
+int pf_iiou_chunk_pixels(void);
+int pf_iiou_accumulate(const void *pred, int pred_kind, const void *inst, int inst_kind, int fmt, int n_cls, int B, int H, int W,
+                       double *acc_inst, long long *acc_counts, double *per_image, long long *per_image_counts, void *ws,
+                       size_t ws_bytes, void *stream);
+int pf_iiou_status(const void *ws, void *stream, int *host_status);
+int pf_iiou_status_reset(void *ws, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * pf_bg_dense_input - the network input of BGModel.forward (models/bg/bg_model.py:61-69) for the configurations the fused stem
  * of pf_bg_forward does not cover (convert2onehot = False, or no depth channels): writes x [B, T*C (+T), H, W] f32 for
  * pf_hardnet_forward_dense.

@@ -177,7 +177,8 @@ def results_from_acc(acc, names):
     return out
 
 
-def print_table(res, out=sys.stdout):
+def print_table(res, out=None):
+    out = out or sys.stdout                      # looked up per call: the stream of import time may be closed by now
     out.write('%-16s %7s %7s %7s %4s\n' % ('', 'PQ', 'SQ', 'RQ', 'N'))
     for name, r in res['per_class'].items():
         out.write('%-16s %7.2f %7.2f %7.2f\n' % (name, 100 * r['pq'], 100 * r['sq'], 100 * r['rq']))

@@ -54,6 +54,11 @@ SIGNATURES = {
     'pf_confusion_accumulate': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'pf_confusion_status': (_i, [_vp, _vp, _c.POINTER(_i)]),
     'pf_confusion_status_reset': (_i, [_vp, _vp]),
+    'pf_iiou_workspace': (_i, [_i, _c.POINTER(_sz)]),
+    'pf_iiou_chunk_pixels': (_i, []),
+    'pf_iiou_accumulate': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pf_iiou_status': (_i, [_vp, _vp, _c.POINTER(_i)]),
+    'pf_iiou_status_reset': (_i, [_vp, _vp]),
     'pf_bg_dense_input': (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _i, _i, _i, _i, _vp, _vp]),
     'pf_seg_loss_workspace': (_i, [_i, _i, _i, _c.POINTER(_sz)]),
     'pf_seg_loss': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),

@@ -747,6 +747,13 @@ int pf_debug_train_plan(const void *blob, size_t bytes, int in_ch, int n_cls, in
  * labels (nullable): [cap_steps][64] chars, the NUL-padded profile label of each step ("" = the launch has none). */
 int pf_debug_fg_schedule(int N, int T_in, int T_out, int flags, long long *regions, int cap_regions, int *n_regions, long long *steps,
                          char *labels, int cap_steps, int *n_steps);
+/* Host only, no device involved, nothing enqueued (tests): how the count kernels of pf_confusion_accumulate and pf_iiou_accumulate
+ * (csrc/label_scan.h) split an image of n pixels whose two maps start at addr_a / addr_b, have elements of esz_a / esz_b bytes and
+ * are loaded by a lane in units of P pixels that need align_a / align_b bytes of alignment.  out5 = {head, units, tail0, map a
+ * aligned after the head, map b aligned after the head}: pixels [0, head) and [tail0, n) are read per element, units * P pixels
+ * from head on by unit loads.  head is the fewest pixels below 16 that align both maps, failing that map a alone, clamped to n. */
+int pf_debug_label_scan_span(unsigned long long addr_a, unsigned long long addr_b, int esz_a, int esz_b, int align_a, int align_b,
+                             unsigned long long n, int P, unsigned long long *out5);
 /* Instrumented builds only (make libpfhip_probe.so, env PF_PROBE=1): the 64 in-kernel timestamps (shader clock)
  * written by workgroup 0 / wave 0 of the last conv_wave launch; PF_EINVAL when nothing was recorded. */
 int pf_debug_probe_read(long long *host64);

@@ -3,12 +3,8 @@
 // ground-truth instance is a distinct value v > 1000 of an image's instance map (labelId * 1000 + k, always in labelIds); it counts
 // when its label's trainId c is a thing class below n_cls.  Enqueue only.
 //
-//   iiou_count_kernel   integers only.  grid (pixel chunks, B): a chunk never spans two images.  An image is [head | units | tail] as
-//                       in conf_count_kernel: the head (< 16 pixels) ends where both maps reach the alignment of a lane's load; a
-//                       unit is what one lane reads per trip - 16 pixels where the prediction is u8 and the instance map u16 (16
-//                       bytes of prediction, two 16-byte loads of instance values), else 4 pixels.  Head and tail go through per
-//                       element (workgroup 0 of the image, one lane per pixel); a map that no head aligns is read by element loads.
-//                       A lane has kIiouGroup trips in flight and folds runs of equal raw (inst, pred) pairs in registers.  A run
+//   iiou_count_kernel   integers only.  The scan of label_scan.h over (pred, inst); 16 pixels per unit where the prediction is u8 and
+//                       the instance map u16.  A lane folds runs of equal raw (inst, pred) pairs in registers.  A run
 //                       that ends is classified once: v <= 1000 leaves at once (stuff, groups, label 1), label = v / 1000 by
 //                       multiply-high, thing index through the 128-entry LUT in LDS, k = v - 1000 * label.  It adds (run, run if the
 //                       prediction has the instance's class else 0) to the counter pair of slot (thing, k): first in the workgroup's
@@ -26,6 +22,7 @@
 //                       acc_counts in image order, writes the per_image outputs (zero for a flagged image) and ORs the flags
 //                       into the sticky status word.
 // Built with FP contraction off; the f64 operations are the _rn intrinsics besides.
+#include "label_scan.h"
 #include "panoptic_ids.h"
 #include "pf_common.h"
 #include "pf_prof.h"
@@ -35,9 +32,6 @@ namespace pf {
 constexpr int kIiouThings = 8;                  // trainIds 11..18
 constexpr int kIiouIndices = 1000;              // k of labelId * 1000 + k
 constexpr int kIiouSlots = kIiouThings * kIiouIndices;
-constexpr int kIiouThreads = 256;
-constexpr int kIiouChunkPixels = 16384;         // pixels of units one count workgroup owns, whatever the kinds
-constexpr int kIiouGroup = 4;                   // trips whose loads are in flight together
 constexpr int kIiouLdsBits = 9;
 constexpr int kIiouLdsSlots = 1 << kIiouLdsBits;   // entries of a workgroup's LDS table
 constexpr int kIiouProbes = 4;
@@ -94,70 +88,6 @@ template <> struct IiouInst<kIiouInstU16> { typedef unsigned short T; };
 template <> struct IiouInst<kIiouInstI32> { typedef int T; };
 template <> struct IiouInst<kIiouInstI64> { typedef long long T; };
 
-// bytes a lane's load of one unit of P pixels must be aligned to
-template <typename T, int P> __host__ __device__ constexpr int iiou_align() { return (int)(P * sizeof(T) < 16 ? P * sizeof(T) : 16); }
-
-// one element; false: a value outside [0, 2^BITS) (BITS = 8 for the prediction, 16 for the instance map)
-template <typename T, int BITS>
-__device__ __forceinline__ bool iiou_load1(const T *base, size_t i, unsigned &v) {
-    if (sizeof(T) * 8 <= BITS) {
-        v = (unsigned)base[i];
-        return true;
-    }
-    const unsigned long long x = (unsigned long long)(long long)base[i];   // a negative value keeps its high bits
-    v = (unsigned)x;
-    return (x >> BITS) == 0;
-}
-
-// four pixels from pixel i on (the generic unit)
-template <typename T, int BITS>
-__device__ __forceinline__ bool iiou_load4(const T *base, size_t i, bool aligned, unsigned v[4]) {
-    if (!aligned) {
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ok = iiou_load1<T, BITS>(base, i + k, v[k]) && ok;
-        return ok;
-    }
-    if constexpr (sizeof(T) == 1) {
-        const unsigned w = *reinterpret_cast<const unsigned *>(base + i);
-        v[0] = w & 255u; v[1] = (w >> 8) & 255u; v[2] = (w >> 16) & 255u; v[3] = w >> 24;
-        return true;
-    } else if constexpr (sizeof(T) == 2) {
-        const uint2 w = *reinterpret_cast<const uint2 *>(base + i);
-        v[0] = w.x & 65535u; v[1] = w.x >> 16; v[2] = w.y & 65535u; v[3] = w.y >> 16;
-        return true;
-    } else if constexpr (sizeof(T) == 4) {
-        const int4 s = *reinterpret_cast<const int4 *>(base + i);
-        v[0] = (unsigned)s.x; v[1] = (unsigned)s.y; v[2] = (unsigned)s.z; v[3] = (unsigned)s.w;
-        return ((v[0] | v[1] | v[2] | v[3]) >> BITS) == 0;
-    } else {
-        const longlong2 *s = reinterpret_cast<const longlong2 *>(base + i);
-        const longlong2 s0 = s[0], s1 = s[1];
-        v[0] = (unsigned)s0.x; v[1] = (unsigned)s0.y; v[2] = (unsigned)s1.x; v[3] = (unsigned)s1.y;
-        return (((unsigned long long)s0.x | (unsigned long long)s0.y | (unsigned long long)s1.x | (unsigned long long)s1.y) >> BITS) == 0;
-    }
-}
-
-// sixteen u8 pixels from pixel i on as four words
-__device__ __forceinline__ uint4 iiou_pred16(const unsigned char *base, size_t i, bool aligned) {
-    if (aligned) return *reinterpret_cast<const uint4 *>(base + i);
-    unsigned w[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        w[k] = (unsigned)base[i + 4 * k] | ((unsigned)base[i + 4 * k + 1] << 8) | ((unsigned)base[i + 4 * k + 2] << 16) |
-               ((unsigned)base[i + 4 * k + 3] << 24);
-    return uint4{w[0], w[1], w[2], w[3]};
-}
-
-// eight u16 pixels from pixel i on as four words
-__device__ __forceinline__ uint4 iiou_inst8(const unsigned short *base, size_t i, bool aligned) {
-    if (aligned) return *reinterpret_cast<const uint4 *>(base + i);
-    unsigned w[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) w[k] = (unsigned)base[i + 2 * k] | ((unsigned)base[i + 2 * k + 1] << 16);
-    return uint4{w[0], w[1], w[2], w[3]};
-}
-
 // a workgroup's table in LDS and the image's table in the workspace
 struct IiouTables {
     unsigned *key;              // [kIiouLdsSlots] slot or kIiouEmpty
@@ -194,49 +124,46 @@ __device__ __forceinline__ void iiou_flush(const IiouTables &t, unsigned key, un
     iiou_add(t, thing * kIiouIndices + (v - label * 1000u), n, p == want ? n : 0u);
 }
 
+// the sink of the scan; key = inst << 8 | pred
 struct IiouFold {
-    unsigned cur, run, p4, i2;   // cur = inst << 8 | pred; p4 / i2: its prediction byte / instance half repeated (u8 x u16 path)
+    IiouTables t;
+    unsigned p4, i2;   // the prediction byte / instance half of the fold's current key repeated (u8 x u16 path)
+
+    __device__ __forceinline__ void flush(unsigned key, unsigned n) { iiou_flush(t, key, n); }
+
+    // four pixels: a word of prediction bytes and two words of instance halves; one compare triple while the run lasts
+    __device__ __forceinline__ void word(RunFold &f, unsigned pw, unsigned i0, unsigned i1) {
+        if (pw == p4 && i0 == i2 && i1 == i2) {
+            f.run += 4;
+            return;
+        }
+        fold_pixel(f, *this, ((i0 & 65535u) << 8) | (pw & 255u));
+        fold_pixel(f, *this, ((i0 >> 16) << 8) | ((pw >> 8) & 255u));
+        fold_pixel(f, *this, ((i1 & 65535u) << 8) | ((pw >> 16) & 255u));
+        fold_pixel(f, *this, ((i1 >> 16) << 8) | (pw >> 24));
+        p4 = (f.cur & 255u) * 0x01010101u;
+        i2 = (f.cur >> 8) * 0x00010001u;
+    }
+
+    __device__ __forceinline__ void raw(RunFold &f, const uint4 &p, const uint4 (&i)[2]) {
+        word(f, p.x, i[0].x, i[0].y);
+        word(f, p.y, i[0].z, i[0].w);
+        word(f, p.z, i[1].x, i[1].y);
+        word(f, p.w, i[1].z, i[1].w);
+    }
 };
 
-__device__ __forceinline__ void iiou_pixel(IiouFold &f, const IiouTables &t, unsigned key) {
-    if (key == f.cur) {
-        ++f.run;
-    } else {
-        if (f.run) iiou_flush(t, f.cur, f.run);
-        f.cur = key;
-        f.run = 1;
-    }
-}
-
-// four pixels: a word of prediction bytes and two words of instance halves; one compare triple while the run lasts
-__device__ __forceinline__ void iiou_word(IiouFold &f, const IiouTables &t, unsigned pw, unsigned i0, unsigned i1) {
-    if (pw == f.p4 && i0 == f.i2 && i1 == f.i2) {
-        f.run += 4;
-        return;
-    }
-    iiou_pixel(f, t, ((i0 & 65535u) << 8) | (pw & 255u));
-    iiou_pixel(f, t, ((i0 >> 16) << 8) | ((pw >> 8) & 255u));
-    iiou_pixel(f, t, ((i1 & 65535u) << 8) | ((pw >> 16) & 255u));
-    iiou_pixel(f, t, ((i1 >> 16) << 8) | (pw >> 24));
-    f.p4 = (f.cur & 255u) * 0x01010101u;
-    f.i2 = (f.cur >> 8) * 0x00010001u;
-}
-
 template <int PK, int IK>
-__global__ __launch_bounds__(kIiouThreads) void iiou_count_kernel(IiouArgs a) {
+__global__ __launch_bounds__(kScanThreads) void iiou_count_kernel(IiouArgs a) {
     typedef typename IiouPred<PK>::T PT;
     typedef typename IiouInst<IK>::T IT;
-    constexpr bool kNative = PK == kIiouPredU8 && IK == kIiouInstU16;
-    constexpr int P = kNative ? 16 : 4;                         // pixels of one unit
-    constexpr int AP = iiou_align<PT, P>(), AI = iiou_align<IT, P>();
-    constexpr size_t kUnitsPerChunk = kIiouChunkPixels / P;
-    static_assert(kUnitsPerChunk % (kIiouGroup * kIiouThreads) == 0, "a chunk is whole groups of trips");
+    constexpr int P = (PK == kIiouPredU8 && IK == kIiouInstU16) ? 16 : 4;   // pixels of one unit
 
     __shared__ unsigned key[kIiouLdsSlots];
     __shared__ unsigned cnt[kIiouLdsSlots][2];
     __shared__ unsigned char lut[128];
     const int b = blockIdx.y, tid = threadIdx.x;
-    for (int i = tid; i < kIiouLdsSlots; i += kIiouThreads) {
+    for (int i = tid; i < kIiouLdsSlots; i += kScanThreads) {
         key[i] = kIiouEmpty;
         cnt[i][0] = 0;
         cnt[i][1] = 0;
@@ -249,87 +176,12 @@ __global__ __launch_bounds__(kIiouThreads) void iiou_count_kernel(IiouArgs a) {
     const size_t n = a.n_per_image;
     const PT *pb = reinterpret_cast<const PT *>(a.pred) + (size_t)b * n;
     const IT *ib = reinterpret_cast<const IT *>(a.inst) + (size_t)b * n;
-    // the head: the fewest pixels after which both maps are aligned for a lane's load; failing that, the prediction alone
-    const uintptr_t pa = (uintptr_t)pb, ia = (uintptr_t)ib;
-    size_t head = 16;
-    for (int h = 15; h >= 0; --h)
-        if ((pa + h * sizeof(PT)) % AP == 0 && (ia + h * sizeof(IT)) % AI == 0) head = h;
-    if (head == 16)
-        for (int h = 15; h >= 0; --h)
-            if ((pa + h * sizeof(PT)) % AP == 0) head = h;
-    if (head > n) head = n;
-    const bool al_p = (pa + head * sizeof(PT)) % AP == 0, al_i = (ia + head * sizeof(IT)) % AI == 0;
-    const size_t units = (n - head) / P, tail0 = head + units * P;   // tail pixels [tail0, n): fewer than P
-
-    IiouTables t{key, &cnt[0][0], reinterpret_cast<unsigned *>(a.ws + a.l.tables) + (size_t)b * kIiouSlots * 2, lut, a.fmt};
-    IiouFold f{0u, 0u, 0u, 0u};
-    bool ok = true;
-    const size_t u0 = (size_t)blockIdx.x * kUnitsPerChunk;
-    const size_t u1 = u0 + kUnitsPerChunk < units ? u0 + kUnitsPerChunk : units;
-    for (size_t g = u0; g < u1; g += (size_t)kIiouGroup * kIiouThreads) {
-        if constexpr (kNative) {
-            uint4 pv[kIiouGroup], iv0[kIiouGroup], iv1[kIiouGroup];
-#pragma unroll
-            for (int k = 0; k < kIiouGroup; ++k) {
-                const size_t u = g + (size_t)k * kIiouThreads + tid;
-                if (u < u1) {
-                    pv[k] = iiou_pred16(pb, head + u * P, al_p);
-                    iv0[k] = iiou_inst8(ib, head + u * P, al_i);
-                    iv1[k] = iiou_inst8(ib, head + u * P + 8, al_i);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kIiouGroup; ++k) {
-                const size_t u = g + (size_t)k * kIiouThreads + tid;
-                if (u < u1) {
-                    iiou_word(f, t, pv[k].x, iv0[k].x, iv0[k].y);
-                    iiou_word(f, t, pv[k].y, iv0[k].z, iv0[k].w);
-                    iiou_word(f, t, pv[k].z, iv1[k].x, iv1[k].y);
-                    iiou_word(f, t, pv[k].w, iv1[k].z, iv1[k].w);
-                }
-            }
-        } else {
-            unsigned pv[kIiouGroup][4], iv[kIiouGroup][4];
-            bool good[kIiouGroup];
-#pragma unroll
-            for (int k = 0; k < kIiouGroup; ++k) {
-                const size_t u = g + (size_t)k * kIiouThreads + tid;
-                good[k] = true;
-                if (u < u1) {
-                    const bool okp = iiou_load4<PT, 8>(pb, head + u * P, al_p, pv[k]);
-                    const bool oki = iiou_load4<IT, 16>(ib, head + u * P, al_i, iv[k]);
-                    good[k] = okp && oki;
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kIiouGroup; ++k) {
-                const size_t u = g + (size_t)k * kIiouThreads + tid;
-                if (u >= u1) continue;
-                if (!good[k]) {   // the image is flagged below and adds nothing: its pixels need not be counted
-                    ok = false;
-                    continue;
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) iiou_pixel(f, t, (iv[k][j] << 8) | pv[k][j]);
-            }
-        }
-    }
-    if (f.run) iiou_flush(t, f.cur, f.run);
-    if (blockIdx.x == 0) {   // head and tail, one lane per pixel: fewer than 16 + P <= 32 of them
-        const size_t ntail = n - tail0;
-        size_t i = n;
-        if ((size_t)tid < head) i = tid;
-        else if ((size_t)tid - head < ntail) i = tail0 + ((size_t)tid - head);
-        if (i < n) {
-            unsigned p, v;
-            const bool okp = iiou_load1<PT, 8>(pb, i, p), oki = iiou_load1<IT, 16>(ib, i, v);
-            if (okp && oki) iiou_flush(t, (v << 8) | p, 1u);
-            else ok = false;
-        }
-    }
+    IiouFold sink{{key, &cnt[0][0], reinterpret_cast<unsigned *>(a.ws + a.l.tables) + (size_t)b * kIiouSlots * 2, lut, a.fmt}, 0u, 0u};
+    const IiouTables &t = sink.t;
+    const bool ok = label_scan<PT, IT, 16, P>(pb, ib, n, sink);
     if (!ok) atomicOr(reinterpret_cast<unsigned *>(a.ws + a.l.flags) + b, PF_IIOU_STATUS_VALUE);
     __syncthreads();
-    for (int i = tid; i < kIiouLdsSlots; i += kIiouThreads) {
+    for (int i = tid; i < kIiouLdsSlots; i += kScanThreads) {
         const unsigned slot = key[i];
         if (slot == kIiouEmpty) continue;
         atomicAdd(t.image + 2 * slot, cnt[i][0]);
@@ -429,9 +281,9 @@ __global__ __launch_bounds__(64) void iiou_finish_kernel(IiouArgs a) {
 
 template <int PK>
 static void iiou_launch_inst(int inst_kind, dim3 grid, hipStream_t s, const IiouArgs &a) {
-    if (inst_kind == kIiouInstU16) hipLaunchKernelGGL((iiou_count_kernel<PK, kIiouInstU16>), grid, dim3(kIiouThreads), 0, s, a);
-    else if (inst_kind == kIiouInstI32) hipLaunchKernelGGL((iiou_count_kernel<PK, kIiouInstI32>), grid, dim3(kIiouThreads), 0, s, a);
-    else hipLaunchKernelGGL((iiou_count_kernel<PK, kIiouInstI64>), grid, dim3(kIiouThreads), 0, s, a);
+    if (inst_kind == kIiouInstU16) hipLaunchKernelGGL((iiou_count_kernel<PK, kIiouInstU16>), grid, dim3(kScanThreads), 0, s, a);
+    else if (inst_kind == kIiouInstI32) hipLaunchKernelGGL((iiou_count_kernel<PK, kIiouInstI32>), grid, dim3(kScanThreads), 0, s, a);
+    else hipLaunchKernelGGL((iiou_count_kernel<PK, kIiouInstI64>), grid, dim3(kScanThreads), 0, s, a);
 }
 
 }  // namespace pf
@@ -442,7 +294,7 @@ extern "C" int pf_iiou_workspace(int B, size_t *bytes) {
     return PF_OK;
 }
 
-extern "C" int pf_iiou_chunk_pixels(void) { return pf::kIiouChunkPixels; }
+extern "C" int pf_iiou_chunk_pixels(void) { return pf::kScanChunkPixels; }
 
 extern "C" int pf_iiou_accumulate(const void *pred, int pred_kind, const void *inst, int inst_kind, int fmt, int n_cls, int B, int H,
                                   int W, double *acc_inst, long long *acc_counts, double *per_image, long long *per_image_counts,
@@ -467,7 +319,7 @@ extern "C" int pf_iiou_accumulate(const void *pred, int pred_kind, const void *i
     hipStream_t s = (hipStream_t)stream;
     if (int rc = pf::launch_zero_fill((char *)ws + l.flags, l.total - l.flags, s)) return rc;
     pf::IiouArgs a{pred, inst, (char *)ws, l, acc_inst, per_image, acc_counts, per_image_counts, n, B, fmt, n_cls};
-    const size_t gx = (n + pf::kIiouChunkPixels - 1) / pf::kIiouChunkPixels;   // the units are at most n pixels; at least one workgroup
+    const size_t gx = (n + pf::kScanChunkPixels - 1) / pf::kScanChunkPixels;   // the units are at most n pixels; at least one workgroup
     const dim3 grid((unsigned)gx, (unsigned)B);
     {
         pf::ProfScope ps(s, "pf::iiou_count_kernel(pf::IiouArgs)", 0.0, (double)B * n * (double)(psz[pred_kind] + isz[inst_kind]));
@@ -490,15 +342,7 @@ extern "C" int pf_iiou_accumulate(const void *pred, int pred_kind, const void *i
 }
 
 extern "C" int pf_iiou_status(const void *ws, void *stream, int *host_status) {
-    if (!ws || !host_status) return pf::fail(PF_EINVAL, "pf_iiou_status: null argument");
-    unsigned st = 0;
-    PF_HIP_CHECK(hipMemcpyAsync(&st, ws, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    PF_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    *host_status = (int)st;
-    return PF_OK;
+    return pf::sticky_status_read("pf_iiou_status", ws, stream, host_status);
 }
 
-extern "C" int pf_iiou_status_reset(void *ws, void *stream) {
-    if (!ws) return pf::fail(PF_EINVAL, "pf_iiou_status_reset: null argument");
-    return pf::launch_zero_fill(ws, 256, (hipStream_t)stream);
-}
+extern "C" int pf_iiou_status_reset(void *ws, void *stream) { return pf::sticky_status_reset("pf_iiou_status_reset", ws, stream); }

@@ -37,6 +37,10 @@ static inline const char *ab_env(const char *name) { return PF_AB ? getenv(name)
 // pf_fill.hip: zero fill / device-to-device copy as kernels (a captured call of the library holds kernel nodes only - see there)
 int launch_zero_fill(void *p, size_t bytes, hipStream_t s);
 int launch_copy(void *dst, const void *src, size_t bytes, hipStream_t s);
+// the evaluators' workspaces begin with a sticky status word in [0, 256): copy it to the host after the stream / enqueue its clearing
+// (who: the entry point's name, for the error text)
+int sticky_status_read(const char *who, const void *ws, void *stream, int *host_status);
+int sticky_status_reset(const char *who, void *ws, void *stream);
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int round_up4(int w) { return (w + 3) / 4 * 4; }   // a row of w pixels padded to whole 16-byte pieces

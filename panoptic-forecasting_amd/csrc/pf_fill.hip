@@ -67,4 +67,18 @@ int launch_copy(void *dst, const void *src, size_t bytes, hipStream_t s) {
     return PF_OK;
 }
 
+int sticky_status_read(const char *who, const void *ws, void *stream, int *host_status) {
+    if (!ws || !host_status) return fail(PF_EINVAL, "%s: null argument", who);
+    unsigned st = 0;
+    PF_HIP_CHECK(hipMemcpyAsync(&st, ws, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    PF_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    *host_status = (int)st;
+    return PF_OK;
+}
+
+int sticky_status_reset(const char *who, void *ws, void *stream) {
+    if (!ws) return fail(PF_EINVAL, "%s: null argument", who);
+    return launch_zero_fill(ws, 256, (hipStream_t)stream);
+}
+
 }  // namespace pf

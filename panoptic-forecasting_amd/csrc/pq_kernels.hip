@@ -21,6 +21,9 @@
 //   pq_finish_kernel  adds the B rows into the caller's accumulators in image order (flagged images add nothing) and ORs the flags
 //                     into the sticky status word.
 // Floating point is only the division and the ordered sums: two runs of a call give the same bits.
+#include <type_traits>
+
+#include "label_scan.h"
 #include "panoptic_ids.h"
 #include "pf_common.h"
 #include "pf_prof.h"
@@ -134,21 +137,10 @@ __device__ __forceinline__ void lds_add(u64 *tab, unsigned *used, u64 *pairs, un
     image_add(pairs, flag, key, n);
 }
 
-template <bool I64>
-__device__ __forceinline__ bool load4(const void *base, size_t quad, unsigned v[4]) {   // false: a value outside [0, 65536)
-    if (I64) {
-        const longlong2 *s = reinterpret_cast<const longlong2 *>(base) + 2 * quad;
-        const longlong2 s0 = s[0], s1 = s[1];
-        v[0] = (unsigned)s0.x; v[1] = (unsigned)s0.y; v[2] = (unsigned)s1.x; v[3] = (unsigned)s1.y;
-        return (((u64)s0.x | (u64)s0.y | (u64)s1.x | (u64)s1.y) >> 16) == 0;
-    }
-    const int4 s = reinterpret_cast<const int4 *>(base)[quad];
-    v[0] = (unsigned)s.x; v[1] = (unsigned)s.y; v[2] = (unsigned)s.z; v[3] = (unsigned)s.w;
-    return ((v[0] | v[1] | v[2] | v[3]) >> 16) == 0;
-}
-
 template <bool P64, bool G64>
 __global__ __launch_bounds__(kPqCountThreads) void pq_count_kernel(PqArgs a) {
+    typedef typename std::conditional<P64, long long, int>::type PT;
+    typedef typename std::conditional<G64, long long, int>::type GT;
     __shared__ u64 tab[kPqLdsSlots];
     __shared__ unsigned used;
     const int b = blockIdx.y;
@@ -158,8 +150,8 @@ __global__ __launch_bounds__(kPqCountThreads) void pq_count_kernel(PqArgs a) {
     char *img = a.ws + a.l.images + (size_t)b * a.l.image_stride;
     u64 *pairs = reinterpret_cast<u64 *>(img + a.l.pairs);
     unsigned *flag = reinterpret_cast<unsigned *>(a.ws + a.l.flags) + b;
-    const char *pb = reinterpret_cast<const char *>(a.pred) + (size_t)b * a.n_per_image * (P64 ? 8 : 4);
-    const char *gb = reinterpret_cast<const char *>(a.gt) + (size_t)b * a.n_per_image * (G64 ? 8 : 4);
+    const PT *pb = reinterpret_cast<const PT *>(a.pred) + (size_t)b * a.n_per_image;
+    const GT *gb = reinterpret_cast<const GT *>(a.gt) + (size_t)b * a.n_per_image;
 
     const size_t n4 = a.n_per_image >> 2;
     const size_t trips = (n4 + kPqCountThreads - 1) / kPqCountThreads, per = (trips + gridDim.x - 1) / gridDim.x;
@@ -170,7 +162,7 @@ __global__ __launch_bounds__(kPqCountThreads) void pq_count_kernel(PqArgs a) {
         const size_t q = t * kPqCountThreads + threadIdx.x;
         if (q >= n4) break;
         unsigned p[4], g[4];
-        const bool okp = load4<P64>(pb, q, p), okg = load4<G64>(gb, q, g);
+        const bool okp = load4<PT, 16>(pb, 4 * q, true, p), okg = load4<GT, 16>(gb, 4 * q, true, g);   // false: a value outside [0, 65536)
         if (!(okp && okg)) {   // the image is flagged below and adds nothing: its pairs need not be counted
             ok = false;
             continue;
@@ -390,16 +382,6 @@ extern "C" int pf_pq_accumulate(const void *pred, int pred_is_i64, const void *g
     return PF_OK;
 }
 
-extern "C" int pf_pq_status(const void *ws, void *stream, int *host_status) {
-    if (!ws || !host_status) return pf::fail(PF_EINVAL, "pf_pq_status: null argument");
-    unsigned st = 0;
-    PF_HIP_CHECK(hipMemcpyAsync(&st, ws, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    PF_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    *host_status = (int)st;
-    return PF_OK;
-}
+extern "C" int pf_pq_status(const void *ws, void *stream, int *host_status) { return pf::sticky_status_read("pf_pq_status", ws, stream, host_status); }
 
-extern "C" int pf_pq_status_reset(void *ws, void *stream) {
-    if (!ws) return pf::fail(PF_EINVAL, "pf_pq_status_reset: null argument");
-    return pf::launch_zero_fill(ws, 256, (hipStream_t)stream);
-}
+extern "C" int pf_pq_status_reset(void *ws, void *stream) { return pf::sticky_status_reset("pf_pq_status_reset", ws, stream); }

@@ -22,7 +22,6 @@ import argparse
 import json
 import os
 import sys
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -37,15 +36,10 @@ from . import dist as pfdist       # noqa: E402
 from . import hop_io               # noqa: E402
 from . import panoptic             # noqa: E402
 from . import pq                   # noqa: E402
+from . import eval_common          # noqa: E402
+from .eval_common import EvalError, LABEL_NAMES, N_CLS, gather_total  # noqa: E402,F401
 
-LABEL_NAMES = ('road', 'sidewalk', 'building', 'wall', 'fence', 'pole', 'traffic light', 'traffic sign', 'vegetation', 'terrain',
-               'sky', 'person', 'rider', 'car', 'truck', 'bus', 'train', 'motorcycle', 'bicycle')
-N_CLS = 19
 THING_IDS = frozenset(panoptic.TRAINID2ID[pq.FIRST_THING:])
-
-
-class EvalError(RuntimeError):
-    pass
 
 
 def parse_args(argv=None):
@@ -123,10 +117,7 @@ def read_pair(item):
 
 def _ids_on_device(rgb, device):
     """[B,H,W,3] u8 host array -> [B,H,W] i32 ids on the device (pinned staging, asynchronous copy)."""
-    t = torch.from_numpy(rgb)
-    if torch.cuda.is_available():
-        t = t.pin_memory()
-    t = t.to(device, non_blocking=True).to(torch.int32)
+    t = eval_common.on_device(rgb, device).to(torch.int32)
     return (t[..., 0] + 256 * t[..., 1] + 65536 * t[..., 2]).contiguous()
 
 
@@ -136,38 +127,17 @@ def accumulate(pairs, a, device=None):
         device = device or torch.device('cuda', torch.cuda.current_device())
         meter = pq.PanopticQuality(N_CLS, fmt='cityscapes', crowd=True, device=device)
     acc = torch.zeros(N_CLS, 4, dtype=torch.float64)
-    with ThreadPoolExecutor(max_workers=max(1, a.num_workers)) as pool:
-        loaded = pool.map(read_pair, pairs)
-        batch, shape = [], None
-        def flush():
-            if not batch:
-                return
-            g = np.stack([x[0] for x in batch])
-            p = np.stack([x[1] for x in batch])
-            if a.matcher == 'device':
-                meter.update(_ids_on_device(p, device), _ids_on_device(g, device))
-            else:
-                pq.pq_panoptic_host(torch.from_numpy(panoptic.decode_png(p)), torch.from_numpy(panoptic.decode_png(g)), N_CLS,
-                                    fmt='cityscapes', crowd=True, acc=acc)
-            del batch[:]
-        for g, p in loaded:
-            if batch and (g.shape != shape or len(batch) >= a.batch_size):
-                flush()
-            shape = g.shape
-            batch.append((g, p))
-        flush()
+    def on_batch(g, p):
+        if a.matcher == 'device':
+            meter.update(_ids_on_device(p, device), _ids_on_device(g, device))
+        else:
+            pq.pq_panoptic_host(torch.from_numpy(panoptic.decode_png(p)), torch.from_numpy(panoptic.decode_png(g)), N_CLS,
+                                fmt='cityscapes', crowd=True, acc=acc)
+    eval_common.for_each_batch(pairs, read_pair, a, on_batch)
     if a.matcher == 'device':
         meter.result()                                    # waits; raises on a set status word
         acc = meter.acc
     return acc
-
-
-def gather_total(acc):
-    """This rank's [19,4] accumulators -> their sum over the ranks, on the host.  The exchange runs where the process group's
-    backend has tensors: RCCL ("nccl") carries device tensors only, gloo host tensors (dist.gather_accumulators moves those itself)."""
-    if pfdist.is_dist() and str(torch.distributed.get_backend()) != 'gloo':
-        acc = acc.to(torch.device('cuda', torch.cuda.current_device()))
-    return pfdist.gather_accumulators(acc).sum(0).cpu()
 
 
 def results_from_acc(acc, names):
@@ -189,31 +159,14 @@ def print_table(res, out=None):
 
 
 def run(a):
-    rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if pfdist.is_dist() else (0, 1)
     pairs, names = pair_images(a)
-    if a.matcher == 'device' and not torch.cuda.is_available():
-        raise EvalError('--matcher device needs a GPU (there is no fallback: pass --matcher host for the host path)')
-    mine = [pairs[i] for i in pfdist.shard_indices(len(pairs), rank, world)]
-    acc = accumulate(mine, a)
-    total = gather_total(acc)
-    res = results_from_acc(total, names)
-    if rank == 0:
-        with open(a.results_file, 'w', encoding='utf-8') as f:
-            json.dump(res, f, indent=4)
-        print_table(res)
-    return res
+    eval_common.require_matcher(a)
+    mine = [pairs[i] for i in pfdist.shard_indices(len(pairs), *eval_common.rank_world())]
+    return eval_common.write_results(results_from_acc(gather_total(accumulate(mine, a)), names), a, print_table)
 
 
 def main(argv=None):
-    a = parse_args(argv)
-    pfdist.init_distributed_mode()
-    try:
-        run(a)
-    except EvalError as e:                              # no barrier: the other ranks may not have failed
-        sys.exit('eval_panoptic: %s' % e)
-    if pfdist.is_dist():
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
+    eval_common.main('eval_panoptic', parse_args, run, argv)
 
 
 if __name__ == '__main__':

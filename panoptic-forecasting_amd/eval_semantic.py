@@ -27,16 +27,14 @@ its images' [8,2] pairs, they are gathered by global index and added in sorted g
 The PNGs are read on a thread pool and go to the device as bytes through pinned staging; ``semantic_iou.SemanticIoU`` counts them
 there (``--matcher device``, batches stay in flight: ``update`` only enqueues) or ``semantic_iou.confusion_host`` on the host
 (``--matcher host``).  Under an initialised process group the images are sharded round-robin and the int64 tables gathered
-(``eval_panoptic.gather_total``: device tensors under RCCL); rank 0 writes the file (All / Stuff / MO / per_class / pixel_acc as fractions and the
+(``eval_common.gather_total``: device tensors under RCCL); rank 0 writes the file (All / Stuff / MO / per_class / pixel_acc as fractions and the
 [20,20] table under 'confusion'; an absent class's iou is ``null``) and prints the table.
 """
 import argparse
 import glob
-import json
 import math
 import os
 import sys
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -50,7 +48,8 @@ if __package__ in (None, ''):                     # run as a script: make the pa
 from . import dist as pfdist       # noqa: E402
 from . import hop_io               # noqa: E402
 from . import semantic_iou         # noqa: E402
-from .eval_panoptic import EvalError, LABEL_NAMES, N_CLS, gather_total  # noqa: E402
+from . import eval_common          # noqa: E402
+from .eval_common import EvalError, LABEL_NAMES, N_CLS, gather_total  # noqa: E402
 
 GT_SUFFIX = {'cityscapes': '_gtFine_labelIds.png', 'trainid': '_labelTrainIds.png'}
 LABEL_SUFFIX = {'cityscapes': '_labelIds.png', 'trainid': '_labelTrainIds.png'}      # what _instanceIds.png replaces
@@ -124,14 +123,6 @@ def read_pair(item):
     return g, p, (i.view(np.int16) if i.dtype.itemsize == 2 else i.astype(np.int32, copy=False))   # 16-bit stays 16-bit
 
 
-def _bytes_on_device(arr, device):
-    """[B,H,W] u8 host array -> the same bytes on the device (pinned staging, asynchronous copy)."""
-    t = torch.from_numpy(arr)
-    if torch.cuda.is_available():
-        t = t.pin_memory()
-    return t.to(device, non_blocking=True)
-
-
 def accumulate(pairs, a, device=None, inst_out=None):
     """[20,20] int64 confusion table of this rank's images (device matcher: on the device).  Where the pairs carry instance files
     (with_instances), the dict ``inst_out`` receives 'per_image' ([n,8,2] float64, the images' (itp, ifn) pairs in the order of
@@ -142,35 +133,21 @@ def accumulate(pairs, a, device=None, inst_out=None):
         meter = semantic_iou.SemanticIoU(N_CLS, fmt=a.format, device=device)
     acc = torch.zeros(semantic_iou.N_CELLS, semantic_iou.N_CELLS, dtype=torch.int64)
     per_image, counts = [], torch.zeros(n_things, 3, dtype=torch.int64)
-    with ThreadPoolExecutor(max_workers=max(1, a.num_workers)) as pool:
-        loaded = pool.map(read_pair, pairs)
-        batch, shape = [], None
-        def flush():
-            if not batch:
-                return
-            g = np.stack([x[0] for x in batch])
-            p = np.stack([x[1] for x in batch])
-            i = np.stack([x[2] for x in batch]) if len(batch[0]) == 3 else None
-            if a.matcher == 'device':
-                if i is None:
-                    meter.update(_bytes_on_device(p, device), _bytes_on_device(g, device))
-                else:
-                    per_image.append(torch.empty(len(batch), n_things, 2, dtype=torch.float64, device=device))
-                    meter.update(_bytes_on_device(p, device), _bytes_on_device(g, device), inst=_bytes_on_device(i, device),
-                                 per_image_inst=per_image[-1])
+    to = eval_common.on_device
+    def on_batch(g, p, i=None):
+        if a.matcher == 'device':
+            if i is None:
+                meter.update(to(p, device), to(g, device))
             else:
-                semantic_iou.confusion_host(torch.from_numpy(p), torch.from_numpy(g), N_CLS, fmt=a.format, acc=acc)
-                if i is not None:
-                    sums, n = semantic_iou.instance_sums_host(torch.from_numpy(p), torch.from_numpy(i), N_CLS, fmt=a.format)
-                    per_image.append(sums)
-                    counts.add_(n.sum(0))
-            del batch[:]
-        for item in loaded:
-            if batch and (item[0].shape != shape or item[-1].dtype != batch[0][-1].dtype or len(batch) >= a.batch_size):
-                flush()
-            shape = item[0].shape
-            batch.append(item)
-        flush()
+                per_image.append(torch.empty(len(g), n_things, 2, dtype=torch.float64, device=device))
+                meter.update(to(p, device), to(g, device), inst=to(i, device), per_image_inst=per_image[-1])
+        else:
+            semantic_iou.confusion_host(torch.from_numpy(p), torch.from_numpy(g), N_CLS, fmt=a.format, acc=acc)
+            if i is not None:
+                sums, n = semantic_iou.instance_sums_host(torch.from_numpy(p), torch.from_numpy(i), N_CLS, fmt=a.format)
+                per_image.append(sums)
+                counts.add_(n.sum(0))
+    eval_common.for_each_batch(pairs, read_pair, a, on_batch)
     if a.matcher == 'device':
         meter.result()                                    # waits; raises on a set status word
         acc = meter.acc
@@ -246,10 +223,9 @@ def ordered_instance_sums(per_image, n_images, world):
 
 
 def run(a):
-    rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if pfdist.is_dist() else (0, 1)
+    rank, world = eval_common.rank_world()
     pairs = pair_images(a)
-    if a.matcher == 'device' and not torch.cuda.is_available():
-        raise EvalError('--matcher device needs a GPU (there is no fallback: pass --matcher host for the host path)')
+    eval_common.require_matcher(a)
     pairs = with_instances(pairs, a)
     mine = [pairs[i] for i in pfdist.shard_indices(len(pairs), rank, world)]
     if len(pairs[0]) == 3:
@@ -260,23 +236,11 @@ def run(a):
         acc = accumulate(mine, a, inst_out=sums)
         total, counts = gather_total(acc), gather_total(sums['counts'])
         res = results_from_acc(total, acc_inst=ordered_instance_sums(sums['per_image'], len(pairs), world), inst_counts=counts)
-    if rank == 0:
-        with open(a.results_file, 'w', encoding='utf-8') as f:
-            json.dump(res, f, indent=4)
-        print_table(res)
-    return res
+    return eval_common.write_results(res, a, print_table)
 
 
 def main(argv=None):
-    a = parse_args(argv)
-    pfdist.init_distributed_mode()
-    try:
-        run(a)
-    except EvalError as e:                              # no barrier: the other ranks may not have failed
-        sys.exit('eval_semantic: %s' % e)
-    if pfdist.is_dist():
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
+    eval_common.main('eval_semantic', parse_args, run, argv)
 
 
 if __name__ == '__main__':

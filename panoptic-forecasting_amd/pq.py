@@ -11,6 +11,8 @@ sharded evaluation reproduces the single-process numbers (sum_iou to float64 rou
 """
 import torch
 
+from .meter import DeviceMeter
+
 VOID = 255
 
 
@@ -206,43 +208,20 @@ def pq_splits(acc, scale=100.0):
     return out
 
 
-class PanopticQuality:
+class PanopticQuality(DeviceMeter):
     """Device-side panoptic quality: ``update`` enqueues pf_pq_accumulate on the current stream and returns at once (no
     synchronisation, capturable), ``acc`` is the [n_cls,4] float64 device tensor, ``result`` waits and reads the status word."""
+    WORKSPACES = {'pq': ('_ws', '')}
+    HOST_PATH = 'pq_panoptic_host'
 
     def __init__(self, n_cls=19, fmt='trainid', crowd=True, device='cuda'):
-        from . import lib as _lib
         if fmt not in FORMATS:
             raise ValueError('fmt must be one of %s (got %r)' % (sorted(FORMATS), fmt))
         if not 1 <= n_cls <= 19:
             raise ValueError('n_cls must be 1..19')
-        self._lib = _lib
+        super().__init__(device)
         self.n_cls, self.fmt, self.crowd = n_cls, fmt, bool(crowd)
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise _lib.PfError('PanopticQuality runs on the GPU (got %s): use pq_panoptic_host on the host' % self.device)
         self.acc = torch.zeros(n_cls, 4, dtype=torch.float64, device=self.device)
-        self._ws = None
-        self._captured = False
-
-    def _workspace(self, b):
-        """The workspace grows with the largest B seen.  A captured graph keeps the pointer it was captured with, so the
-        workspace may not grow during a capture or after one: call update once with the largest batch before capturing."""
-        import ctypes
-        need = ctypes.c_size_t()
-        self._lib.check(self._lib.load().pf_pq_workspace(b, ctypes.byref(need)), 'pf_pq_workspace')
-        capturing = torch.cuda.is_current_stream_capturing()
-        if self._ws is None or self._ws.numel() < need.value:
-            if capturing or self._captured:
-                raise self._lib.PfError('PanopticQuality: the workspace would have to grow to B = %d %s a graph capture, whose replays '
-                                        'keep the old pointer: call update() with the largest batch before capturing'
-                                        % (b, 'during' if capturing else 'after'))
-            ws = torch.zeros(need.value, dtype=torch.uint8, device=self.device)    # status word starts at 0
-            if self._ws is not None:
-                ws[:256].copy_(self._ws[:256])                                       # a sticky bit survives the growth
-            self._ws = ws
-        self._captured = self._captured or capturing
-        return self._ws
 
     @torch.no_grad()
     def update(self, pred, gt, per_image=None):
@@ -264,7 +243,7 @@ class PanopticQuality:
             lib.require_cuda(per_image, 'per_image')
             if per_image.dtype != torch.float64 or tuple(per_image.shape) != (b, self.n_cls, 4):
                 raise lib.PfError('per_image must be float64 [%d,%d,4]' % (b, self.n_cls))
-        ws = self._workspace(b)
+        ws = self._workspace(b, 'pq')
         lib.check(L.pf_pq_accumulate(maps[0].data_ptr(), int(maps[0].dtype == torch.int64), maps[1].data_ptr(),
                                      int(maps[1].dtype == torch.int64), FORMATS[self.fmt], int(self.crowd), self.n_cls, b, h, w,
                                      self.acc.data_ptr(), per_image.data_ptr() if per_image is not None else None,
@@ -273,12 +252,7 @@ class PanopticQuality:
 
     def status(self):
         """The sticky status word (waits for the current stream)."""
-        import ctypes
-        if self._ws is None:
-            return 0
-        st = ctypes.c_int()
-        self._lib.check(self._lib.load().pf_pq_status(self._ws.data_ptr(), self._lib.stream_ptr(), ctypes.byref(st)), 'pf_pq_status')
-        return st.value
+        return self._status_word('pq')
 
     def result(self):
         """pq_from_acc's dict plus the 'All' / 'Things' / 'Stuff' split; PfError naming the bit when the status word is set."""
@@ -293,6 +267,5 @@ class PanopticQuality:
 
     def reset(self):
         self.acc.zero_()
-        if self._ws is not None:
-            self._lib.check(self._lib.load().pf_pq_status_reset(self._ws.data_ptr(), self._lib.stream_ptr()), 'pf_pq_status_reset')
+        self._status_reset()
         return self

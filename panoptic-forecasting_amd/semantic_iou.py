@@ -19,6 +19,8 @@ exchange: they are bit-identical whatever batch the image is in, and a sharded e
 """
 import torch
 
+from .meter import DeviceMeter
+
 FORMATS = {'trainid': 0, 'cityscapes': 1}
 N_CELLS = 20                           # 19 classes + void
 VOID = 19
@@ -219,51 +221,24 @@ def category_scores(acc, acc_inst=None, scale=100.0):
     return out
 
 
-class SemanticIoU:
+class SemanticIoU(DeviceMeter):
     """Device-side confusion meter: ``update`` enqueues pf_confusion_accumulate (and, given an instance map, pf_iiou_accumulate)
     on the current stream and returns at once (no synchronisation, capturable), ``acc`` is the [20,20] int64 device tensor,
     ``acc_inst`` / ``acc_inst_counts`` the [8,2] float64 / [8,3] int64 instance sums, ``result`` waits and reads the status words."""
+    WORKSPACES = {'confusion': ('_ws', 'confusion '), 'iiou': ('_ws_inst', 'iiou ')}   # the iIoU calls have a workspace and a status word of their own
+    HOST_PATH = 'confusion_host'
 
     def __init__(self, n_cls=19, fmt='trainid', device='cuda'):
-        from . import lib as _lib
         if fmt not in FORMATS:
             raise ValueError('fmt must be one of %s (got %r)' % (sorted(FORMATS), fmt))
         if not 1 <= n_cls <= 19:
             raise ValueError('n_cls must be 1..19')
-        self._lib = _lib
+        super().__init__(device)
         self.n_cls, self.fmt = n_cls, fmt
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise _lib.PfError('SemanticIoU runs on the GPU (got %s): use confusion_host on the host' % self.device)
         self.acc = torch.zeros(N_CELLS, N_CELLS, dtype=torch.int64, device=self.device)
         self.acc_inst = torch.zeros(N_THINGS, 2, dtype=torch.float64, device=self.device)
         self.acc_inst_counts = torch.zeros(N_THINGS, 3, dtype=torch.int64, device=self.device)
-        self._ws = None
-        self._ws_inst = None
-        self._captured = False
         self._updates = [0, 0]           # updates without / with an instance map
-
-    def _workspace(self, b, which='confusion'):
-        """The workspace grows with the largest B seen.  A captured graph keeps the pointer it was captured with, so the
-        workspace may not grow during a capture or after one: call update once with the largest batch before capturing.
-        The iIoU calls have a workspace (and a status word) of their own under the same rule."""
-        import ctypes
-        attr = '_ws' if which == 'confusion' else '_ws_inst'
-        old = getattr(self, attr)
-        need = ctypes.c_size_t()
-        self._lib.check(getattr(self._lib.load(), 'pf_%s_workspace' % which)(b, ctypes.byref(need)), 'pf_%s_workspace' % which)
-        capturing = torch.cuda.is_current_stream_capturing()
-        if old is None or old.numel() < need.value:
-            if capturing or self._captured:
-                raise self._lib.PfError('SemanticIoU: the %s workspace would have to grow to B = %d %s a graph capture, whose replays '
-                                        'keep the old pointer: call update() with the largest batch before capturing'
-                                        % (which, b, 'during' if capturing else 'after'))
-            ws = torch.zeros(need.value, dtype=torch.uint8, device=self.device)    # status word starts at 0
-            if old is not None:
-                ws[:256].copy_(old[:256])                                            # a sticky bit survives the growth
-            setattr(self, attr, ws)
-        self._captured = self._captured or capturing
-        return getattr(self, attr)
 
     @torch.no_grad()
     def update(self, pred, gt, per_image=None, inst=None, per_image_inst=None, per_image_inst_counts=None):
@@ -306,7 +281,7 @@ class SemanticIoU:
                 lib.require_cuda(t, name)
                 if t.dtype != dtype or tuple(t.shape) != (b, N_THINGS, last):
                     raise lib.PfError('%s must be %s [%d,%d,%d]' % (name, str(dtype).split('.')[1], b, N_THINGS, last))
-        ws = self._workspace(b)
+        ws = self._workspace(b, 'confusion')
         ws_inst = self._workspace(b, 'iiou') if inst is not None else None     # both sized before anything is enqueued
         lib.check(L.pf_confusion_accumulate(maps[0].data_ptr(), _KINDS[maps[0].dtype], maps[1].data_ptr(), _KINDS[maps[1].dtype],
                                             FORMATS[self.fmt], self.n_cls, b, h, w, self.acc.data_ptr(),
@@ -323,15 +298,7 @@ class SemanticIoU:
 
     def _status_words(self):
         """(confusion status word, iIoU status word); waits for the current stream."""
-        import ctypes
-        out = []
-        for ws, which in ((self._ws, 'confusion'), (self._ws_inst, 'iiou')):
-            st = ctypes.c_int()
-            if ws is not None:
-                self._lib.check(getattr(self._lib.load(), 'pf_%s_status' % which)(ws.data_ptr(), self._lib.stream_ptr(), ctypes.byref(st)),
-                                'pf_%s_status' % which)
-            out.append(st.value)
-        return tuple(out)
+        return self._status_word('confusion'), self._status_word('iiou')
 
     def status(self):
         """The sticky status words ORed (both calls use bit 1 for a value out of range; waits for the current stream)."""
@@ -362,8 +329,5 @@ class SemanticIoU:
         self.acc_inst.zero_()
         self.acc_inst_counts.zero_()
         self._updates = [0, 0]
-        for ws, which in ((self._ws, 'confusion'), (self._ws_inst, 'iiou')):
-            if ws is not None:
-                self._lib.check(getattr(self._lib.load(), 'pf_%s_status_reset' % which)(ws.data_ptr(), self._lib.stream_ptr()),
-                                'pf_%s_status_reset' % which)
+        self._status_reset()
         return self

@@ -553,7 +553,16 @@ int pf_odom_backward(const float *packed, int flags, int B, int T_in, int T_out,
  *                   launch goes away.  In FC-HarDNet-70: base.4.layers.3 and base.5.  1 = where it measured faster
  *                   (csrc/conv_select.cpp::down_wanted), 0 = never - and a plan CREATED while the process-wide value is 0 packs no
  *                   weights for it -, 2 = wherever the form exists (A/B runs, tests); results agree with the two launches within
- *                   1e-5 (1 + max) (tests/test_gpu_fold_down.py);
+ *                   1e-5 (1 + max) (tests/test_gpu_fold_down.py).  The same option covers 3x3 convs of three cout tiles, all in one
+ *                   workgroup, in front of a 1x1 conv of at most 96 couts (conv_s4_down_kernel<3, 32, 8, 1>, fragments in a region of
+ *                   their own; in FC-HarDNet-70: base.7.layers.3 and base.8; tests/test_gpu_fold_wide.py);
+ *   "fold_lo"       (default 1) a 3x3 packed-pair conv of three cout tiles in front of an upsample + 1x1 conv pair that runs commuted
+ *                   ("fuse_upsample"): the launch also computes the 1x1 conv's columns over the upsample's input at the low resolution
+ *                   (at most 64 couts; no bias, no ReLU: those belong to the other half) into the fp32 scratch the other half samples
+ *                   (csrc/conv_s4.hip, conv_s4_lo_kernel); the range the upsample reads ends with the 3x3 conv's slice as for
+ *                   "fold_down".  The slice is stored only if another op reads it; otherwise pf_hardnet_tensor_read of its tensor is
+ *                   refused ("elided").  In FC-HarDNet-70: denseBlocksUp.2.layers.3 and conv1x1_up.3.  0 / 1 / 2 as for "fold_down"
+ *                   (csrc/conv_select.cpp::lo_wanted; tests/test_gpu_fold_wide.py);
  *   "train_blocked_sum" (default 1; process-wide only) the 3x3 convolutions of a training step add every round of 8 input channels
  *                   into a second accumulator set (blocked summation, like ATen's): forward activations 0.79-0.95 x as far from
  *                   float64 as torch-CPU fp32; 0 = one fp32 chain over all 9 Cin terms;
@@ -713,6 +722,11 @@ int pf_debug_plan_tail(const void *blob, size_t bytes, int in_ch, int n_cls, flo
 /* Host only, as pf_debug_plan_tail: the region of the down form ("fold_down"), and per op the offset in floats of the 1x1 reader's
  * fragments, kept on the 3x3 op: [cout tile 4][chunk 2][term 2][lane 64][8 fp16]; 0 = none. */
 int pf_debug_plan_down(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                       long long *table, int table_ops);
+/* Host only, as pf_debug_plan_down: the regions of the forms of three-tile producers - form 2: down3 ("fold_down"), [cout tile 6]; form 3:
+ * lo ("fold_lo"), [cout tile 4] - whose fragments are [cout tile][chunk 3][term 2][lane 64][8 fp16] (chunk 2: the third cout tile's
+ * four values of a lane in its low half, zeros above). */
+int pf_debug_plan_wide(int form, const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
                        long long *table, int table_ops);
 /* Host only, no device involved, nothing enqueued (tests): the plan of one pf_train_forward_backward of a training plan created now
  * from this blob - the workspace layout and the schedule of a step on B dense inputs of H x W with labels of out_h x out_w, under

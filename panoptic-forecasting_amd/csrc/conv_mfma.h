@@ -73,16 +73,17 @@ struct ConvArgs {
     //      is read last by a 1x1 conv R.  L's finished values, still in registers as the two terms R would read back, are multiplied by
     //      R's weights together with the centre pixels of R's other channels (read from their packed planes), so R's launch goes away.
     //      R's operands, the same for every form:
-    const float *fold_w;     // pack_conv_weights_fold(): R's A fragments, [cout tile][chunk 0: R's other channels, chunk 1: this launch's couts][term][64 lanes][8 fp16]
+    const float *fold_w;     // pack_conv_weights_fold(): R's A fragments, [cout tile][chunk 0: R's other channels, chunk 1 (, 2): this launch's couts][term][64 lanes][8 fp16]
     const float *fold_bias;  // R's bias, zero padded to whole tiles
     float fold_scale;        // R's acc_scale
     const float *fold_src;   // R's other channels: the packed tensor they live in, fold_c4 channel groups (term stride = fold_c4 planes), ...
     int fold_c4, fold_g0, fold_gn;   // ... its groups fold_g0 .. fold_g0 + fold_gn - 1 (fold_gn <= 8: one K = 32 chunk; 0: none)
     //      tail: R has no ReLU and at most 16 couts and goes to fp32 NCHW; it is linear in its input and the slice's only reader, so the
     //      slice is never stored
+    //      lo (three cout tiles): as tail with up to 64 couts of R; the slice is stored as by the plain form unless dst is nullptr
     float *tail_dst;         // R's destination [B, tail_ctotal, Hout, Wout] fp32, R's couts from channel tail_choff on
-    int fold_cout, tail_ctotal, tail_choff;   // fold_cout: R's couts, whatever the form (tail: <= 16, down: <= 64)
-    //      down: R has a ReLU, up to 64 couts and a 2x2 average pool behind it.  The slice is stored as by the plain form; R's pooled
+    int fold_cout, tail_ctotal, tail_choff;   // fold_cout: R's couts, whatever the form (tail: <= 16, down, lo: <= 64, down3: <= 96)
+    //      down (down3: three cout tiles, up to 96 couts of R): R has a ReLU, up to 64 couts and a 2x2 average pool behind it.  The slice is stored as by the plain form; R's pooled
     //      output is stored as packed pairs, or as fp32 where its readers want that
     float *down_dst;         // R's pooled destination: down_fmt = 1, the S4 layout [B][2 terms][down_c4][Hout / 2][Wout / 2][4] fp16 ...
     int down_c4, down_choff, down_limit;   // ... its channel groups, R's first channel in it and the dst_limit of R's stores;
@@ -318,24 +319,33 @@ int launch_conv_s4_share(const ConvArgs &a, int nt, int B, hipStream_t stream);
 int launch_conv_s4_add(const ConvArgs &a, int nt, int B, hipStream_t stream);
 inline int share_row0(int p_cout) { return (p_cout + 3) / 4 * 4; }   // a lane's four couts never straddle the two convs
 bool share_wanted(int p_cin, int p_cout, int c_cin, int c_cout, int h, int w, int B, int mode);
-// the fold forms: a 3x3 launch L of two cout tiles per workgroup on 8 x 32 tiles that also computes the 1x1 conv R reading its slice last
-// (ConvArgs::fold_..).  tail: R without ReLU, one cout tile, into fp32 (ConvArgs::tail_..); R's output is stored instead of L's slice.
-// down: R with ReLU, at most kDownTiles cout tiles, and the 2x2 average pool behind it (ConvArgs::down_..); L's slice is stored too.
-// tail_wanted / down_wanted (conv_select.cpp): mode = the plan's fold_final / fold_down option (0 never, 1 the measured rule, 2 wherever
-// the form exists); cin, cout = the 3x3 conv's, r_cout = R's
-enum FoldForm : int { FOLD_TAIL, FOLD_DOWN };
-constexpr int kFoldForms = 2;
+// the fold forms: a 3x3 launch L of two or three cout tiles - all in one workgroup - on 8 x 32 tiles that also computes the 1x1 conv R
+// reading its slice last (ConvArgs::fold_..).  tail: R without ReLU, one cout tile, into fp32 (ConvArgs::tail_..); R's output is stored
+// instead of L's slice.  down: R with ReLU, at most kDownTiles cout tiles, and the 2x2 average pool behind it (ConvArgs::down_..); L's
+// slice is stored too.  The wide forms, L of three cout tiles (<3, 32, 8, 1>): down3 = down with at most kWideTiles cout tiles of R;
+// lo: R = the low-resolution half of a commuted upsample + 1x1 conv (no bias, no ReLU, at most kLoTiles cout tiles) into the fp32
+// scratch its other half samples (ConvArgs::tail_..); L's slice is stored unless R is its only reader (ConvArgs::dst == nullptr).
+// tail_wanted / down_wanted / lo_wanted (conv_select.cpp): mode = the plan's fold_final / fold_down / fold_lo option (0 never, 1 the
+// measured rule, 2 wherever the form exists); cin, cout = the 3x3 conv's, r_cout = R's
+enum FoldForm : int { FOLD_TAIL, FOLD_DOWN, FOLD_DOWN3, FOLD_LO };
+constexpr int kFoldForms = 4;
 int launch_conv_s4_tail(const ConvArgs &a, int B, hipStream_t stream);
-int launch_conv_s4_down(const ConvArgs &a, int B, hipStream_t stream);
+int launch_conv_s4_down(const ConvArgs &a, int B, hipStream_t stream);   // (two or three cout tiles: by a.ntiles)
+int launch_conv_s4_lo(const ConvArgs &a, int B, hipStream_t stream);
 bool tail_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode);
 bool down_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode);
-constexpr int kTailChunks = 2;   // K = 32 chunks of R's A fragments: R's other channels (at most 8 groups), then the launch's 32 couts
+bool lo_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode);
+// K = 32 chunks of R's A fragments: R's other channels (at most 8 groups), then the launch's first 32 couts (a lane's 4 + 4 values of
+// cout tiles 0 and 1); the wide forms: a third chunk whose low half is the lane's 4 values of cout tile 2, zeros above them
+constexpr int kTailChunks = 2, kWideChunks = 3;
 constexpr int kDownTiles = 4;    // the down form's fragments hold this many cout tiles of R, zeros past R's couts
+constexpr int kWideTiles = 6, kLoTiles = 4;   // ... and the wide forms' (down3, lo)
 constexpr int kDownFragBytes = kDownTiles * kTailChunks * 2 * 64 * 16;
-inline size_t fold_packed_floats(int ntiles) { return (size_t)ntiles * kTailChunks * 2 * 64 * 4; }
+constexpr int kWideFragBytes = kWideTiles * kWideChunks * 2 * 64 * 16;   // (room for either wide form in the stage ring)
+inline size_t fold_packed_floats(int ntiles, int chunks = kTailChunks) { return (size_t)ntiles * chunks * 2 * 64 * 4; }
 // R's weights (OIHW, 1x1, already scaled by its 2^k) as [cout tile ntiles][chunk][term][64 lanes][8 fp16] in the folds' K order
 // (conv_ranges.h: order_tail, tail_channel)
-void pack_conv_weights_fold(const float *w_oihw, int cin, int cout, const KOrder &k, int ntiles, float *out);
+void pack_conv_weights_fold(const float *w_oihw, int cin, int cout, const KOrder &k, int ntiles, float *out, int chunks = kTailChunks);
 
 // conv_pair.hip: an odd HarDBlock layer P = conv3x3(S) computed inside its consumer C = conv3x3(P ++ S ++ others) (hardnet.py:177-194)
 struct PairArgs {

@@ -45,9 +45,12 @@ KOrder order_tail(const BlobSrc &src, int slice_choff, int slice_ch) {
 }
 
 int tail_channel(const KOrder &k, int chunk, int g, int e) {
-    const KRange &r = k.r[chunk];
-    // chunk 0: channel (e & 3) of group entry 2g + e / 4 (the range starts on a group); chunk 1: cout 4g + (e & 3) of cout tile e / 4
-    const int c = chunk == 0 ? 4 * (2 * g + e / 4) + (e & 3) : 16 * (e / 4) + 4 * g + (e & 3);
+    const KRange &r = k.r[chunk == 0 ? 0 : 1];
+    // chunk 0: channel (e & 3) of group entry 2g + e / 4 (the range starts on a group); chunk 1: cout 4g + (e & 3) of cout tile e / 4;
+    // chunk 2 (three-tile producers): cout 4g + e of cout tile 2 in its low half, nothing above: a lane's D fragments are 4 couts of one
+    // pixel per cout tile, so tiles 0 and 1 fill one 8-value K slice and tile 2 half of a second one - no cross-lane traffic
+    if (chunk == 2 && e >= 4) return -1;
+    const int c = chunk == 0 ? 4 * (2 * g + e / 4) + (e & 3) : chunk == 1 ? 16 * (e / 4) + 4 * g + (e & 3) : 32 + 4 * g + e;
     return c < r.ch ? r.cstart + c : -1;
 }
 

@@ -30,7 +30,8 @@ KOrder order_add(const BlobSrc *src, int n);
 KOrder order_tail(const BlobSrc &src, int slice_choff, int slice_ch);
 // ... and its K order: R's input channel at K position e (0..7) of lane group g in chunk 0 (the other channels: group entries 2g and
 // 2g + 1 of range 0, four channels each) or chunk 1 (the slice as the producing launch holds it: couts 4g .. 4g + 3 of its first cout
-// tile, then of its second); -1 = no channel (the weight is zero)
+// tile, then of its second) or, for a producer of three cout tiles, chunk 2 (couts 4g .. 4g + 3 of its third cout tile at e = 0..3,
+// nothing at e = 4..7); -1 = no channel (the weight is zero)
 int tail_channel(const KOrder &k, int chunk, int g, int e);
 
 // starts of n ranges of len[j] elements, each padded to whole units of `unit`, counted in units: out[j] for j <= kConvMaxSrc (out[n]

@@ -105,7 +105,8 @@ struct S4Cfg {
 #undef S4_KERNEL_NAME
 #undef S4_KERNEL_EPI
 // the fold forms (the launch also computes the 1x1 conv that reads its slice last: launch_conv_s4_tail / _down below), instantiated for
-// two cout tiles on 8 x 32 tiles without a K split at the plain form's launch bounds.  tail: the 1x1 conv's output is stored, the slice not
+// two cout tiles - down and lo: also, or only, for three - on 8 x 32 tiles without a K split at the plain form's launch bounds.  tail: the
+// 1x1 conv's output is stored, the slice not
 #define S4_KERNEL_NAME conv_s4_tail_kernel
 #define S4_KERNEL_EPI 3
 #include "conv_s4_kernel.inc"
@@ -114,6 +115,12 @@ struct S4Cfg {
 // down: the slice is stored, and the 2x2 average pool of the 1x1 conv's output
 #define S4_KERNEL_NAME conv_s4_down_kernel
 #define S4_KERNEL_EPI 4
+#include "conv_s4_kernel.inc"
+#undef S4_KERNEL_NAME
+#undef S4_KERNEL_EPI
+// lo (three cout tiles): the 1x1 conv is the low-resolution half of a commuted upsample + 1x1 conv; the slice is stored if anyone else reads it
+#define S4_KERNEL_NAME conv_s4_lo_kernel
+#define S4_KERNEL_EPI 5
 #include "conv_s4_kernel.inc"
 #undef S4_KERNEL_NAME
 #undef S4_KERNEL_EPI
@@ -131,10 +138,11 @@ struct S4Cfg {
 #undef S4_KERNEL_EPI
 #undef S4_KERNEL_WAVES
 
-// one launcher for the six forms of the 3x3 kernel (conv_s4_kernel.inc); the label = the symbol rocprofv3 reports (bench.py looks
+// one launcher for the seven forms of the 3x3 kernel (conv_s4_kernel.inc); the label = the symbol rocprofv3 reports (bench.py looks
 // its PMC bytes up by it)
-enum S4Form { S4_PLAIN, S4_BLOCKED, S4_SHARE, S4_ADD, S4_TAIL, S4_DOWN };
-constexpr const char *kS4FormName[] = {"conv_s4_kernel", "conv_s4_blocked_kernel", "conv_s4_share_kernel", "conv_s4_add_kernel", "conv_s4_tail_kernel", "conv_s4_down_kernel"};
+enum S4Form { S4_PLAIN, S4_BLOCKED, S4_SHARE, S4_ADD, S4_TAIL, S4_DOWN, S4_LO };
+constexpr const char *kS4FormName[] = {"conv_s4_kernel", "conv_s4_blocked_kernel", "conv_s4_share_kernel", "conv_s4_add_kernel", "conv_s4_tail_kernel", "conv_s4_down_kernel",
+                                       "conv_s4_lo_kernel"};
 template <S4Form FORM, int NT, int TW_, int TH_, int KS_>
 static constexpr auto s4_kernel() {   // (only the form asked for is instantiated)
     if constexpr (FORM == S4_PLAIN) return &conv_s4_kernel<NT, TW_, TH_, KS_>;
@@ -142,7 +150,8 @@ static constexpr auto s4_kernel() {   // (only the form asked for is instantiate
     else if constexpr (FORM == S4_SHARE) return &conv_s4_share_kernel<NT, TW_, TH_, KS_>;
     else if constexpr (FORM == S4_ADD) return &conv_s4_add_kernel<NT, TW_, TH_, KS_>;
     else if constexpr (FORM == S4_TAIL) return &conv_s4_tail_kernel<NT, TW_, TH_, KS_>;
-    else return &conv_s4_down_kernel<NT, TW_, TH_, KS_>;
+    else if constexpr (FORM == S4_DOWN) return &conv_s4_down_kernel<NT, TW_, TH_, KS_>;
+    else return &conv_s4_lo_kernel<NT, TW_, TH_, KS_>;
 }
 template <S4Form FORM, int NT, int TW_ = 32, int TH_ = 8, int KS_ = 1>
 static int launch_s4_form(const ConvArgs &a0, int B, hipStream_t s) {
@@ -164,10 +173,11 @@ static int launch_s4_form(const ConvArgs &a0, int B, hipStream_t s) {
     const int rows = FORM == S4_SHARE ? a.Cout + a.share_cout : a.Cout;
     const double sums = FORM == S4_SHARE || FORM == S4_ADD ? (double)(a.share_cout + 3) / 4 * 4 : 0.0;
     // folds: both convs' flops; read the 3x3 conv's input and the other channels of the 1x1 conv's.  tail writes the 1x1 conv's output only,
-    // down its slice and a quarter of the 1x1 conv's pixels
-    constexpr bool FOLD = FORM == S4_TAIL || FORM == S4_DOWN;
+    // down its slice and a quarter of the 1x1 conv's pixels, lo the 1x1 conv's output and the slice if it is stored
+    constexpr bool FOLD = FORM == S4_TAIL || FORM == S4_DOWN || FORM == S4_LO;
     const double flops = 2.0 * px * rows * a.Cin * 9 + (FOLD ? 2.0 * px * a.fold_cout * (4 * a.fold_gn + a.Cout) : 0.0);
-    const double stored = FORM == S4_TAIL ? (double)a.fold_cout : FORM == S4_DOWN ? a.Cout + 0.25 * a.fold_cout : a.Cout + sums;
+    const double stored = FORM == S4_TAIL ? (double)a.fold_cout : FORM == S4_DOWN ? a.Cout + 0.25 * a.fold_cout
+                          : FORM == S4_LO ? (a.dst ? a.Cout : 0) + (double)a.fold_cout : a.Cout + sums;
     const double extra = FOLD ? px * 4 * a.fold_gn + (double)a.fold_cout * (4 * a.fold_gn + a.Cout) : 0.0;
     ProfScope ps(s, label, flops, 4.0 * ((double)B * a.Cin * a.Hin * a.Win + px * stored + (double)rows * a.Cin * 9 + extra));
     hipLaunchKernelGGL(kernel, dim3(a.tilesX * a.tilesY, (a.ntiles + NT - 1) / NT, B), dim3(C::NTHR * C::KS), C::LDS_BYTES, s, a);
@@ -205,13 +215,13 @@ int launch_conv_s4_add(const ConvArgs &a, int nt, int B, hipStream_t s) {
 }
 #undef PF_S4_SHARE
 // the fold forms: a = the 3x3 conv's plain launch with R's operands (a.fold_..: fragments, bias and scale, the planes of R's other channels,
-// R's couts, at most max_cout) and the form's destination of R filled
-static int check_fold(const ConvArgs &a, const char *who, int max_cout) {
+// R's couts, at most max_cout) and the form's destination of R filled; ntiles: the cout tiles of the instantiation that will run
+static int check_fold(const ConvArgs &a, const char *who, int max_cout, int ntiles = 2) {
     if (!a.src_fmt || !a.dst_fmt) return fail(PF_EINVAL, "%s: sources and the slice in the S4 layout only", who);
     if ((a.Wout & 3) != 0 || a.Hin != a.Hout || a.Win != a.Wout) return fail(PF_EUNSUPPORTED, "%s: stride 1, width %% 4 == 0 only", who);
     if (a.pool || a.res || a.no_bias || a.kacc || a.share) return fail(PF_EUNSUPPORTED, "%s: no fused epilogue stages of its own", who);
     if (a.chunk_begin != 0 || a.chunk_end != a.nchunks) return fail(PF_EUNSUPPORTED, "%s: whole K range only", who);
-    if (a.ntiles != 2) return fail(PF_EUNSUPPORTED, "%s: %d cout tiles, the form is built for two", who, a.ntiles);
+    if (a.ntiles != ntiles) return fail(PF_EUNSUPPORTED, "%s: %d cout tiles, the form is built for %d", who, a.ntiles, ntiles);
     if (!a.fold_w || !a.fold_bias || a.fold_cout < 1 || a.fold_cout > max_cout || a.fold_gn < 0 || a.fold_gn > 8 || (a.fold_gn && !a.fold_src) ||
         (reinterpret_cast<uintptr_t>(a.fold_w) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.fold_bias) & 15) != 0 || a.fold_g0 < 0 ||
         a.fold_g0 + a.fold_gn > a.fold_c4)
@@ -225,13 +235,20 @@ int launch_conv_s4_tail(const ConvArgs &a, int B, hipStream_t s) {
     return launch_s4_form<S4_TAIL, 2>(a, B, s);
 }
 int launch_conv_s4_down(const ConvArgs &a, int B, hipStream_t s) {
-    if (int rc = check_fold(a, "conv_s4 down", 16 * kDownTiles)) return rc;
+    const bool wide = a.ntiles == 3;
+    if (int rc = check_fold(a, "conv_s4 down", 16 * (wide ? kWideTiles : kDownTiles), wide ? 3 : 2)) return rc;
     if (a.Hout < 2 || a.Wout < 2) return fail(PF_EUNSUPPORTED, "conv_s4 down: nothing to pool at %d x %d", a.Hout, a.Wout);
     const bool packed_ok = (a.down_choff & 1) == 0 && a.down_limit >= a.down_choff + a.fold_cout && a.down_limit <= 4 * a.down_c4 &&
                            a.down_limit <= (a.down_choff + a.fold_cout + 3) / 4 * 4;
     if (!a.down_dst || a.down_choff < 0 || (a.down_fmt ? !packed_ok : a.down_choff + a.fold_cout > a.down_ctotal))
         return fail(PF_EINVAL, "conv_s4 down: pooled destination of %d channels from %d (limit %d) in %d groups", a.fold_cout, a.down_choff, a.down_limit, a.down_c4);
-    return launch_s4_form<S4_DOWN, 2>(a, B, s);
+    return wide ? launch_s4_form<S4_DOWN, 3>(a, B, s) : launch_s4_form<S4_DOWN, 2>(a, B, s);
+}
+int launch_conv_s4_lo(const ConvArgs &a, int B, hipStream_t s) {
+    if (int rc = check_fold(a, "conv_s4 lo", 16 * kLoTiles, 3)) return rc;
+    if (!a.tail_dst || a.tail_choff < 0 || a.tail_choff + a.fold_cout > a.tail_ctotal)
+        return fail(PF_EINVAL, "conv_s4 lo: second conv of %d couts over %d groups", a.fold_cout, a.fold_gn);
+    return launch_s4_form<S4_LO, 3>(a, B, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -681,13 +698,13 @@ void pack_conv_weights_s4(const float *w, int cin, int cout, int ks, const KOrde
         }
 }
 
-// the fold forms' second conv R: [cout tile ntiles][chunk][term 2][lane 64][8 fp16], lane = (cout lane & 15 of the tile, lane group g),
+// the fold forms' second conv R: [cout tile ntiles][chunk (2, or 3 for a producer of three cout tiles)][term 2][lane 64][8 fp16], lane = (cout lane & 15 of the tile, lane group g),
 // value e = R's weight of the input channel tail_channel(k, chunk, g, e) (conv_ranges.cpp), zero where there is none and past R's couts
-void pack_conv_weights_fold(const float *w, int cin, int cout, const KOrder &k, int ntiles, float *out_f) {
+void pack_conv_weights_fold(const float *w, int cin, int cout, const KOrder &k, int ntiles, float *out_f, int chunks) {
     unsigned short *out = reinterpret_cast<unsigned short *>(out_f);
     size_t o = 0;
     for (int t = 0; t < ntiles; ++t)
-        for (int chunk = 0; chunk < kTailChunks; ++chunk)
+        for (int chunk = 0; chunk < chunks; ++chunk)
             for (int term = 0; term < 2; ++term)
                 for (int lane = 0; lane < 64; ++lane)
                     for (int e = 0; e < 8; ++e) {

@@ -13,6 +13,10 @@
 //                      down (8 x 32 tiles; ConvArgs::down_..): the slice IS stored, as by the plain epilogue; R has a ReLU and up to four
 //                      cout tiles, and its 2x2 average pool - two M-tile rows of a wave, lane pairs of a row - is stored (packed pairs or
 //                      fp32 NCHW)
+//                    The wide forms (NT = 3): a lane's 4 values of the third cout tile are the low half of one more K slice of R (chunk 2; R's
+//                    fragments hold zeros above them), three products more per M-tile and cout tile of R.  4 "down" again, R of up to six
+//                    cout tiles; 5 "lo": R is the low-resolution half of a commuted upsample + 1x1 conv - no bias, no ReLU, up to four
+//                    cout tiles, stored as fp32 NCHW like tail's (ConvArgs::tail_..) - and the slice is stored unless a.dst is nullptr
 template <int NT, int TW_, int TH_, int KS_>
 __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAME(ConvArgs a) {
     [[maybe_unused]] constexpr int KACC = S4_KERNEL_KACC;
@@ -331,7 +335,9 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
         // wait, between the stores below).  Both: the lane's B fragments of chunk 0 - lane group g supplies group entries 2g and 2g + 1
         // of R's other channels at the CENTRE pixel of every M-tile, straight from the packed planes (entries past the range, pixels
         // outside the image: the zero page)
-        constexpr bool FOLD = EPI == 3 || EPI == 4;
+        constexpr bool FOLD = EPI == 3 || EPI == 4 || EPI == 5;
+        constexpr bool RING = EPI == 4 || EPI == 5;   // R's fragments pass through the stage ring, [cout tile][chunk NT][term][lane]
+        [[maybe_unused]] constexpr int FRAG_BYTES = NT == 3 ? kWideFragBytes : kDownFragBytes, RTILES = NT == 3 ? kWideTiles : kDownTiles;
         [[maybe_unused]] s4_h8 tw_h[EPI == 3 ? 2 : 1], tw_m[EPI == 3 ? 2 : 1];
         [[maybe_unused]] s4_h4 to_h[FOLD ? C::MP : 1][2], to_m[FOLD ? C::MP : 1][2];
         [[maybe_unused]] s4_f32x4 tbias = s4_f32x4{0.f, 0.f, 0.f, 0.f};
@@ -345,21 +351,23 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
             }
             tbias = *reinterpret_cast<const s4_f32x4 *>(a.fold_bias + 4 * (lane >> 4));
         }
-        if constexpr (EPI == 4) {
-            static_assert(NT == 2 && TW_ == 32 && TH_ == 8 && KS_ == 1, "M-tiles m and m + 2 of a wave are two rows of the same 16 columns");
-            static_assert(kDownFragBytes + kDownTiles * 16 * sizeof(float) <= C::STAGES_BYTES, "R's fragments and bias live in the stage ring");
+        if constexpr (RING) {
+            static_assert((NT == 2 || NT == 3) && TW_ == 32 && TH_ == 8 && KS_ == 1, "M-tiles m and m + 2 of a wave are two rows of the same 16 columns");
+            static_assert(NT == 3 || EPI == 4, "lo is built for three cout tiles");
+            static_assert(FRAG_BYTES + RTILES * 16 * sizeof(float) <= C::STAGES_BYTES, "R's fragments and bias live in the stage ring");
             const int rt = (a.fold_cout + 15) >> 4;             // R's cout tiles (uniform)
             __syncthreads();                                    // every wave is done reading the ring
             const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void *)a.fold_w, 0, 0x7FFFFFFF, 0x00020000);
 #pragma unroll
-            for (int it = 0; it < kDownFragBytes / 16 / C::NTHR; ++it) {
-                const int p = it * C::NTHR + tid;               // 16-B piece; a cout tile is 256 of them
+            for (int it = 0; it < FRAG_BYTES / 16 / C::NTHR; ++it) {
+                const int p = it * C::NTHR + tid;               // 16-B piece; a cout tile is NT * 128 of them
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(frs, (s4_lds_ptr_t)(smem_all + (it * C::NTHR + wave * 64) * 16), 16,
-                                                         p < rt * 256 ? (unsigned)p * 16u : kS4Oob, 0, 0, 0);
+                                                         p < rt * (NT * 128) ? (unsigned)p * 16u : kS4Oob, 0, 0, 0);
             }
-            if (wave == 0) {                                    // R's bias: 64 values, zero past its tiles
+            if (wave < (RTILES * 16 + 63) / 64) {               // R's bias: 64 values per wave, zero past its tiles
                 const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void *)a.fold_bias, 0, 0x7FFFFFFF, 0x00020000);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, (s4_lds_ptr_t)(smem_all + kDownFragBytes), 4, lane < rt * 16 ? (unsigned)lane * 4u : kS4Oob,
+                const int bi = wave * 64 + lane;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, (s4_lds_ptr_t)(smem_all + FRAG_BYTES + wave * 256), 4, bi < rt * 16 ? (unsigned)bi * 4u : kS4Oob,
                                                          0, 0, 0);
             }
         }
@@ -384,7 +392,7 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
             }
         }
         __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0), expcnt / lgkmcnt untouched
-        if constexpr (EPI == 4) __syncthreads();   // every wave's pieces of R's fragments have landed
+        if constexpr (RING) __syncthreads();       // every wave's pieces of R's fragments have landed
         const int g = lane >> 4, px = lane & 15;
         const size_t hw = (size_t)a.Hout * a.Wout;
         const size_t term = (size_t)a.dst_c4 * hw * 8;
@@ -435,7 +443,18 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
             t = PF_MFMA_SPLIT(wh1, x1h, t);
             return t;
         };
-        [[maybe_unused]] s4_h8 dx0h[EPI == 4 ? C::MP : 1], dx0m[EPI == 4 ? C::MP : 1], dx1h[EPI == 4 ? C::MP : 1], dx1m[EPI == 4 ? C::MP : 1];
+        [[maybe_unused]] s4_h8 dx0h[RING ? C::MP : 1], dx0m[RING ? C::MP : 1], dx1h[RING ? C::MP : 1], dx1m[RING ? C::MP : 1];
+        [[maybe_unused]] s4_h4 dx2h[RING && NT == 3 ? C::MP : 1], dx2m[RING && NT == 3 ? C::MP : 1];   // chunk 2: the third cout tile's values
+        // ... and chunk 2's three products on top (wide forms)
+        [[maybe_unused]] auto fold_products2 = [](s4_f32x4 t, const s4_h8 &wh2, const s4_h8 &wm2, const s4_h4 &x2h, const s4_h4 &x2m) {
+            const s4_h4 zero4 = {0, 0, 0, 0};
+            const s4_h8 xh = s4_join(x2h, zero4), xm = s4_join(x2m, zero4);
+            t = PF_MFMA_SPLIT(wh2, xm, t);
+            t = PF_MFMA_SPLIT(wm2, xh, t);
+            t = PF_MFMA_SPLIT(wh2, xh, t);
+            return t;
+        };
+        [[maybe_unused]] const bool slice_stored = EPI != 5 || a.dst != nullptr;   // (uniform)
 #pragma unroll
         for (int m = 0; m < C::MP; ++m) {
             const int mt = wave * C::MP + m;
@@ -471,16 +490,16 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 }
                 continue;
             }
-            if constexpr (EPI == 4) {
+            if constexpr (RING) {
                 // the plain epilogue for every lane (rows past this launch's couts: zero weights, zero bias -> 0), the slice stored as the
                 // plain form stores it; the same values split into the two terms R would read back are K slice g of R's chunk 1, as in
                 // the tail form, and are kept for all four M-tiles next to chunk 0's.  (The finishing loop is the tail form's, written out
                 // twice: as a shared lambda, capturing or not, it changes the register allocation of both kernels, which sit at 114 and
                 // 117 of 128 registers.  Likewise the pooled store below is store_px written out for R's destination)
                 const bool in = oy < a.Hout && ox < a.Wout;
-                s4_h4 xh[2], xm[2];
+                s4_h4 xh[NT], xm[NT];
 #pragma unroll
-                for (int n = 0; n < 2; ++n) {
+                for (int n = 0; n < NT; ++n) {
                     const int co = (tile0 + n) * 16 + 4 * g;
                     s4_f32x4 v = acc[m][n];
                     const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(bias_lds + n * 16 + 4 * g);
@@ -489,9 +508,10 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                     const float vm = range_acc(vmax, v[0], v[1], v[2], v[3]);
                     vmax = in ? vm : vmax;
                     split_terms4(v, xh[n], xm[n]);
-                    if (in && co < a.Cout + 2) store_px(co, (size_t)oy * a.Wout + ox, v);
+                    if (in && co < a.Cout + 2 && slice_stored) store_px(co, (size_t)oy * a.Wout + ox, v);
                 }
                 dx1h[m] = s4_join(xh[0], xh[1]); dx1m[m] = s4_join(xm[0], xm[1]);
+                if constexpr (NT == 3) { dx2h[m] = xh[2]; dx2m[m] = xm[2]; }
                 fold_chunk0(m, dx0h[m], dx0m[m]);
                 continue;
             }
@@ -546,20 +566,25 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
             const bool pin = poy < Ho && pox < Wo;
             const size_t ppix = (size_t)poy * Wo + pox;
             const unsigned char *fw = smem_all + lane * 16;
-            const float *rbias = reinterpret_cast<const float *>(smem_all + kDownFragBytes);
+            const float *rbias = reinterpret_cast<const float *>(smem_all + FRAG_BYTES);
             float vmax2 = 0.f;
             auto swap_px = [](float x) {                         // the value of lane px ^ 1: quad_perm [1, 0, 3, 2]
                 return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
             };
 #pragma unroll 1
             for (int ct = 0; ct < rt; ++ct) {
-                const s4_h8 wh0 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 4 + 0) * 1024), wm0 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 4 + 1) * 1024);
-                const s4_h8 wh1 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 4 + 2) * 1024), wm1 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 4 + 3) * 1024);
+                const s4_h8 wh0 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 2 * NT + 0) * 1024), wm0 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 2 * NT + 1) * 1024);
+                const s4_h8 wh1 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 2 * NT + 2) * 1024), wm1 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 2 * NT + 3) * 1024);
+                [[maybe_unused]] s4_h8 wh2, wm2;
+                if constexpr (NT == 3) {
+                    wh2 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 6 + 4) * 1024); wm2 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 6 + 5) * 1024);
+                }
                 const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(rbias + ct * 16 + 4 * g);
                 s4_f32x4 v[C::MP];
 #pragma unroll
                 for (int m = 0; m < C::MP; ++m) {
-                    const s4_f32x4 t = fold_products(wh0, wm0, wh1, wm1, dx0h[m], dx0m[m], dx1h[m], dx1m[m]);
+                    s4_f32x4 t = fold_products(wh0, wm0, wh1, wm1, dx0h[m], dx0m[m], dx1h[m], dx1m[m]);
+                    if constexpr (NT == 3) t = fold_products2(t, wh2, wm2, dx2h[m], dx2m[m]);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[m][r] = fmaxf(t[r] * a.fold_scale + b4[r], 0.f);
                 }
@@ -603,6 +628,36 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 }
             }
             range_commit(a.down_status, a.down_slot, vmax2);
+        }
+        if constexpr (EPI == 5) {
+            // R, one cout tile at a time, as in the down form; its values go out as the tail form's do: fp32 NCHW, 2^-k and bias (the zero
+            // page: the other half of the commuted pair adds R's) and nothing else - the scratch is no operand of a split kernel
+            const int rt = (a.fold_cout + 15) >> 4;
+            const unsigned char *fw = smem_all + lane * 16;
+            const float *rbias = reinterpret_cast<const float *>(smem_all + FRAG_BYTES);
+#pragma unroll 1
+            for (int ct = 0; ct < rt; ++ct) {
+                const s4_h8 wh0 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 6 + 0) * 1024), wm0 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 6 + 1) * 1024);
+                const s4_h8 wh1 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 6 + 2) * 1024), wm1 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 6 + 3) * 1024);
+                const s4_h8 wh2 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 6 + 4) * 1024), wm2 = *reinterpret_cast<const s4_h8 *>(fw + (ct * 6 + 5) * 1024);
+                const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(rbias + ct * 16 + 4 * g);
+                const int co = ct * 16 + 4 * g;
+#pragma unroll
+                for (int m = 0; m < C::MP; ++m) {
+                    const int mt = wave * C::MP + m;
+                    const int oy = tileY * C::TH + mt / C::MTR;
+                    const int ox = tileX * C::TW + (mt % C::MTR) * 16 + px;
+                    s4_f32x4 t = fold_products(wh0, wm0, wh1, wm1, dx0h[m], dx0m[m], dx1h[m], dx1m[m]);
+                    t = fold_products2(t, wh2, wm2, dx2h[m], dx2m[m]);
+                    if (oy < a.Hout && ox < a.Wout) {
+                        const size_t pix = (size_t)oy * a.Wout + ox;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (co + r < a.fold_cout)
+                                a.tail_dst[((size_t)b * a.tail_ctotal + a.tail_choff + co + r) * hw + pix] = t[r] * a.fold_scale + b4[r];
+                    }
+                }
+            }
         }
         range_commit(a.status, a.range_slot, vmax);
     }

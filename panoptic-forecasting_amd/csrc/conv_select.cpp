@@ -126,13 +126,28 @@ bool tail_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode) {
 // option fold_down: 0 never, 2 wherever the form exists (tests, A/B runs), 1 (default): only the class of launches whose folded runs
 // MEASURED faster than the two launches in every run (MI355X, 1024x2048 network, same box, fold_down 0 / 2 alternated three times:
 // profiles/r09_experiments.md): 76 -> 28 -> 64 at 256x512, B = 4 .. 32 - 103 -> 79 us, 205-207 -> 164-165 us, 393-401 -> 317-324 us,
-// 781-790 -> 640-642 us: the folded launch takes the 3x3 launch's time and about half of the 1x1 launch's.  Other channel counts,
-// smaller launches (B = 1, 2) and launches of more than 4 194 304 pixels were not measured and keep their two launches
+// 781-790 -> 640-642 us: the folded launch takes the 3x3 launch's time and about half of the 1x1 launch's.  And the three-tile form
+// (profiles/r10_experiments.md, the same protocol): 108 -> 46 -> 96 at 128x256, B = 4 .. 32 - 67-69 -> 52-54 us, 108-109 -> 89-91 us,
+// 201-202 -> 164-166 us, 393-397 -> 315-322 us.  Other channel counts, smaller launches (B = 1, 2) and larger ones than the measured
+// were not measured and keep their two launches
 bool down_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode) {
     if (mode >= 2) return true;
     if (mode <= 0) return false;
     const long px = (long)B * h * w;
+    if (cin == 108 && cout == 46 && r_cout == 96) return px >= 131072 && px <= 1048576;
     return cin == 76 && cout == 28 && r_cout == 64 && px >= 524288 && px <= 4194304;
+}
+
+// conv_s4.hip lo (a three-tile 3x3 conv's launch also computes the low-resolution half of the commuted upsample + 1x1 conv behind it)
+// instead of the two launches?  mode = plan option fold_lo: 0 never, 2 wherever the form exists (tests, A/B runs), 1 (default): only the
+// class of launches whose folded runs MEASURED faster than the two launches in every run (MI355X, 1024x2048 network, same box, the
+// options 0 / 2 alternated three times: profiles/r10_experiments.md): 163 -> 46 -> 63 at 128x256, B = 4 .. 32 - 78-79 -> 64-65 us,
+// 138 -> 108-111 us, 243-252 -> 200-203 us, 475-477 -> 388-392 us: the slice is not stored either.  Nothing else was measured
+bool lo_wanted(int cin, int cout, int r_cout, int h, int w, int B, int mode) {
+    if (mode >= 2) return true;
+    if (mode <= 0) return false;
+    const long px = (long)B * h * w;
+    return cin == 163 && cout == 46 && r_cout == 63 && px >= 131072 && px <= 1048576;
 }
 
 ConvChoice choose_conv(int ks, int stride, int cin, int cout, int hout, int wout, int B, int need, int use_tuned) {

@@ -43,7 +43,7 @@ struct ConvPlan {
     // packed only by plans created with the form's option != 0: R's A fragments, an offset in floats into the form's region
     // (pf_plan::fold, whose first 64 floats are zeros: 0 = the op has none).  Regions of their own: the weight arena stays what it was
     // without the forms
-    size_t fold_off[pf::kFoldForms] = {0, 0};
+    size_t fold_off[pf::kFoldForms] = {0, 0, 0, 0};
 };
 
 // The switches a plan carries (include/pfhip.h documents each), with their defaults.  g_plan_opt is the process-wide set
@@ -64,6 +64,9 @@ struct PlanOptions {
     // nothing for the form; 1 = the form's rule in conv_select.cpp; 2 = wherever built).  The forms: kFolds below
     int fold_final = 1;        // tail: the 1x1 conv is small, goes to fp32 and is the slice's only reader; the slice is never stored
     int fold_down = 1;         // down: the 1x1 conv has a ReLU and a 2x2 average pool behind it, which the launch computes too; the slice is stored as ever
+                               // (3x3 convs of two cout tiles, and - down3 - of three)
+    int fold_lo = 1;           // lo: the 1x1 conv is the low-resolution half of a commuted upsample + 1x1 conv (fp32 scratch, no bias, no ReLU); the
+                               // 3x3 conv has three cout tiles; its slice is stored only if something else reads it
 };
 
 struct pf_plan {
@@ -79,7 +82,7 @@ struct pf_plan {
     } fold[pf::kFoldForms];
     PlanOptions opt;             // read only by forwards of this plan
     // formats of the last forward (pf_hardnet_tensor_read): 1 = S4, 0xFF = elided (never stored: conv_front.hip), 0xFE = its last
-    // slice elided (never stored: the tail form of conv_s4.hip)
+    // slice elided (never stored: the tail and lo forms of conv_s4.hip)
     mutable std::vector<uint8_t> last_fmt;
     // range normalisation (conv_mfma.h): tensor t, channel c is stored multiplied by chan_scale[t][c] (a power of two; 1 for
     // the network input, the head's input and every tensor no convolution reads); inv_scale_off[t] = offset in dev_weights
@@ -110,21 +113,28 @@ int layout(const pf_plan *p, int B, int H, int W, std::vector<Dims> &d, std::vec
 
 // ops i (P) and i + 1 (C) form a pair conv_pair.hip can run as one launch (plan_create.hip)
 bool is_conv_pair(const NetTable &t, size_t i);
-// What distinguishes the fold forms (FoldForm: conv_mfma.h).  Common to all: L = op i, a 3x3 stride-1 conv of two cout tiles; R = op i + 1,
-// a 1x1 stride-1 conv whose single range ends with L's slice
+// What distinguishes the fold forms (FoldForm: conv_mfma.h).  Common to all: L = op i, a 3x3 stride-1 conv of l_tiles cout tiles; R = the
+// 1x1 stride-1 conv behind it, whose range ends with L's slice: op i + 1 and its single range, or (up) op i + 2 and the range of the
+// upsample op i + 1 between them, whose whole output is R's first range of two (hardnet_plan.hip runs that range at the low resolution)
 struct FoldDesc {
+    int l_tiles;                    // L's cout tiles: two, or three (the wide forms: a third K chunk in R's fragments)
     bool r_relu;                    // R's ReLU
     int r_tiles;                    // R's cout tiles at most = the tiles its fragments are packed as
     bool pool;                      // op i + 2 is R's 2x2 average pool and the only reader of R's output
+    bool up;                        // op i + 1 is an upsample of the range, R = op i + 2 reads all of its output first
     bool other_readers;             // ops other than R may read L's slice (it is stored)
     int PlanOptions::*option;
     bool (*wanted)(int cin, int cout, int r_cout, int h, int w, int B, int mode);
+    constexpr int chunks() const { return l_tiles == 3 ? kWideChunks : kTailChunks; }
+    constexpr size_t r_at() const { return up ? 2 : 1; }   // R = op i + r_at()
 };
 constexpr FoldDesc kFolds[kFoldForms] = {
-    {false, 1, false, false, &PlanOptions::fold_final, tail_wanted},     // FOLD_TAIL
-    {true, kDownTiles, true, true, &PlanOptions::fold_down, down_wanted},   // FOLD_DOWN
+    {2, false, 1, false, false, false, &PlanOptions::fold_final, tail_wanted},      // FOLD_TAIL
+    {2, true, kDownTiles, true, false, true, &PlanOptions::fold_down, down_wanted},   // FOLD_DOWN
+    {3, true, kWideTiles, true, false, true, &PlanOptions::fold_down, down_wanted},   // FOLD_DOWN3
+    {3, false, kLoTiles, false, true, true, &PlanOptions::fold_lo, lo_wanted},        // FOLD_LO
 };
-// ops i (L) and i + 1 (R) have the form: conv_s4.hip can compute R in L's launch (plan_create.hip)
+// ops i (L) and i + r_at() (R) have the form: conv_s4.hip can compute R in L's launch (plan_create.hip)
 bool is_conv_fold(const NetTable &t, size_t i, FoldForm form);
 
 }  // namespace pf

@@ -17,7 +17,7 @@ namespace {
 // ---- A forward = build_schedule (host code only: every launch with all its arguments, each naming exactly one kernel) + the
 //      enqueue loop of run_net.  S_CONV: inside build_schedule only, a convolution whose kernel is picked once the formats are known
 enum StepKind : uint8_t {
-    S_RANGE_CHECK, S_STEM, S_STEM_FRONT, S_PAIR, S_CONV, S_CONV_S4, S_CONV_S4_SHARE, S_CONV_S4_ADD, S_CONV_S4_TAIL, S_CONV_S4_DOWN, S_CONV_GENERIC, S_CONV_SPLIT, S_CONV_SPLIT1, S_CONV_WAVE, S_CONV_DMA,
+    S_RANGE_CHECK, S_STEM, S_STEM_FRONT, S_PAIR, S_CONV, S_CONV_S4, S_CONV_S4_SHARE, S_CONV_S4_ADD, S_CONV_S4_TAIL, S_CONV_S4_DOWN, S_CONV_S4_LO, S_CONV_GENERIC, S_CONV_SPLIT, S_CONV_SPLIT1, S_CONV_WAVE, S_CONV_DMA,
     S_POOL, S_UPSAMPLE, S_HEAD };
 struct PlainArgs { const float *src; float *dst; int planes, hin, win, hout, wout; size_t n; unsigned *status, *slot; };   // pool, upsample, range check
 struct Step {
@@ -437,7 +437,8 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
 
     // ---- 6. the folds of conv_s4.hip, one form after the other: a 3x3 conv L and the 1x1 conv R that reads its slice last (is_conv_fold) as
     //      ONE launch.  Two adjacent plain conv_s4 steps - not part of a pair or a share / add step, whose kinds differ -, L on
-    //      <2, 32, 8, 1> into packed pairs; R's step goes away
+    //      <2, 32, 8, 1> or, the wide forms, <3, 32, 8, 1> into packed pairs; R's step goes away.  (up: R's step is the low-resolution half of
+    //      the commuted upsample + 1x1 conv, made under the upsample's op; the other half stays as it is)
     auto fold = [&](FoldForm form) {
         const FoldDesc &f = kFolds[form];
         const int mode = p->opt.*f.option;
@@ -445,25 +446,37 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
             Step &sl = steps[k];
             const Step &sr = steps[k + 1];
             const size_t i = (size_t)sl.op;
-            if (sl.kind != S_CONV_S4 || sr.kind != S_CONV_S4 || sl.ci != (int)i || sr.op != (int)i + 1 || sr.ci != (int)i + 1) continue;
+            if (sl.kind != S_CONV_S4 || sr.kind != S_CONV_S4 || sl.ci != (int)i || sr.op != (int)i + 1 || sr.ci != (int)(i + f.r_at())) continue;
             if (!p->conv[i].fold_off[form] || !is_conv_fold(p->net, i, form)) continue;
-            const BlobOp &L = p->net.ops[i], &R = p->net.ops[i + 1];
+            const BlobOp &L = p->net.ops[i], &R = p->net.ops[i + f.r_at()];
             ConvArgs &a = sl.u.c;
             const ConvArgs &r = sr.u.c;
             const S4Shape &sh = sl.dec.s4;
-            if (sh.NT != 2 || sh.TW != 32 || sh.TH != 8 || sh.KS != 1 || !a.dst_fmt || r.res || r.no_bias || a.Hout != r.Hout || a.Wout != r.Wout) continue;
+            if (sh.NT != f.l_tiles || sh.TW != 32 || sh.TH != 8 || sh.KS != 1 || !a.dst_fmt || r.res || a.Hout != r.Hout || a.Wout != r.Wout) continue;
             // tail: R without fused stages into fp32, nothing of it range-checked.  down: R with its pool fused and nothing else, into
-            // packed pairs or fp32
-            if (form == FOLD_TAIL ? (r.dst_fmt || r.status || r.pool) : (!r.pool || !r.relu)) continue;
+            // packed pairs or fp32.  lo: the first range of R alone, without bias or ReLU, into fp32
+            if (f.up ? (!r.no_bias || r.relu || r.src_begin != 0 || r.src_end != 1 || r.dst_fmt || r.status || r.pool)
+                     : r.no_bias || (form == FOLD_TAIL ? (r.dst_fmt || r.status || r.pool) : (!r.pool || !r.relu)))
+                continue;
             if (!f.wanted((int)L.cin, (int)L.cout, (int)R.cout, a.Hout, a.Wout, Bt, mode)) continue;
-            const KOrder ko = order_tail(R.src[0], (int)L.dst_choff, (int)L.cout);
+            const KOrder ko = order_tail(p->net.ops[i + 1].src[0], (int)L.dst_choff, (int)L.cout);
             a.fold_w = p->fold[form].dev + p->conv[i].fold_off[form];
-            a.fold_bias = r.bias; a.fold_scale = r.acc_scale; a.fold_cout = r.Cout;
+            a.fold_bias = f.up ? a.zero_page : r.bias; a.fold_scale = r.acc_scale; a.fold_cout = r.Cout;
             a.fold_src = a.dst; a.fold_c4 = a.dst_c4; a.fold_g0 = ko.r[0].choff / 4; a.fold_gn = ko.r[0].ch / 4;
-            if (form == FOLD_TAIL) {
+            if (form == FOLD_TAIL || form == FOLD_LO) {
                 a.tail_dst = r.dst; a.tail_ctotal = r.dst_ctotal; a.tail_choff = r.dst_choff;
-                sl.kind = S_CONV_S4_TAIL;
-                fmt[L.dst] = 0xFE;   // pf_hardnet_tensor_read refuses the tensor: its last slice is never stored
+                sl.kind = form == FOLD_TAIL ? S_CONV_S4_TAIL : S_CONV_S4_LO;
+                // lo: the slice is stored as ever unless the upsample is the only op that reads it
+                bool read_elsewhere = false;
+                for (size_t j = 0; j < p->net.ops.size(); ++j)
+                    for (uint32_t q = 0; q < p->net.ops[j].n_src && j != i + 1; ++q) {
+                        const BlobSrc &os = p->net.ops[j].src[q];
+                        read_elsewhere = read_elsewhere || (os.tensor == L.dst && os.choff < L.dst_choff + L.cout && os.choff + os.ch > L.dst_choff);
+                    }
+                if (form == FOLD_TAIL || !read_elsewhere) {
+                    fmt[L.dst] = 0xFE;   // pf_hardnet_tensor_read refuses the tensor: its last slice is never stored
+                    if (form == FOLD_LO) a.dst = nullptr;
+                }
             } else {   // L's slice is stored as ever
                 a.down_dst = r.dst; a.down_c4 = r.dst_c4; a.down_choff = r.dst_choff; a.down_limit = r.dst_limit;
                 a.down_fmt = r.dst_fmt; a.down_ctotal = r.dst_ctotal;
@@ -471,13 +484,12 @@ int build_schedule(const pf_plan *p, const StemArgs *stem, const float *dense_x,
                 sl.kind = S_CONV_S4_DOWN;
             }
             if (tags)
-                snprintf(sl.tag, sizeof(sl.tag), "%02zu+%02zu %s+%s %u->%u->%u %dx%d", i, i + 1, p->net.tensors[L.dst].name, p->net.tensors[R.dst].name, L.cin,
+                snprintf(sl.tag, sizeof(sl.tag), "%02zu+%02zu %s+%s %u->%u->%u %dx%d", i, i + f.r_at(), p->net.tensors[L.dst].name, p->net.tensors[R.dst].name, L.cin,
                          L.cout, R.cout, a.Hout, a.Wout);
             steps.erase(steps.begin() + (long)k + 1);
         }
     };
-    fold(FOLD_TAIL);
-    fold(FOLD_DOWN);
+    for (int form = 0; form < kFoldForms; ++form) fold((FoldForm)form);
     return PF_OK;
 }
 
@@ -517,6 +529,7 @@ int run_net(const pf_plan *p, const StemArgs *stem, const float *dense_x, int B,
             case S_CONV_S4_ADD: rc = launch_conv_s4_add(a, st.dec.s4_nt, B, s); break;
             case S_CONV_S4_TAIL: rc = launch_conv_s4_tail(a, B, s); break;
             case S_CONV_S4_DOWN: rc = launch_conv_s4_down(a, B, s); break;
+            case S_CONV_S4_LO: rc = launch_conv_s4_lo(a, B, s); break;
             case S_CONV_GENERIC: rc = launch_conv(a, p->conv[st.ci].tiling, B, s); break;
             case S_CONV_SPLIT: rc = launch_conv_split(a, ch.split_nt(), ch.split_wide(), B, s); break;
             case S_CONV_SPLIT1: rc = launch_conv_split1(a, ch.split_nt(), B, s); break;

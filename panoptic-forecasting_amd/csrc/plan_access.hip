@@ -115,7 +115,7 @@ extern "C" int pf_hardnet_tensor_read(const pf_plan *p, const char *name, int B,
     if (t < p->last_fmt.size() && p->last_fmt[t] == 0xFF)
         return fail(PF_EUNSUPPORTED, "tensor '%s' was elided by the fused front end (never stored); set plan option fuse_front = 0 to tap it", name);
     if (t < p->last_fmt.size() && p->last_fmt[t] == 0xFE)
-        return fail(PF_EUNSUPPORTED, "tensor '%s': its last slice was elided by the tail form of its producer (never stored); set plan option fold_final = 0 to tap it", name);
+        return fail(PF_EUNSUPPORTED, "tensor '%s': its last slice was elided by the tail or lo form of its producer (never stored); set plan options fold_final and fold_lo = 0 to tap it", name);
     if (t < p->last_fmt.size() && p->last_fmt[t]) {
         if ((rc = launch_s4_unpack(src, dst, B, c, h, w, (hipStream_t)stream))) return rc;
     } else {

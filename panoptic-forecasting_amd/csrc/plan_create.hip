@@ -38,6 +38,7 @@ const Option kOptions[] = {
     {"share_s", nullptr, &PlanOptions::share_s, nullptr, true, true, false},
     {"fold_final", nullptr, &PlanOptions::fold_final, nullptr, true, true, false},
     {"fold_down", nullptr, &PlanOptions::fold_down, nullptr, true, true, false},
+    {"fold_lo", nullptr, &PlanOptions::fold_lo, nullptr, true, true, false},
     {"profile_tag_ops", nullptr, &PlanOptions::profile_tag_ops, nullptr, true, true, false},
     {"table_batch", nullptr, &PlanOptions::table_batch, nullptr, false, true, true},
     {"normalize_ranges", nullptr, &PlanOptions::normalize_ranges, nullptr, true, false, false},
@@ -87,25 +88,34 @@ bool pf::is_conv_pair(const NetTable &t, size_t i) {
     return conv_pair_supports((int)C.cout, (int)P.cout);
 }
 
-// L = op i, a 3x3 stride-1 conv of two cout tiles; R = op i + 1, a 1x1 stride-1 conv whose single range ends with L's slice.  The slice and
-// R's range start on a 4-channel boundary, R's other channels (in front of the slice) are at most 8 groups - one K = 32 chunk of the fold
-// forms - and every one of them was written by an earlier op.  What the form adds (kFolds): R's ReLU and cout tiles; tail: R is the only op
-// that reads the slice, which is never stored; down: op i + 2 is the 2x2 average pool of R's output, its only reader, and other ops may
-// read the slice: it is stored.  (The formats of L's and R's destinations and which kernels they run on are known to the schedule
-// only: hardnet_plan.hip.)
+// L = op i, a 3x3 stride-1 conv of the form's two or three cout tiles; R = the 1x1 stride-1 conv behind it whose range ends with L's
+// slice: op i + 1 and its single range, or (FoldDesc::up) op i + 2 behind the upsample op i + 1 of that range, whose whole output is the
+// first of R's two ranges and read by nothing else.  The slice and the range start on a 4-channel boundary, the range's other channels
+// (in front of the slice) are at most 8 groups - one K = 32 chunk of the fold forms - and every one of them was written by an earlier
+// op.  What the form adds (kFolds): R's ReLU (up: R's own belongs to its other half) and cout tiles; tail: R is the only op that reads
+// the slice, which is never stored; down: op i + 2 is the 2x2 average pool of R's output, its only reader, and other ops may read the
+// slice: it is stored.  (The formats of L's and R's destinations and which kernels they run on are known to the schedule only:
+// hardnet_plan.hip.)
 bool pf::is_conv_fold(const NetTable &t, size_t i, FoldForm form) {
     const FoldDesc &f = kFolds[form];
-    if (i + (f.pool ? 2 : 1) >= t.ops.size()) return false;
-    const BlobOp &L = t.ops[i], &R = t.ops[i + 1];
-    if (L.kind != OP_CONV || R.kind != OP_CONV || L.k != 3 || L.stride != 1 || R.k != 1 || R.stride != 1 || (R.relu != 0) != f.r_relu || R.n_src != 1) return false;
-    if (L.cout <= 16 || L.cout > 32 || R.cout > 16u * f.r_tiles) return false;
+    const size_t ri = i + f.r_at();
+    if (ri + (f.pool ? 1 : 0) >= t.ops.size()) return false;
+    const BlobOp &L = t.ops[i], &R = t.ops[ri];
+    if (L.kind != OP_CONV || R.kind != OP_CONV || L.k != 3 || L.stride != 1 || R.k != 1 || R.stride != 1 || R.n_src != (f.up ? 2u : 1u)) return false;
+    if (!f.up && (R.relu != 0) != f.r_relu) return false;
+    if (L.cout <= 16u * (f.l_tiles - 1) || L.cout > 16u * f.l_tiles || R.cout > 16u * f.r_tiles) return false;
     if (f.pool) {
         const BlobOp &P = t.ops[i + 2];
         if (P.kind != OP_POOL || P.src[0].tensor != R.dst || R.dst_choff != 0 || R.cout != t.tensors[R.dst].channels) return false;
     }
+    if (f.up) {
+        const BlobOp &U = t.ops[i + 1];
+        if (U.kind != OP_UPSAMPLE || R.src[0].tensor != U.dst || R.src[0].choff != 0 || R.src[0].ch != t.tensors[U.dst].channels || U.src[0].ch != R.src[0].ch)
+            return false;
+    }
     for (uint32_t j = 0; j < L.n_src; ++j)
         if (L.src[j].choff & 1) return false;
-    const BlobSrc &rs = R.src[0];
+    const BlobSrc &rs = t.ops[i + 1].src[0];   // the range: R's, or the upsample's
     const uint32_t d0 = L.dst_choff, d1 = L.dst_choff + L.cout;
     if (rs.tensor != L.dst || (rs.choff & 3) || (d0 & 3) || rs.choff > d0 || rs.choff + rs.ch != d1 || d0 - rs.choff > 32) return false;
     std::vector<uint8_t> written(t.tensors[L.dst].channels, 0);
@@ -117,6 +127,7 @@ bool pf::is_conv_fold(const NetTable &t, size_t i, FoldForm form) {
             const BlobSrc &os = o.src[s];
             if (!f.other_readers && j != i + 1 && os.tensor == L.dst && os.choff < d1 && os.choff + os.ch > d0) return false;   // another reader of the slice
             if (f.pool && j != i + 2 && os.tensor == R.dst) return false;   // the pool is the only reader of R's output
+            if (f.up && j != ri && os.tensor == t.ops[i + 1].dst) return false;   // R is the only reader of the upsample's
         }
     }
     for (uint32_t c = rs.choff; c < d0; ++c)
@@ -346,12 +357,13 @@ void pack_share(const BlobOp &P, const float *wP, const BlobOp &o, const float *
     pack_conv_weights_s4(ws, (int)o.cin, (int)o.cout, 3, ko_b, 0, a.at(c.share_b_off));
 }
 
-// conv_s4.hip folds: o is the 3x3 conv, R the 1x1 conv behind it (is_conv_fold), wr = R's weights times R's 2^k (the power-of-two scale of
-// every source channel folded in by normalize_ranges, as for R's own packings).  Into the form's region of the plan
-void pack_fold(FoldForm form, const BlobOp &o, const BlobOp &R, const float *wr, Arena region, ConvPlan &c) {
-    const int tiles = kFolds[form].r_tiles;
-    c.fold_off[form] = region.take(fold_packed_floats(tiles), 16);
-    pack_conv_weights_fold(wr, (int)R.cin, (int)R.cout, order_tail(R.src[0], (int)o.dst_choff, (int)o.cout), tiles, region.at(c.fold_off[form]));
+// conv_s4.hip folds: o is the 3x3 conv, R the 1x1 conv behind it, `range` the range that ends with o's slice - R's, or the upsample's
+// between them, whose channels are R's first (is_conv_fold) -, wr = R's weights times R's 2^k (the power-of-two scale of every source
+// channel folded in by normalize_ranges, as for R's own packings).  Into the form's region of the plan, cout tile by cout tile
+void pack_fold(FoldForm form, const BlobOp &o, const BlobOp &R, const BlobSrc &range, const float *wr, Arena region, ConvPlan &c) {
+    const FoldDesc &f = kFolds[form];
+    c.fold_off[form] = region.take(fold_packed_floats(f.r_tiles, f.chunks()), 16);
+    pack_conv_weights_fold(wr, (int)R.cin, (int)R.cout, order_tail(range, (int)o.dst_choff, (int)o.cout), f.r_tiles, region.at(c.fold_off[form]), f.chunks());
 }
 
 void pack_front(const BlobOp &o, const float *ws, Arena &a, ConvPlan &c) {   // 3x3 stride 2, one range
@@ -414,8 +426,11 @@ int build_plan_weights(pf_plan &p, const float *wts, std::vector<float> &host) {
         if (i > 0 && is_conv_pair(p.net, i - 1)) pack_pair(ops[i - 1], wts + ops[i - 1].w_off, o, ws, a, c);
         if (i > 0 && p.opt.share_s && is_conv_pair(p.net, i - 1)) pack_share(ops[i - 1], wts + ops[i - 1].w_off, o, ws, a, c);
         if (o.k == 3 && o.stride == 2 && o.kind == OP_CONV && o.n_src == 1 && (o.src[0].choff & 3) == 0 && o.cout <= 32) pack_front(o, ws, a, c);
-        for (int f = 0; f < kFoldForms && i > 0; ++f)   // (o = the reader)
-            if (p.opt.*kFolds[f].option && is_conv_fold(p.net, i - 1, (FoldForm)f)) pack_fold((FoldForm)f, ops[i - 1], o, ws, Arena{p.fold[f].host}, p.conv[i - 1]);
+        for (int f = 0; f < kFoldForms; ++f) {   // (o = the reader)
+            const size_t back = kFolds[f].r_at();
+            if (i >= back && p.opt.*kFolds[f].option && is_conv_fold(p.net, i - back, (FoldForm)f))
+                pack_fold((FoldForm)f, ops[i - back], o, ops[i - back + 1].src[0], ws, Arena{p.fold[f].host}, p.conv[i - back]);
+        }
         if (o.stride == 1) pack_wave(o, w, src_ch, a, c);
         if (o.kind == OP_STEM) pack_stem(o, w, (int)p.net.hdr.n_cls, a, c);
         a.take(0, 64);
@@ -530,8 +545,8 @@ extern "C" int pf_debug_plan_arena(const void *blob, size_t bytes, int in_ch, in
     return PF_OK;
 }
 
-// a fold form's region of that plan - tail: option "fold_final", down: "fold_down" - (its first 64 floats are zeros) and per op of the
-// table its offset into it (0 = the op has no such packing)
+// a fold form's region of that plan - tail: option "fold_final", down and down3: "fold_down", lo: "fold_lo" - (its first 64 floats are
+// zeros) and per op of the table its offset into it (0 = the op has no such packing)
 static int debug_plan_fold(const char *who, FoldForm form, const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
                            long long *table, int table_ops) {
     pf_plan p;
@@ -550,6 +565,13 @@ extern "C" int pf_debug_plan_tail(const void *blob, size_t bytes, int in_ch, int
 extern "C" int pf_debug_plan_down(const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
                                   long long *table, int table_ops) {
     return debug_plan_fold("pf_debug_plan_down", FOLD_DOWN, blob, bytes, in_ch, n_cls, out, cap, n_floats, table, table_ops);
+}
+
+// form: 2 = down3, 3 = lo (the forms of three-tile producers)
+extern "C" int pf_debug_plan_wide(int form, const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
+                                  long long *table, int table_ops) {
+    if (form != FOLD_DOWN3 && form != FOLD_LO) return fail(PF_EINVAL, "pf_debug_plan_wide: form %d", form);
+    return debug_plan_fold("pf_debug_plan_wide", (FoldForm)form, blob, bytes, in_ch, n_cls, out, cap, n_floats, table, table_ops);
 }
 
 extern "C" void pf_hardnet_plan_destroy(pf_plan *p) {

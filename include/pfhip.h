@@ -728,6 +728,27 @@ int pf_debug_plan_down(const void *blob, size_t bytes, int in_ch, int n_cls, flo
  * four values of a lane in its low half, zeros above). */
 int pf_debug_plan_wide(int form, const void *blob, size_t bytes, int in_ch, int n_cls, float *out, size_t cap, size_t *n_floats,
                        long long *table, int table_ops);
+/* Host only, no device involved, nothing enqueued (tests): the schedule of one inference forward (csrc/hardnet_schedule.cpp) of the plan
+ * a blob would give now under the process-wide options and pf_debug_force_conv, with the per-plan option table_batch as given (0 = the
+ * batch itself), on B inputs of H x W.  stem_T > 0: the pf_bg_forward route, a fused stem over stem_T frames; stem_T = 0: the
+ * pf_hardnet_forward_dense route.  Weights, fold regions, workspace and the caller's buffers get made-up addresses that are far apart
+ * and the same on every call; the schedule computes with them and reads nothing through them.
+ * formats: per tensor of the table (*n_formats of them, copied while they fit) what pf_hardnet_tensor_read goes by: 0 = fp32 NCHW,
+ * 1 = packed pairs (S4), 0xFF = never stored (the tensor inside the fused front end), 0xFE = its last slice never stored (tail / lo).
+ * steps: *n_steps rows of 30 (copied while they fit), one per launch in order (S_STEM_FRONT: the stem and the front end):
+ * [0] kind (enum StepKind of csrc/hardnet_schedule.h), [1] first op of the table it executes, [2] op whose weights it runs (-1: not a
+ * convolution); [3..6] NT, TW, TH, KS of the conv_s4 instantiation it launches (0 unless kind is one of the S_CONV_S4.. kinds);
+ * [7..10] kind, p0, p1, p2 of the ConvChoice of the other convolution kinds (csrc/conv_mfma.h; else 0); [11] src_fmt, [12] dst_fmt,
+ * [13] tensor it stores (the fused pool's, the front end's output); [14] fused 2x2 pool, [15] samples a residual, [16] no bias (the
+ * low-resolution half of a commuted upsample + 1x1), [17] its own slice is not stored (lo); [18] cout tiles, [19] K chunks / rounds,
+ * [20] couts of the folded 1x1 conv, [21] couts of the share / add sums, [22] format of the down form's pooled tensor; [23], [24] the
+ * ranges [src_begin, src_end) of op [2] it accumulates (pair, add: the consumer's), [25..28] the tensor of each range of op [2] as the
+ * step reads it (-1: none); [29] arg_hash, a 64-bit FNV-1a of its labels and of the argument struct handed to its launcher - equal
+ * across calls and builds exactly when every argument is; no meaning of its own.  Columns [11], [12] and [14..28] are 0 / -1 unless the
+ * step is a convolution or a pair ([12]: or the front end); [13] is the op's destination for every other step. */
+int pf_debug_hardnet_schedule(const void *blob, size_t bytes, int in_ch, int n_cls, int B, int H, int W, int out_h, int out_w, int stem_T,
+                              int table_batch, unsigned char *formats, int cap_formats, int *n_formats, long long *steps, int cap_steps,
+                              int *n_steps);
 /* Host only, no device involved, nothing enqueued (tests): the plan of one pf_train_forward_backward of a training plan created now
  * from this blob - the workspace layout and the schedule of a step on B dense inputs of H x W with labels of out_h x out_w, under
  * the process-wide options as pf_train_create and a step read them, without pf_train_autotune; the addresses it is built against

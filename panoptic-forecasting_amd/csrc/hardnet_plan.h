@@ -1,5 +1,6 @@
-// The inference plan as its three translation units share it (not part of the ABI): plan_create.hip builds it (options, range
-// normalisation, weight arena), hardnet_plan.hip runs forwards of it, plan_access.hip answers questions about it.
+// The inference plan as its translation units share it (not part of the ABI): plan_create.hip builds it (options, range
+// normalisation, weight arena), hardnet_schedule.cpp turns a forward of it into a list of launches (hardnet_schedule.h),
+// hardnet_plan.hip enqueues that list, plan_access.hip answers questions about it.
 #pragma once
 #include <vector>
 
@@ -107,7 +108,7 @@ constexpr size_t kStatusBytes = PF_WS_STATUS_BYTES;
 constexpr int kStickyWord = PF_WS_STICKY_OFFSET / 4, kLiveWord = 2, kSlot0 = 16, kMaxSlots = ((int)(kStatusBytes / 4) - kSlot0) / 2;
 
 // the plan's geometry for a batch of B inputs of H x W: every tensor's size and workspace offset ((size_t)-1: not stored), and
-// the workspace size (plan_access.hip).  share_off (nullable): offset of the scratch region of the share / add launches - one region,
+// the workspace size (hardnet_schedule.cpp: the schedule's first pass).  share_off (nullable): offset of the scratch region of the share / add launches - one region,
 // sized for the largest pair the plan has packings for, reused by all of them; (size_t)-1 when the plan has none
 int layout(const pf_plan *p, int B, int H, int W, std::vector<Dims> &d, std::vector<size_t> &off, size_t &total, size_t *share_off = nullptr);
 
@@ -136,5 +137,8 @@ constexpr FoldDesc kFolds[kFoldForms] = {
 };
 // ops i (L) and i + r_at() (R) have the form: conv_s4.hip can compute R in L's launch (plan_create.hip)
 bool is_conv_fold(const NetTable &t, size_t i, FoldForm form);
+// Host only (the pf_debug_* entries; plan_create.hip): the plan this blob would give now under the process-wide options, nothing
+// uploaded - `host` = its weight arena, dev_weights and the fold regions' dev stay null.  who: the caller's name in error messages
+int debug_plan(const char *who, const void *blob, size_t bytes, int in_ch, int n_cls, const size_t *n_floats, pf_plan &p, std::vector<float> &host);
 
 }  // namespace pf

@@ -1,40 +1,10 @@
-// What a caller may ask about a plan or its workspace without running it: workspace size and layout, the status words, taps of
-// intermediate tensors, the flop count; and the packed-pair layout of a single tensor (pf_s4_pack / pf_s4_unpack).
-#include <algorithm>
+// What a caller may ask about a plan or its workspace without running it: workspace size (pf::layout: hardnet_schedule.cpp), the status
+// words, taps of intermediate tensors, the flop count; and the packed-pair layout of a single tensor (pf_s4_pack / pf_s4_unpack).
 #include <cstring>
 
 #include "hardnet_plan.h"
 
 using namespace pf;
-
-int pf::layout(const pf_plan *p, int B, int H, int W, std::vector<Dims> &d, std::vector<size_t> &off, size_t &total, size_t *share_off) {
-    int rc = propagate_dims(p->net, H, W, d);
-    if (rc) return rc;
-    off.assign(p->net.tensors.size(), (size_t)-1);
-    size_t cur = kStatusBytes;
-    const uint32_t input = p->net.ops[0].src[0].tensor;
-    for (size_t t = 0; t < p->net.tensors.size(); ++t) {
-        if (t == input || d[t].h == 0) continue;
-        off[t] = cur;
-        // channels padded to whole groups of 4: the same region holds the tensor as fp32 NCHW or in the S4 layout
-        cur += align_up((size_t)B * ((p->net.tensors[t].channels + 3) / 4 * 4) * d[t].h * d[t].w * sizeof(float), 256);
-    }
-    // the stored sums of the share / add launches: fp32 units of four of the consumer's channels per pixel, sized for the largest pair
-    // the plan's share_s option selects at this batch; the share launch's write and the add launch's read are adjacent steps of one
-    // stream, so every pair uses the same region
-    size_t share_bytes = 0;
-    const int Bt = p->opt.table_batch > 0 ? p->opt.table_batch : B;
-    for (size_t i = 1; i < p->net.ops.size(); ++i) {
-        const BlobOp &P = p->net.ops[i - 1], &C = p->net.ops[i];
-        const Dims &o = d[C.dst];
-        if (p->conv[i].share_a_off && p->opt.share_s && share_wanted((int)P.cin, (int)P.cout, (int)C.cin, (int)C.cout, o.h, o.w, Bt, p->opt.share_s))
-            share_bytes = std::max(share_bytes, (size_t)B * ((C.cout + 3) / 4 * 4) * o.h * o.w * sizeof(float));
-    }
-    if (share_off) *share_off = share_bytes ? cur : (size_t)-1;
-    cur += align_up(share_bytes, 256);
-    total = cur;
-    return PF_OK;
-}
 
 extern "C" int pf_hardnet_workspace(const pf_plan *p, int B, int H, int W, size_t *bytes) {
     if (!p || !bytes || B <= 0 || H <= 0 || W <= 0) return fail(PF_EINVAL, "pf_hardnet_workspace: bad argument");

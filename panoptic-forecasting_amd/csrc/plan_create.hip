@@ -466,6 +466,12 @@ int check_plan_ops(const NetTable &t, size_t n_w) {
     return PF_OK;
 }
 
+void count_readers(pf_plan &p) {
+    p.readers.assign(p.net.tensors.size(), 0);
+    for (const BlobOp &o : p.net.ops)
+        for (uint32_t j = 0; j < o.n_src; ++j) p.readers[o.src[j].tensor]++;
+}
+
 }  // namespace
 
 extern "C" int pf_hardnet_plan_create(const void *blob, size_t bytes, int in_ch, int n_cls, pf_plan **out) {
@@ -490,9 +496,7 @@ extern "C" int pf_hardnet_plan_create(const void *blob, size_t bytes, int in_ch,
         delete p;
         return rc;
     }
-    p->readers.assign(p->net.tensors.size(), 0);
-    for (const BlobOp &o : p->net.ops)
-        for (uint32_t j = 0; j < o.n_src; ++j) p->readers[o.src[j].tensor]++;
+    count_readers(*p);
     p->dev_floats = host.size();
     uint8_t lut[256];
     fill_lut(lut);
@@ -512,9 +516,9 @@ extern "C" int pf_hardnet_plan_create(const void *blob, size_t bytes, int in_ch,
     return PF_OK;
 }
 
-// Host only, no device involved (tests): the plan this blob would give now under the process-wide options, as far as
-// build_plan_weights takes it (`host` = its weight arena)
-static int debug_plan(const char *who, const void *blob, size_t bytes, int in_ch, int n_cls, const size_t *n_floats, pf_plan &p, std::vector<float> &host) {
+// Host only, no device involved (tests): the plan this blob would give now under the process-wide options, with everything but
+// the uploads (`host` = its weight arena; the fold regions stay in pf_plan::fold[].host)
+int pf::debug_plan(const char *who, const void *blob, size_t bytes, int in_ch, int n_cls, const size_t *n_floats, pf_plan &p, std::vector<float> &host) {
     if (!blob || !n_floats) return fail(PF_EINVAL, "%s: null argument", who);
     p.opt = g_plan_opt;
     int rc = parse_net_table(blob, bytes, in_ch, n_cls, p.net);
@@ -524,6 +528,7 @@ static int debug_plan(const char *who, const void *blob, size_t bytes, int in_ch
     const float *w0 = reinterpret_cast<const float *>((const char *)blob + p.net.hdr.weights_off);
     std::vector<float> wnorm(w0, w0 + n_w);
     normalize_ranges(&p, wnorm);
+    count_readers(p);
     return build_plan_weights(p, wnorm.data(), host);
 }
 

@@ -101,6 +101,7 @@ SIGNATURES = {
     'pf_debug_plan_down': (_i, [_vp, _sz, _i, _i, _vp, _sz, _c.POINTER(_sz), _vp, _i]),
     'pf_debug_plan_wide': (_i, [_i, _vp, _sz, _i, _i, _vp, _sz, _c.POINTER(_sz), _vp, _i]),
     'pf_debug_train_plan':(_i, [_vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _c.POINTER(_i), _vp, _i, _c.POINTER(_i), _vp]),
+    'pf_debug_hardnet_schedule': (_i, [_vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _c.POINTER(_i), _vp, _i, _c.POINTER(_i)]),
     'pf_debug_fg_schedule': (_i, [_i, _i, _i, _i, _vp, _i, _c.POINTER(_i), _vp, _vp, _i, _c.POINTER(_i)]),
     'pf_debug_label_scan_span': (_i, [_c.c_ulonglong, _c.c_ulonglong, _i, _i, _i, _i, _c.c_ulonglong, _i, _c.POINTER(_c.c_ulonglong)]),
     'pf_profile_enable': (_i, [_i]),

@@ -3,7 +3,8 @@ a 1x1 conv with ReLU of at most 96 couts and its 2x2 average pool - and lo - pla
 upsample + 1x1 conv pair whose low-resolution half the schedule runs on its own.  Which ops of a table plan creation matches, what it
 packs for them - into regions of their own (pf_debug_plan_wide), cout tile by cout tile, three K = 32 chunks per tile - and that the
 weight arena, the tail region and the down region stay byte for byte what they are.  (Which launches the schedule folds - K-split
-shapes, the add launch of a share pair, the rule - needs a plan on a device: tests/test_gpu_fold_wide.py.)"""
+shapes, the add launch of a share pair, the rule - is read from the step list, without a device: tests/test_hardnet_schedule_host.py;
+the numbers of the folded launches: tests/test_gpu_fold_wide.py.)"""
 import ctypes
 import json
 import os
@@ -194,7 +195,7 @@ def test_reader_with_two_ranges_is_refused(option):
 
 @pytest.mark.parametrize('form,kw', [(DOWN3, dict(skip=True)), (LO, dict(second_reader=True))], ids=['down3', 'lo'])
 def test_other_readers_of_the_slice_are_allowed(form, kw, option):
-    """(the schedule then stores the slice: tests/test_gpu_fold_wide.py)"""
+    """(the schedule then stores the slice: tests/test_hardnet_schedule_host.py, tests/test_gpu_fold_wide.py)"""
     option(OPTION[form], 2, 1)
     spec, P, _ = wide_net(form, torch.Generator().manual_seed(1), 16, 46, 63, **kw)
     blob = packing.pack_blob(None, spec.in_ch, spec.n_cls, spec=spec, params=P)

@@ -696,6 +696,16 @@ int pf_debug_force_conv(int kind, int p0, int p1, int p2);
  * tile it then asks for, and NT, TW, TH, KS of the conv_s4 instantiation that request runs (s4_resolve). */
 int pf_debug_conv_decision(int ks, int stride, int cin, int cout, int hout, int wout, int B, int need, int flags, int rounds,
                            int *out, int cap);
+/* Host only, no device involved, nothing enqueued (tests): the kernel the library runs for a fused stem (what = 0), an upsample + argmax
+ * head (1) or pf_seg_loss (2) of the given sizes (csrc/net_select.cpp), or the error code (and pf_last_error) with which the launch would be
+ * refused.  what 0: iargs[11] = T, n_cls, H, W, Hout, Wout, B, seg_is_i64, hop flags, dst_fmt (1 = packed pairs for the fused front end),
+ * whether the plan's re-packed stem weights are present; fargs[4] = depth mean, std, min_depth, max_depth.  what 1 and 2: iargs[6] = B, C,
+ * Hin, Win, Hout, Wout, no fargs.  label (label_cap bytes, nullable with 0) = the launch's profile label.  out[0..7] (cap >= 8): [0] the
+ * family (stem: 0 generic, 1 v3, 2 v4; head: 0 head_kernel, 1 head4_kernel, 2 head_col_kernel), [1..3] grid x, y, z, [4] lanes per
+ * workgroup, [5] dynamic LDS bytes, [6] stem: the flags in force, 1 = SEG64, 2 = HOP_D, 4 = HOP_LUT, 8 = FAST_DIV; head: C; loss: workgroups
+ * of the tile kernel (= partial sums), [7] stem: the row of the family's instantiation list; loss: the bytes of pf_seg_loss_workspace. */
+int pf_debug_net_choice(int what, const int *iargs, int n_iargs, const float *fargs, int n_fargs, char *label, size_t label_cap,
+                        long long *out, int cap);
 /* Host only, no device involved, nothing enqueued (tests): the range tables of one launch of a convolution that reads n_src (1..4) channel
  * ranges - range j = channels [choff[j], choff[j] + ch[j]) of a tensor of ctotal[j] channels - as the packers and the schedules take them from
  * csrc/conv_ranges.cpp; n_cases convolutions per call: choff, ch, ctotal = [n_cases][4] ints, out = [n_cases][39] (cap ints, >= 39 * n_cases).

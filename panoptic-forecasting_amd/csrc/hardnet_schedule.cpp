@@ -222,7 +222,7 @@ bool Sched::front_fits(size_t i, const StemArgs &a, const Dims &out) const {
            p->readers[o.dst] == 1 && p->readers[n1.dst] == 1 && n1.relu && p->conv[i + 1].s4_off && p->conv[i + 1].s4_rounds == 2 &&
            n2.kind == OP_CONV && n2.k == 3 && n2.stride == 2 && n2.n_src == 1 && n2.src[0].tensor == n1.dst && n2.src[0].choff == 0 &&
            n2.src[0].ch == n1.cout && p->conv[i + 2].front_off && (n2.dst_choff & 3) == 0 &&
-           conv_front_supports((int)o.cout, (int)n1.cout, (int)n2.cout, out.h, out.w, (int)p->net.tensors[n2.dst].channels) && stem_writes_s4(a) && !conv_forced();
+           conv_front_supports((int)o.cout, (int)n1.cout, (int)n2.cout, out.h, out.w, (int)p->net.tensors[n2.dst].channels) && stem_family(a) == STEM_V4 && !conv_forced();
 }
 
 // the fused one-hot stem of pf_bg_forward, alone or with the front end behind it (then i ends on the front end's second conv)

@@ -11,7 +11,7 @@
 //                       clamp masked values to [min_depth, max_depth].
 //
 // The fused forecast path (task bg_forecast) performs the same arithmetic in registers inside the stem kernel
-// (net_kernels.hip); these kernels exist so that the two-stage, file-based pipeline of the reference
+// (stem_kernels.hip); these kernels exist so that the two-stage, file-based pipeline of the reference
 // (scripts/bg/run_export_bg_val.sh -> data/bg/* -> task bg) runs on the device up to the PNG encoder, with 3 B per
 // pixel crossing PCIe instead of 5, and so that tests can prove "in-register hop == file hop" bit for bit.
 // One lane = 4 consecutive pixels (16-B depth loads, 8-B u16 stores, 4-B label stores).

@@ -94,6 +94,7 @@ SIGNATURES = {
     'pf_hardnet_plan_set_option': (_i, [_vp, _c.c_char_p, _i]),
     'pf_debug_force_conv': (_i, [_i, _i, _i, _i]),
     'pf_debug_conv_decision': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _i]),
+    'pf_debug_net_choice': (_i, [_i, _c.POINTER(_i), _i, _c.POINTER(_f), _i, _c.c_char_p, _sz, _c.POINTER(_c.c_longlong), _i]),
     'pf_debug_probe_read': (_i, [_c.POINTER(_c.c_longlong)]),
     'pf_debug_conv_ranges': (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _sz]),
     'pf_debug_plan_arena': (_i, [_vp, _sz, _i, _i, _vp, _sz, _c.POINTER(_sz), _vp, _i]),

@@ -20,7 +20,7 @@ and float64's own rounding.  A fused multiply-add removes one rounding and only 
 A pixel whose float64 top-1 / top-2 margin is <= 2*HEAD_BAR may legitimately get either label from an fp32 kernel (each of the two
 logits moves by at most HEAD_BAR); everywhere else the label is determined.  NEAR_TIE_CAP bounds the share of such pixels.
 
-LOSS_P, the per-pixel bound of the loss, derived.  The kernel (csrc/net_kernels.hip: seg_loss_tile_kernel) computes, on its fp32
+LOSS_P, the per-pixel bound of the loss, derived.  The kernel (csrc/head_kernels.hip: seg_loss_tile_kernel) computes, on its fp32
 logits v (each within HEAD_BAR of v64), nll = (best + logf(sum_c expf(v_c - best))) - v_label, converts to double and adds in
 double.  log-sum-exp moves by at most max_c |dv_c|, so the interpolation enters twice: 2*HEAD_BAR (once through the log-sum-exp,
 once through v_label).  On top, with the device functions' documented 1 ulp = 2*u relative error for expf and logf (HIP math API):
@@ -114,7 +114,7 @@ def seg_loss64(logits, labels, ho, wo, ignore, v=None):
 
 # ------------------------------------------------------------------------------------------------ the cases
 class HeadCase:
-    """C classes, Hin x Win -> Hout x Wout at batch B, and the kernel launch_head's conditions (csrc/net_kernels.hip) select"""
+    """C classes, Hin x Win -> Hout x Wout at batch B, and the kernel launch_head's conditions (csrc/net_select.cpp: choose_head) select"""
 
     def __init__(self, c, hin, win, ho, wo, kernel, note, b=2):
         self.c, self.hin, self.win, self.ho, self.wo, self.kernel, self.note, self.b = c, hin, win, ho, wo, kernel, note, b

@@ -1,4 +1,4 @@
-"""The float64 checker of the fused one-hot stem (csrc/net_kernels.hip: launch_stem), plain torch / NumPy on the CPU, and the
+"""The float64 checker of the fused one-hot stem (csrc/stem_kernels.hip: launch_stem), plain torch / NumPy on the CPU, and the
 cases tests/test_gpu_stem.py runs (tests/test_stem_host.py pins the checker itself without a GPU).
 
 stem_inputs() forms the [B, T*(n_cls+1), H, W] fp32 tensor the reference network feeds its first convolution (bg_model.py:53-69

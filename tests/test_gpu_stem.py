@@ -1,4 +1,4 @@
-"""The fused one-hot stem (csrc/net_kernels.hip: launch_stem) one kernel at a time against the float64 reference of
+"""The fused one-hot stem (csrc/stem_kernels.hip: launch_stem, the choice of csrc/net_select.cpp) one kernel at a time against the float64 reference of
 tests/stem_ref64.py (the bar and the cases are derived there and pinned on the CPU by tests/test_stem_host.py).
 
 The stem runs as the first op of a three-op network, stem -> fin (1x1, 16 -> n_cls, bias, no ReLU) -> head, through pf_bg_forward

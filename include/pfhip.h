@@ -718,6 +718,16 @@ int pf_debug_net_choice(int what, const int *iargs, int n_iargs, const float *fa
  * [37] chunk_begin, [38] chunk_end; what the chosen tables do not fill is 0. */
 int pf_debug_conv_ranges(int form, int ks, int kc, int pad, int n_src, int n_cases, const int *choff, const int *ch, const int *ctotal,
                          int src_begin, int src_end, int *out, size_t cap);
+/* Host only, no device involved (tests): one weight layout of csrc/conv_pack.cpp for the OIHW weights w [cout][cin][ks][ks] of a conv that
+ * reads n_src (1..4) ranges, range j = ch[j] channels from channel choff[j] of its tensor (sum of ch = cin).  *n_floats = what the layout's
+ * size function answers; PF_EINVAL (nothing written) when cap, the floats out has room for, is smaller.  layout: 0 = generic
+ * (pack_conv_weights under choose_tiling), 1 = tiled and 2 = rem, the last `rem` (1..16) couts (conv_dma; chunks of dma_kc(ks, stride)),
+ * 3 = wave, 4 = split (3x3), 5 = split1 (1x1), 6 = s4 (pad_sources: every range padded to whole rounds), 7 = fold: the 1x1 reader's
+ * fragments for `tiles` cout tiles and `chunks` (2 or 3) K chunks, range 0 = the reader's other channels (ch may be 0), range 1 = the
+ * slice right behind them, 8 / 9 = the `two` / `nine` stream of conv_pair's producer (3x3, one range).  The fp16-pair layouts (4..9) take
+ * the weights as given: already scaled.  Arguments a layout does not take are ignored. */
+int pf_debug_pack_conv(int layout, int ks, int stride, int cin, int cout, int n_src, const int *choff, const int *ch, int pad_sources,
+                       int rem, int tiles, int chunks, const float *w, float *out, size_t cap, size_t *n_floats);
 /* Host only, no device involved (tests): the weight arena a plan created now from this blob would upload - every packing of every
  * convolution under the process-wide options - copied to out when cap >= *n_floats, and per op of the table (table_ops rows of six
  * numbers, nullable): offset in floats and rounds of its packed-pair packing, offset and cout tiles of its share launch's packing,

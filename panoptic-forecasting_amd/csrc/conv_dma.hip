@@ -540,53 +540,4 @@ int launch_conv_dma(const ConvArgs &a, int ks, int stride, int B, hipStream_t s,
     return fail(PF_EUNSUPPORTED, "conv_dma: no kernel for ks=%d stride=%d wm=%d nt=%d", ks, stride, wm, nt);
 }
 
-// [chunk][kgroup][tap][rv/4][4 input channels][4 couts] (rv = 2: [chunk][kgroup][tap][2 couts][4 input channels]):
-// the last `rem` output channels, zero padded to rv = dma_rem_rv(rem)
-void pack_conv_weights_rem(const float *w, int cin, int cout, int rem, int ks, int kc, const int *src_ch, int n_src, float *out) {
-    const int ks2 = ks * ks, rv = dma_rem_rv(rem), co0 = cout - rem;
-    size_t o = 0;
-    int c0 = 0;
-    for (int j = 0; j < n_src; ++j) {
-        for (int lc = 0; lc * kc < src_ch[j]; ++lc)
-            for (int kg = 0; kg < kc / 4; ++kg)
-                for (int tap = 0; tap < ks2; ++tap) {
-                    if (rv == 2) {   // [cout][4 input channels]: read as two uniform 16-B rows
-                        for (int r = 0; r < 2; ++r)
-                            for (int c = 0; c < 4; ++c) {
-                                const int cl = lc * kc + kg * 4 + c;
-                                out[o++] = (r < rem && cl < src_ch[j]) ? w[((size_t)(co0 + r) * cin + c0 + cl) * ks2 + tap] : 0.f;
-                            }
-                        continue;
-                    }
-                    for (int g = 0; g < rv / 4; ++g)
-                        for (int c = 0; c < 4; ++c)
-                            for (int q = 0; q < 4; ++q) {
-                                const int cl = lc * kc + kg * 4 + c, r = g * 4 + q;
-                                out[o++] = (r < rem && cl < src_ch[j]) ? w[((size_t)(co0 + r) * cin + c0 + cl) * ks2 + tap] : 0.f;
-                            }
-                }
-        c0 += src_ch[j];
-    }
-}
-
-// per-tile packing: [cout tile][chunk][kgroup][tap][64 lanes]; K order = the input ranges in order, each padded to
-// whole chunks (zero weights), so a chunk never straddles two source tensors
-void pack_conv_weights_tiled(const float *w, int cin, int cout, int ks, int kc, const int *src_ch, int n_src, float *out) {
-    const int ks2 = ks * ks, ntiles = (cout + 15) / 16;
-    size_t o = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        int c0 = 0;
-        for (int j = 0; j < n_src; ++j) {
-            for (int lc = 0; lc * kc < src_ch[j]; ++lc)
-                for (int kg = 0; kg < kc / 4; ++kg)
-                    for (int tap = 0; tap < ks2; ++tap)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int co = t * 16 + (lane & 15), cl = lc * kc + kg * 4 + (lane >> 4);
-                            out[o++] = (co < cout && cl < src_ch[j]) ? w[((size_t)co * cin + c0 + cl) * ks2 + tap] : 0.f;
-                        }
-            c0 += src_ch[j];
-        }
-    }
-}
-
 }  // namespace pf

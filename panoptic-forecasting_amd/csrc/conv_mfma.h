@@ -5,6 +5,7 @@
 // "concatenation" (hardnet.py:225-230) as up to four channel ranges of earlier tensors instead of a
 // torch.cat copy.
 #pragma once
+#include "conv_pack.h"
 #include "pf_blob.h"
 #include "pf_common.h"
 
@@ -18,7 +19,7 @@ struct ConvArgs {
     int src_chunk0[kConvMaxSrc + 1]; // first K chunk of each range ([n_src] = nchunks) in the launched kernel's chunk
                                      // size; every range is padded to whole chunks: a chunk never straddles tensors
     int n_src;
-    const float *wpk;  // packed weights, see pack_conv_weights()
+    const float *wpk;  // packed weights in the layout of the launched kernel family (conv_pack.h)
     const float *bias; // [n_tiles_total*16], zero padded
     float *dst;        // [B, dst_ctotal, Hout, Wout]
     int dst_ctotal, dst_choff;
@@ -197,11 +198,7 @@ __device__ __forceinline__ void split_terms4(const V4 &v, split_x4 &hi, split_x4
     mid = split_x4{m0[0], m0[1], m1[0], m1[1]};
 }
 #define PF_MFMA_SPLIT(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-// host side (weight packing): fp32 -> fp16 bits, round to nearest even, subnormals kept; and back
-unsigned short split_host_f16(float x);
-float split_host_f32(unsigned short h);
-// 2^k with max|w| * 2^k in [2^14, 2^15) (1 for an all-zero tensor)
-float split_weight_scale(const float *w, size_t n);
+// (host side, weight packing: split_host_f16 / split_host_f32 / split_weight_scale of conv_pack.h)
 
 // Workgroup -> (pixel tile, cout group) for the grids dim3(pixel tiles, cout groups, B) of the fast kernels.  Workgroups are
 // dispatched in linear id order (x fastest) to the 8 XCDs round-robin, and each XCD has its own L2.  With a tile count that
@@ -234,13 +231,10 @@ struct ConvTiling {
     int nt;   // 16-wide cout tiles per workgroup
     int twt;  // workgroup tile width in 16-pixel units (4: 4x64, 2: 8x32, 1: 16x16 pixels)
     int cout_blocks, nchunks;
-    size_t packed_floats() const { return (size_t)cout_blocks * nchunks * (kc / 4) * ks * ks * nt * 64; }
+    size_t packed_floats() const;   // of pack_conv_weights (conv_pack.cpp)
 };
 
 ConvTiling choose_tiling(int ks, int stride, int cin, int cout, int wout_hint);
-// OIHW fp32 -> [cout_block][chunk][kgroup][tap][nt][64 lanes] with
-//   value = W[(cb*nt+t)*16 + (lane&15)][chunk*kc + kg*4 + (lane>>4)][tap]  (0 outside Cin/Cout)
-void pack_conv_weights(const float *w_oihw, int cin, int cout, const ConvTiling &t, float *out);
 // Enqueue one conv for a batch of B images (generic path: any stride/width).
 int launch_conv(const ConvArgs &a, const ConvTiling &t, int B, hipStream_t stream);
 
@@ -255,8 +249,6 @@ inline int dma_valu_split(int cout) {
     if (cout < 16) return 0;
     return cout % 16;
 }
-void pack_conv_weights_rem(const float *w_oihw, int cin, int cout, int rem, int ks, int kc, const int *src_ch, int n_src, float *out);
-void pack_conv_weights_tiled(const float *w_oihw, int cin, int cout, int ks, int kc, const int *src_ch, int n_src, float *out);
 // force_wm/force_nt > 0 override the cost model (tuning runs); model_B > 0: the cost model sees this batch size
 // instead of B (batch-invariant shape choice, plan option "table_batch")
 int launch_conv_dma(const ConvArgs &a, int ks, int stride, int B, hipStream_t stream, int force_wm = 0, int force_nt = 0, int model_B = 0);
@@ -267,9 +259,6 @@ bool conv_dma_supported(const ConvArgs &a, int ks, int stride, int B, int force_
 // output and a.nchunks = ceil(Cin / wave_kc(ks)).  Tile = mh rows x 16 pixels, nt cout tiles, wk-way K split.
 constexpr int wave_kc_ct(int ks) { return ks == 1 ? 32 : 8; }
 inline int wave_kc(int ks) { return wave_kc_ct(ks); }
-// src_ch[n_src]: channels of each input range (sum = cin); K order = ranges in order, each padded to whole chunks (conv_ranges.h)
-void pack_conv_weights_wave(const float *w_oihw, int cin, int cout, int ks, const int *src_ch, int n_src, float *out);
-size_t wave_packed_floats(const int *src_ch, int n_src, int cout, int ks);
 int launch_conv_wave(const ConvArgs &a, int ks, int mh, int nt, int wk, int B, hipStream_t stream);
 bool conv_wave_supported(const ConvArgs &a, int ks, int mh, int nt, int wk);   // launch_conv_wave has a kernel for this launch
 // LDS bytes of a conv_wave workgroup (WaveCfg in conv_wave.hip asserts the match)
@@ -281,27 +270,18 @@ constexpr size_t wave_lds_bytes(int ks, int mh, int nt, int wk) {
 }
 
 // split path (conv_split.hip; 3x3/s1, Wout % 4 == 0, no fused epilogue; two fp16 terms per operand, see split_terms2
-// above): a.wpk must point at pack_conv_weights_split() output, chunks of 8 channels; the packers take the weights
-// ALREADY multiplied by split_weight_scale() and a.acc_scale = 1 / that scale.
-size_t split_packed_floats(const int *src_ch, int n_src, int cout);
-void pack_conv_weights_split(const float *w_oihw, int cin, int cout, const int *src_ch, int n_src, float *out);
+// above): a.wpk must point at pack_conv_weights_split() output, chunks of 8 channels, a.acc_scale = 1 / the weights' scale.
 int launch_conv_split(const ConvArgs &a, int nt, int wide, int B, hipStream_t stream);
 bool conv_split_supported(const ConvArgs &a);   // launch_conv_split has a kernel for this launch
 // 1x1/s1 on the same scheme (chunks of 32 channels; pack_conv_weights_split1()); supports the fused epilogue stages
-size_t split1_packed_floats(const int *src_ch, int n_src, int cout);
-void pack_conv_weights_split1(const float *w_oihw, int cin, int cout, const int *src_ch, int n_src, float *out);
 int launch_conv_split1(const ConvArgs &a, int nt, int B, hipStream_t stream);
 bool conv_split1_supported(const ConvArgs &a, int nt);   // ... and launch_conv_split1 (a residual window must fit LDS)
 
 // S4 path (conv_s4.hip; stride 1, W % 4 == 0): every source in the packed-pair layout, tiles arrive by LDS-DMA, no split
-// phase.  K order = the group entries of the ranges in order, two entries (8 channels) per 3x3 round, eight (32 channels)
-// per 1x1 round; weights of channels a range does not own inside its first/last group are zero.
+// phase; a.wpk = pack_conv_weights_s4() output (conv_pack.h: its K order).
 struct S4Range { int choff, ch; };   // a source range in the channel numbering of its tensor
 struct KOrder;   // the ranges of a launch in K order with their starts in the conv's input-channel numbering (conv_ranges.h, which counts
                  // the entries and rounds): they may be packed in ANOTHER order than the one they are concatenated in (conv_pair.hip)
-// pad_sources: every range padded to whole rounds (convs that may be launched one range at a time)
-size_t s4_packed_floats(const KOrder &k, int cout, int ks, int pad_sources);
-void pack_conv_weights_s4(const float *w_oihw, int cin, int cout, int ks, const KOrder &k, int pad_sources, float *out);
 // the pixel tile a 3x3 launch is asked for: 8x32, 8x64, 16x32 on 8 waves, 8x32 with 2 / 4 wave groups splitting the rounds.  The values
 // are the ABI of pf_debug_force_conv(5, nt, tile, 0) and the contents of conv_s4_tuned.inc
 enum S4Tile : int { S4_8x32 = 0, S4_8x64 = 1, S4_16x32 = 2, S4_8x32_K2 = 3, S4_8x32_K4 = 4 };
@@ -343,9 +323,6 @@ constexpr int kWideTiles = 6, kLoTiles = 4;   // ... and the wide forms' (down3,
 constexpr int kDownFragBytes = kDownTiles * kTailChunks * 2 * 64 * 16;
 constexpr int kWideFragBytes = kWideTiles * kWideChunks * 2 * 64 * 16;   // (room for either wide form in the stage ring)
 inline size_t fold_packed_floats(int ntiles, int chunks = kTailChunks) { return (size_t)ntiles * chunks * 2 * 64 * 4; }
-// R's weights (OIHW, 1x1, already scaled by its 2^k) as [cout tile ntiles][chunk][term][64 lanes][8 fp16] in the folds' K order
-// (conv_ranges.h: order_tail, tail_channel)
-void pack_conv_weights_fold(const float *w_oihw, int cin, int cout, const KOrder &k, int ntiles, float *out, int chunks = kTailChunks);
 
 // conv_pair.hip: an odd HarDBlock layer P = conv3x3(S) computed inside its consumer C = conv3x3(P ++ S ++ others) (hardnet.py:177-194)
 struct PairArgs {
@@ -370,10 +347,6 @@ bool conv_pair_merged_supports(int c_cout, int p_cout);     // PairArgs::merged 
 // conv_select.cpp: run this pair as one conv_pair launch?  mode = the plan's fuse_pairs option (1: where measured / modelled faster, 2: wherever possible,
 // 3: wherever possible and never merged, 4: the merged pairs only)
 bool pair_wanted(int p_cin, int p_cout, int c_cin, int c_cout, int h, int w, int B, int mode);
-// P's weights (already scaled by 2^k like every split packing): `two` = [tile][round][2 blocks], `nine` = [tile][round][term][lane][4]
-size_t pair_p_two_floats(const S4Range &r, int cout);
-size_t pair_p_nine_floats(const S4Range &r, int cout);
-void pack_conv_weights_pair_p(const float *w_oihw, int cin, int cout, const S4Range &r, float *two, float *nine);
 int launch_conv_pair(const PairArgs &pa, int B, hipStream_t stream);
 // layout conversion (tests, tensor taps): fp32 NCHW <-> S4
 // status (nullable, device): PF_STATUS_RANGE is raised when an element exceeds what the pair represents (|x| > 65504)

@@ -160,21 +160,6 @@ ConvTiling choose_tiling(int ks, int stride, int cin, int cout, int /*wout_hint*
     return t;
 }
 
-void pack_conv_weights(const float *w, int cin, int cout, const ConvTiling &t, float *out) {
-    const int ks2 = t.ks * t.ks;
-    size_t o = 0;
-    for (int cb = 0; cb < t.cout_blocks; ++cb)
-        for (int ch = 0; ch < t.nchunks; ++ch)
-            for (int kg = 0; kg < t.kc / 4; ++kg)
-                for (int tap = 0; tap < ks2; ++tap)
-                    for (int n = 0; n < t.nt; ++n)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int co = (cb * t.nt + n) * 16 + (lane & 15);
-                            const int ci = ch * t.kc + kg * 4 + (lane >> 4);
-                            out[o++] = (co < cout && ci < cin) ? w[((size_t)co * cin + ci) * ks2 + tap] : 0.f;
-                        }
-}
-
 template <int KS, int STRIDE, int TWT, int NT, int KC>
 static int launch_cfg(const ConvArgs &a0, int B, int cout_blocks, hipStream_t s) {
     using C = ConvCfg<KS, STRIDE, TWT, NT, KC>;

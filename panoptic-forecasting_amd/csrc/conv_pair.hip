@@ -23,7 +23,6 @@
 // in the order [S, others, P] instead of [P, S, others]: same terms, another fp32 summation order.
 #include <cstring>
 #include <type_traits>
-#include <vector>
 
 #include "conv_s4.h"
 #include "pf_prof.h"
@@ -167,7 +166,7 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(PairArgs pa) {
         const int gy = Y0 - 1 + row, gx = X0 - 2 + 2 * cp;
         poffC[j] = (p < C::PIECES_C && gy >= 0 && gy < a.Hin && gx >= 0 && gx < a.Win) ? (unsigned)(gy * a.Win + gx) * 8u : kS4Oob;
     }
-    const int nblocksC = s4_blocks_total(nrounds), nblocksP = 2 * RS;   // P's stream: instr 0 / instr 1 of every round (pack_conv_weights_s4_two); its ninth tap: p_w9
+    const int nblocksC = s4_blocks_total(nrounds), nblocksP = 2 * RS;   // P's stream: instr 0 / instr 1 of every round (pack_conv_weights_pair_p's `two`); its ninth tap: p_w9
     // weight pieces: a cout tile's two instruction blocks of a round are 256 16-B pieces; threads 0..255 fetch tile 2i, threads
     // 256..511 tile 2i + 1 (uniform per wave)
     unsigned woffC[C::NWC], woffP;
@@ -557,39 +556,6 @@ bool conv_pair_supports(int c_cout, int p_cout) { return c_cout <= 48 && p_cout 
 // merged: built for two cout tiles of C, P in at most three lane groups of the second (the fourth plane entry is zero-filled by C's lanes)
 bool conv_pair_merged_supports(int c_cout, int p_cout) {
     return c_cout > 16 && c_cout <= 32 && p_cout <= 12 && (c_cout + 3) / 4 * 4 - 16 == 4 && p_cout + 20 <= 32;
-}
-
-// ---- host side: P's weights.  `two`: blocks of [term 2][lane 64][8 fp16] as in pack_conv_weights_s4 (lane = cout n = lane & 15,
-// lane group g = tap of instr 0 / 1, the lane's 8 values = 4 channels of the round's two entries), two per round and tile, no
-// collected-tap blocks.  `nine`: per round and tile [term 2][lane 64][4 fp16]: lane group 0 / 1 = tap (2,2) of the round's first /
-// second entry, groups 2 and 3 zero (K = 16 instruction)
-static int pair_p_rounds(const S4Range &r) { return (((r.choff + r.ch + 3) / 4 - r.choff / 4) + 1) / 2; }
-size_t pair_p_two_floats(const S4Range &r, int cout) { return (size_t)((cout + 15) / 16) * pair_p_rounds(r) * 2 * (2 * 64 * 4); }
-size_t pair_p_nine_floats(const S4Range &r, int cout) { return (size_t)((cout + 15) / 16) * pair_p_rounds(r) * (2 * 64 * 2); }
-void pack_conv_weights_pair_p(const float *w, int cin, int cout, const S4Range &r, float *two_f, float *nine_f) {
-    unsigned short *two = reinterpret_cast<unsigned short *>(two_f), *nine = reinterpret_cast<unsigned short *>(nine_f);
-    const int g0 = r.choff / 4, n_ent = (r.choff + r.ch + 3) / 4 - g0, rounds = (n_ent + 1) / 2, ntiles = (cout + 15) / 16;
-    // weight of (cout co, entry ent, channel slot e of the group, tap): zero outside the range / the layer
-    auto wv = [&](int co, int ent, int e, int tap) -> float {
-        const int ci = 4 * (g0 + ent) + e - r.choff;
-        if (co >= cout || ent >= n_ent || ci < 0 || ci >= r.ch) return 0.f;
-        return w[((size_t)co * cin + ci) * 9 + tap];
-    };
-    auto put = [&](unsigned short *&o, float v, int term) {
-        const unsigned short hi = split_host_f16(v);
-        *o++ = term == 0 ? hi : split_host_f16(v - split_host_f32(hi));
-    };
-    static const int tap3[2][4] = {{0, 1, 3, 4}, {6, 7, 2, 5}};   // conv_s4.hip
-    for (int t = 0; t < ntiles; ++t)
-        for (int rd = 0; rd < rounds; ++rd) {
-            for (int s = 0; s < 2; ++s)
-                for (int term = 0; term < 2; ++term)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) put(two, wv(t * 16 + (lane & 15), rd * 2 + e / 4, e & 3, tap3[s][lane >> 4]), term);
-            for (int term = 0; term < 2; ++term)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 4; ++e) put(nine, (lane >> 4) < 2 ? wv(t * 16 + (lane & 15), rd * 2 + (lane >> 4), e, 8) : 0.f, term);
-        }
 }
 
 // pa.c = the consumer with its sources in the K order [S, other ranges.., P's output] (pack_conv_weights_s4 with pad_sources = 1 in

@@ -29,9 +29,7 @@
 // instead of 12, no zero slots.  Wave w DMAs plane (term = w >> 1, entry = w & 1) of a stage.
 // 1x1: K = 32 = 8 group entries per instruction and round; 8x32-pixel tiles, the fused epilogue stages of conv_epilogue.h.
 #include <cstring>
-#include <vector>
 
-#include "conv_ranges.h"
 #include "conv_s4.h"
 #include "pf_prof.h"
 
@@ -634,85 +632,6 @@ int launch_conv_s4(const ConvArgs &a, int ks, const S4Shape &sh, int B, hipStrea
 #undef PF_S41
     }
     return fail(PF_EUNSUPPORTED, "conv_s4 %dx%d: shape <%d, %d, %d, %d> is not built", ks, ks, sh.NT, sh.TW, sh.TH, sh.KS);
-}
-
-// ------------------------------------------------------------------------------------------------ host side: weights
-size_t s4_packed_floats(const KOrder &k, int cout, int ks, int pad_sources) {
-    const int rounds = s4_rounds(k, ks, pad_sources);
-    return (size_t)((cout + 15) / 16) * (ks == 3 ? s4_blocks_total(rounds) : rounds) * 2 * 64 * 4;
-}
-
-// Blocks of [term 2][lane 64][8 fp16]; lane = (cout n = lane & 15, lane group g = lane >> 4), the lane's 8 values = 4 channels
-// of two group entries.  1x1: [tile][round], g = entry pair of the round.  3x3: [tile][per round: instr 0, instr 1, and after
-// every 4th (and the last) round the collected-tap block]; instr blocks: g = tap, entries of the round; collected block:
-// g = round 4q + g of its group of four, tap (2,2)
-void pack_conv_weights_s4(const float *w, int cin, int cout, int ks, const KOrder &k, int pad_sources, float *out_f) {
-    unsigned short *out = reinterpret_cast<unsigned short *>(out_f);
-    // entry -> (first conv input channel of the group's channel 0, may be negative; valid channel window)
-    std::vector<int> ent_c0, ent_lo, ent_hi;
-    const int per = s4_per_round(ks);
-    for (int j = 0; j < k.n; ++j) {
-        const KRange &r = k.r[j];
-        const int g0 = r.choff / 4;
-        for (int g = g0; g < g0 + s4_range_groups(r.choff, r.ch); ++g) {
-            ent_c0.push_back(r.cstart + 4 * g - r.choff);
-            ent_lo.push_back(r.cstart);
-            ent_hi.push_back(r.cstart + r.ch);
-        }
-        while (pad_sources && ent_c0.size() % per != 0) {   // padding entry: no valid channel
-            ent_c0.push_back(0);
-            ent_lo.push_back(0);
-            ent_hi.push_back(0);
-        }
-    }
-    const int n_ent = (int)ent_c0.size(), rounds = (n_ent + per - 1) / per, ntiles = (cout + 15) / 16;
-    size_t o = 0;
-    // one block: value of (lane, e) = weight of cout (t, lane & 15), entry ent_of(lane >> 4, e / 4), channel e & 3, tap tap_of(lane >> 4)
-    auto block = [&](int t, auto ent_of, auto tap_of) {
-        for (int term = 0; term < 2; ++term)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int co = t * 16 + (lane & 15), g = lane >> 4;
-                    const int ent = ent_of(g, e / 4), tap = tap_of(g);
-                    float v = 0.f;
-                    if (co < cout && tap >= 0 && ent >= 0 && ent < n_ent) {
-                        const int ci = ent_c0[ent] + (e & 3);
-                        if (ci >= ent_lo[ent] && ci < ent_hi[ent]) v = w[((size_t)co * cin + ci) * ks * ks + tap];
-                    }
-                    const unsigned short hi = split_host_f16(v);
-                    out[o++] = term == 0 ? hi : split_host_f16(v - split_host_f32(hi));
-                }
-    };
-    static const int tap3[2][4] = {{0, 1, 3, 4}, {6, 7, 2, 5}};   // ky * 3 + kx of (instr, lane group): see the kernel's aoff
-    for (int t = 0; t < ntiles; ++t)
-        for (int rd = 0; rd < rounds; ++rd) {
-            if (ks == 1) {
-                block(t, [&](int g, int h) { return rd * 8 + g * 2 + h; }, [](int) { return 0; });
-                continue;
-            }
-            for (int s = 0; s < 2; ++s) block(t, [&](int, int h) { return rd * 2 + h; }, [&](int g) { return tap3[s][g]; });
-            if ((rd & 3) == 3 || rd == rounds - 1) {
-                const int q = rd / 4;
-                block(t, [&](int g, int h) { return 4 * q + g < rounds ? (4 * q + g) * 2 + h : -1; }, [](int) { return 8; });
-            }
-        }
-}
-
-// the fold forms' second conv R: [cout tile ntiles][chunk (2, or 3 for a producer of three cout tiles)][term 2][lane 64][8 fp16], lane = (cout lane & 15 of the tile, lane group g),
-// value e = R's weight of the input channel tail_channel(k, chunk, g, e) (conv_ranges.cpp), zero where there is none and past R's couts
-void pack_conv_weights_fold(const float *w, int cin, int cout, const KOrder &k, int ntiles, float *out_f, int chunks) {
-    unsigned short *out = reinterpret_cast<unsigned short *>(out_f);
-    size_t o = 0;
-    for (int t = 0; t < ntiles; ++t)
-        for (int chunk = 0; chunk < chunks; ++chunk)
-            for (int term = 0; term < 2; ++term)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 8; ++e) {
-                        const int co = t * 16 + (lane & 15), ci = tail_channel(k, chunk, lane >> 4, e);
-                        const float v = (co < cout && ci >= 0 && ci < cin) ? w[(size_t)co * cin + ci] : 0.f;
-                        const unsigned short hi = split_host_f16(v);
-                        out[o++] = term == 0 ? hi : split_host_f16(v - split_host_f32(hi));
-                    }
 }
 
 // ------------------------------------------------------------------------------------------------ layout conversion

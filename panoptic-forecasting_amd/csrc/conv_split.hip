@@ -24,7 +24,6 @@
 #include <cstring>
 
 #include "conv_epilogue.h"
-#include "conv_ranges.h"
 #include "pf_prof.h"
 
 #ifndef PF_PROBE
@@ -563,101 +562,6 @@ int launch_conv_split1(const ConvArgs &a, int nt, int B, hipStream_t s) {
     PF_S1(1) PF_S1(2) PF_S1(3) PF_S1(4)
 #undef PF_S1
     return PF_EUNSUPPORTED;
-}
-
-// bytes as floats: [tile][chunk of 32 ch][term 2][lane 64][8 fp16]; lane = (cout n = lane & 15, k-group lane >> 4)
-size_t split1_packed_floats(const int *src_ch, int n_src, int cout) {
-    return (size_t)((cout + 15) / 16) * range_chunks(src_ch, n_src, 32) * 2 * 64 * 4;
-}
-
-void pack_conv_weights_split1(const float *w, int cin, int cout, const int *src_ch, int n_src, float *out_f) {
-    unsigned short *out = reinterpret_cast<unsigned short *>(out_f);
-    const int ntiles = (cout + 15) / 16;
-    size_t o = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        int c0 = 0;
-        for (int j = 0; j < n_src; ++j) {
-            for (int lc = 0; lc * 32 < src_ch[j]; ++lc)
-                for (int term = 0; term < 2; ++term)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = t * 16 + (lane & 15), cl = lc * 32 + (lane >> 4) * 8 + e;
-                            const float v = (co < cout && cl < src_ch[j]) ? w[(size_t)co * cin + c0 + cl] : 0.f;
-                            const unsigned short hi = split_host_f16(v);
-                            out[o++] = term == 0 ? hi : split_host_f16(v - split_host_f32(hi));
-                        }
-            c0 += src_ch[j];
-        }
-    }
-}
-
-// ---- host halves of the operand split (conv_mfma.h)
-unsigned short split_host_f16(float x) {
-    unsigned u;
-    memcpy(&u, &x, 4);
-    const unsigned short sign = (unsigned short)((u >> 16) & 0x8000u);
-    u &= 0x7fffffffu;
-    if (u >= 0x7f800000u) return (unsigned short)(sign | (u > 0x7f800000u ? 0x7e00u : 0x7c00u));   // nan / inf
-    if (u >= 0x477ff000u) return (unsigned short)(sign | 0x7c00u);                                  // >= 65520 rounds to inf
-    if (u < 0x38800000u) {   // below 2^-14: a multiple of the subnormal step 2^-24 (1024 steps = the smallest normal: same bits)
-        float f;
-        memcpy(&f, &u, 4);
-        return (unsigned short)(sign | (unsigned)nearbyintf(f * 16777216.0f));   // default rounding mode: nearest even
-    }
-    u -= 0x38000000u;                        // exponent bias 127 -> 15
-    u += 0xfffu + ((u >> 13) & 1u);          // nearest even on the 13 dropped bits (a carry moves into the exponent)
-    return (unsigned short)(sign | (u >> 13));
-}
-float split_host_f32(unsigned short h) {
-    const unsigned sign = (unsigned)(h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
-    float f;
-    if (e == 0) {
-        f = (float)m * (1.0f / 16777216.0f);
-        unsigned u;
-        memcpy(&u, &f, 4);
-        u |= sign;
-        memcpy(&f, &u, 4);
-        return f;
-    }
-    const unsigned u = sign | (e == 31 ? 0x7f800000u | (m << 13) : ((e + 112u) << 23) | (m << 13));
-    memcpy(&f, &u, 4);
-    return f;
-}
-float split_weight_scale(const float *w, size_t n) {
-    float mx = 0.f;
-    for (size_t i = 0; i < n; ++i) mx = fmaxf(mx, fabsf(w[i]));
-    if (!(mx > 0.f) || !std::isfinite(mx)) return 1.0f;
-    int e;
-    frexpf(mx, &e);                          // mx = f * 2^e, f in [0.5, 1)
-    return ldexpf(1.0f, 15 - e);             // mx * 2^(15 - e) in [2^14, 2^15)
-}
-
-// bytes as floats (the weight arena is a float array): [tile][chunk][step 3][term 2][lane 64][8 fp16] = 16 B per lane
-size_t split_packed_floats(const int *src_ch, int n_src, int cout) {
-    return (size_t)((cout + 15) / 16) * range_chunks(src_ch, n_src, 8) * 3 * 2 * 64 * 4;
-}
-
-void pack_conv_weights_split(const float *w, int cin, int cout, const int *src_ch, int n_src, float *out_f) {
-    unsigned short *out = reinterpret_cast<unsigned short *>(out_f);
-    const int ntiles = (cout + 15) / 16;
-    size_t o = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        int c0 = 0;
-        for (int j = 0; j < n_src; ++j) {
-            for (int lc = 0; lc * 8 < src_ch[j]; ++lc)
-                for (int s = 0; s < 3; ++s)
-                    for (int term = 0; term < 2; ++term)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 8; ++e) {
-                                const int co = t * 16 + (lane & 15), tap = 4 * s + (lane >> 4), cl = lc * 8 + e;
-                                float v = 0.f;
-                                if (co < cout && tap < 9 && cl < src_ch[j]) v = w[((size_t)co * cin + c0 + cl) * 9 + tap];
-                                const unsigned short hi = split_host_f16(v);
-                                out[o++] = term == 0 ? hi : split_host_f16(v - split_host_f32(hi));
-                            }
-            c0 += src_ch[j];
-        }
-    }
 }
 
 }  // namespace pf

@@ -15,7 +15,6 @@
 #include <cstring>
 
 #include "conv_epilogue.h"
-#include "conv_ranges.h"
 #include "pf_prof.h"
 
 #ifndef PF_PROBE
@@ -365,39 +364,6 @@ int launch_conv_wave(const ConvArgs &a, int ks, int mh, int nt, int wk, int B, h
 #undef PF_CASES_WK
 #undef PF_CASE
     return PF_EUNSUPPORTED;   // (unreachable: conv_wave_supported)
-}
-
-// fragment-order packing for direct L2 -> VGPR loads, per (cout tile, chunk): [quad][64 lanes][4] then the
-// remainder [64 lanes][NR];  value idx = q*4+e (or 4*NQ+e) -> (kg, tap) = (idx / ks2, idx % ks2):
-//   W[t*16 + (lane&15)][first channel of the chunk + kg*4 + (lane>>4)][tap]
-// K order: the input ranges in order, each padded to whole chunks (zeros), so a chunk lies inside one tensor.
-void pack_conv_weights_wave(const float *w, int cin, int cout, int ks, const int *src_ch, int n_src, float *out) {
-    const int kc = wave_kc(ks), ks2 = ks * ks, nv = (kc / 4) * ks2, nq = nv / 4, nr = nv % 4;
-    const int ntiles = (cout + 15) / 16;
-    size_t o = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        int c0 = 0;
-        for (int j = 0; j < n_src; ++j) {
-            for (int lc = 0; lc * kc < src_ch[j]; ++lc) {
-                auto val = [&](int idx, int lane) {
-                    const int kg = idx / ks2, tap = idx % ks2;
-                    const int co = t * 16 + (lane & 15), cl = lc * kc + kg * 4 + (lane >> 4);
-                    return (co < cout && cl < src_ch[j]) ? w[((size_t)co * cin + c0 + cl) * ks2 + tap] : 0.f;
-                };
-                for (int q = 0; q < nq; ++q)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 4; ++e) out[o++] = val(q * 4 + e, lane);
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < nr; ++e) out[o++] = val(nq * 4 + e, lane);
-            }
-            c0 += src_ch[j];
-        }
-    }
-}
-
-size_t wave_packed_floats(const int *src_ch, int n_src, int cout, int ks) {
-    const int kc = wave_kc(ks), nv = (kc / 4) * ks * ks;
-    return (size_t)((cout + 15) / 16) * range_chunks(src_ch, n_src, kc) * ((nv / 4) * 256 + (nv % 4) * 64);
 }
 
 }  // namespace pf

@@ -266,7 +266,7 @@ void pack_generic(const BlobOp &o, const float *w, const float *bias, Arena &a, 
 void pack_dma(const BlobOp &o, const float *w, const int *src_ch, Arena &a, ConvPlan &c) {
     const int kc = dma_kc((int)o.k, (int)o.stride);
     c.tiled_chunks = range_chunks(src_ch, (int)o.n_src, kc);
-    c.tiled_off = a.take((size_t)((o.cout + 15) / 16) * c.tiled_chunks * (kc / 4) * o.k * o.k * 64);
+    c.tiled_off = a.take(tiled_packed_floats(src_ch, (int)o.n_src, (int)o.cout, (int)o.k, (int)o.stride));
     pack_conv_weights_tiled(w, (int)o.cin, (int)o.cout, (int)o.k, kc, src_ch, (int)o.n_src, a.at(c.tiled_off));
     // trailing couts that may run on the vector ALU beside the MFMA tiles (conv_dma.hip): groups of at most valu_max (beyond
     // that the padded MFMA tile measured faster)
@@ -274,7 +274,7 @@ void pack_dma(const BlobOp &o, const float *w, const int *src_ch, Arena &a, Conv
     const int split = (o.k == 3 && o.stride == 1) ? dma_valu_split((int)o.cout) : 0;
     if (split > 0 && split <= valu_max) {
         c.rem_count = split;
-        c.rem_off = a.take((size_t)c.tiled_chunks * (kc / 4) * 9 * dma_rem_rv(split) * 4, 4);
+        c.rem_off = a.take(rem_packed_floats(src_ch, (int)o.n_src, split, 3, kc), 4);
         pack_conv_weights_rem(w, (int)o.cin, (int)o.cout, split, 3, kc, src_ch, (int)o.n_src, a.at(c.rem_off));
     }
 }

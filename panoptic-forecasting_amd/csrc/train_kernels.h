@@ -18,8 +18,6 @@ namespace pf {
 // ---- train_pack.hip
 int launch_onehot_dense(const void *seg, int seg_i64, const float *depth, const uint8_t *mask, float mean, float stdv, int B, int T,
                         int n_cls, int H, int W, float *x, hipStream_t s);
-// floats of one conv's weights in the per-tile order of the LDS-DMA kernels (conv_dma.hip); src_ch[n_src] = its input ranges
-size_t tiled_packed_floats(const int *src_ch, int n_src, int cout, int ks, int stride);
 constexpr int kPackBatch = 24;
 struct PackJob {
     long long w_off, out_off, total;   // floats: weights inside theta, packing inside the arena, packed size

@@ -30,11 +30,7 @@ int launch_onehot_dense(const void *seg, int seg_i64, const float *depth, const 
 }
 
 // ------------------------------------------------------------------------------------------------ weight packing on the device
-size_t tiled_packed_floats(const int *src_ch, int n_src, int cout, int ks, int stride) {
-    return (size_t)((cout + 15) / 16) * range_chunks(src_ch, n_src, dma_kc(ks, stride)) * (dma_kc(ks, stride) / 4) * ks * ks * 64;
-}
-
-// OIHW -> the per-tile order of the LDS-DMA kernels (conv_dma.hip::pack_conv_weights_tiled: [cout tile][chunk][kgroup][tap][64 lanes],
+// OIHW -> the per-tile order of the LDS-DMA kernels (conv_pack.cpp: pack_conv_weights_tiled, [cout tile][chunk][kgroup][tap][64 lanes],
 // K order = the input ranges in order, each padded to whole chunks of kc channels).
 // transpose_flip = 0: forward weights.  transpose_flip = 1: the backward-data convolution of input range [c0, c0+ch):
 //   Wd[co_d][ci_d][tap] = W[ci_d][c0 + co_d][ks2-1-tap]   (ci_d runs over the forward cout)

@@ -4,7 +4,7 @@
 // same functions the inference path runs on conv_s4 (every fp32 operand as two round-to-nearest fp16 terms, three products on
 // v_mfma_f32_16x16x32_f16, fp32 accumulation: conv_mfma.h).  What training adds:
 //   * weights change every step: s4_pack_weights_dev_kernel packs them ON THE DEVICE from the fp32 arena (theta) into the block layout
-//     pack_conv_weights_s4 (conv_s4.hip) produces on the host (checked end to end against float64 autograd:
+//     pack_conv_weights_s4 (conv_pack.cpp) produces on the host (checked end to end against float64 autograd:
 //     tests/test_gpu_train.py::test_mini_network_forward_on_packed_pairs_vs_autograd) - with ONE fixed scale 2^12 instead of a per-conv 2^k
 //     from max|w| (the kernel's 2^-k is a launch argument: a data-dependent scale would need the host to wait for the device).
 //     |w| >= 16 does not fit fp16 then: the kernel stores NaN for such a weight, the loss of the step is NaN - loud, never a silently
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void s4_pack_weights_dev_kernel(const float *t
     __shared__ short ent_c0[kS4MaxEnt], ent_lo[kS4MaxEnt], ent_hi[kS4MaxEnt];
     __shared__ int n_ent_s;
     const int per = jb.ks == 3 ? 2 : 8;
-    if (threadIdx.x == 0) {      // the entry table of pack_conv_weights_s4_ex (conv_s4.hip), a few dozen entries
+    if (threadIdx.x == 0) {      // the entry table of pack_conv_weights_s4 (conv_pack.cpp), a few dozen entries
         int n = 0, c0 = 0;
         for (int s = 0; s < jb.n_src; ++s) {
             const int g0 = jb.choff[s] / 4, g1 = (jb.choff[s] + jb.ch[s] + 3) / 4;
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void s4_pack_weights_dev_kernel(const float *t
         const int ninstr = 2 * (nrem < 4 ? nrem : 4);
         if (r9 < ninstr) {
             const int rd = 4 * q + (r9 >> 1), s = r9 & 1;
-            const int tap3[2][4] = {{0, 1, 3, 4}, {6, 7, 2, 5}};                   // ky * 3 + kx of (instr, lane group): conv_s4.hip
+            const int tap3[2][4] = {{0, 1, 3, 4}, {6, 7, 2, 5}};                   // ky * 3 + kx of (instr, lane group): conv_pack.cpp
             ent[0] = rd * 2;
             ent[1] = rd * 2 + 1;
             tap = tap3[s][g];

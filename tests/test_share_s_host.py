@@ -12,7 +12,7 @@ from conftest import GOLDEN
 from panoptic_forecasting_amd import lib as pflib
 from panoptic_forecasting_amd import packing, synth
 
-TAP3 = ((0, 1, 3, 4), (6, 7, 2, 5))   # ky * 3 + kx of (instruction, lane group): csrc/conv_s4.hip, pack_conv_weights_s4_ex
+TAP3 = ((0, 1, 3, 4), (6, 7, 2, 5))   # ky * 3 + kx of (instruction, lane group): csrc/conv_pack.cpp, pack_conv_weights_s4
 
 
 @pytest.fixture
@@ -43,7 +43,7 @@ def plan_arena(blob, in_ch, n_cls, n_ops):
 
 
 def unpack_s4_3x3(arena, off, cout, cin, ranges, cstart):
-    """inverse of pack_conv_weights_s4_ex for a 3x3 conv without padded ranges: [cout][cin][9] float64 of hi + mid.  ranges = (choff, ch)
+    """inverse of pack_conv_weights_s4 for a 3x3 conv without padded ranges: [cout][cin][9] float64 of hi + mid.  ranges = (choff, ch)
     of every source range in the packed order, cstart = its first channel in the conv's input numbering"""
     ent = []                      # (conv channel of the group's channel 0, lo, hi)
     for (choff, ch), c0 in zip(ranges, cstart):

@@ -812,6 +812,12 @@ int pf_debug_label_scan_span(unsigned long long addr_a, unsigned long long addr_
 /* Instrumented builds only (make libpfhip_probe.so, env PF_PROBE=1): the 64 in-kernel timestamps (shader clock)
  * written by workgroup 0 / wave 0 of the last conv_wave launch; PF_EINVAL when nothing was recorded. */
 int pf_debug_probe_read(long long *host64);
+/* The fill of every destination tile's source-block list after the last pf_warp_splat call that used the workspace `ws` with these
+ * dimensions and flags: host_counts[B][G][32x128 destination tiles, row-major], G = T with PF_SPLAT_PER_FRAME and 1 without.  A
+ * count is the number of 8x32 source blocks whose valid points' bins touch the tile (above 64 the list overflowed and the tile took
+ * the box-scan path).  n_counts receives B*G*tiles; host_counts == NULL only asks for it.  Waits for `stream`. */
+int pf_debug_splat_counts(const void *ws, size_t ws_bytes, int B, int T, int H, int W, int per_frame, unsigned *host_counts, size_t cap,
+                          size_t *n_counts, void *stream);
 
 #ifdef __cplusplus
 }

@@ -9,15 +9,18 @@
 // agent-scope atomics are executed memory-side across the 8 non-coherent XCD L2s
 // (profiles/r01_a_first_path_kernel_stats.txt).  This version is a two-pass binning rasteriser:
 //
-//   bin_kernel     one workgroup per 16x64 SOURCE tile: exact-order fp32 projection (this file is built with
+//   bin_kernel     one workgroup per 16x64 SOURCE tile, one wave per 8x32 BLOCK of it: exact-order fp32 projection (this file is built with
 //                  -ffp-contract=off; every product/sum rounded separately, IEEE divides) — four pixels per lane in
 //                  lockstep on the packed fp32 pipe with exact shortcuts for affine cameras (project4_fast), the full (project4_full)
-//                  scalar chain otherwise — stored as 8 B per point {bits(z), packed bins}; block max(z) partial; the
+//                  scalar chain otherwise — stored as 8 B per point {bits(z), packed bins}; tile max(z) partial; per block the
 //                  bounding box of the destination bins its VALID points reach; a byte mark per bin reached by an
-//                  INVALID point (plain stores of the constant 1 - no atomics needed); optional result2d.  The tile then
-//                  appends its id to the list of every destination tile its box touches (one global atomicAdd per pair).
-//   raster_kernel  one workgroup (512 threads = two groups of 256, each taking its own source tiles) per 32x128 DESTINATION
-//                  tile: reads its list (kFlight source tiles' 32-B-per-lane records in flight per group at a time; a list that overflowed kListCap falls back to testing every box of the frame), and
+//                  INVALID point (plain stores of the constant 1 - no atomics needed); optional result2d.  Every wave then
+//                  appends its block's id to the list of every destination tile its own box touches (one global atomicAdd
+//                  per pair).  The unit was the whole tile up to round 10: the raster pass then decoded 2.1-2.3 points per
+//                  source point, half of them from tiles that only graze the destination tile; per block it is 1.0-1.3
+//                  (tools/splat_list_counts.py).
+//   raster_kernel  one workgroup (512 threads = eight waves, each taking its own source blocks) per 32x128 DESTINATION
+//                  tile: reads its list (kFlight source blocks' 32-B-per-lane records in flight per wave at a time; a list that overflowed kListCap falls back to testing every box of the frame), and
 //                  resolves "min depth, ties -> lowest element index" with 64-bit ds_min on a packed key in a 32 KB LDS
 //                  z-buffer it alone owns; then writes seg/depth for its pixels.  The z-buffer never exists in HBM.
 //                  List order is arbitrary (atomic appends); min() does not care: the output is deterministic.
@@ -56,17 +59,21 @@ constexpr int kThreads = 256;
 // invalid-point mark stores of bin_kernel (same-box A/B, 32 frames, profiles/r06_experiments.md): four unconditional byte stores
 // (rounds 1-5) took 1138 / 1119 / 1138 us; only the distinct bins 1088 / 1093 / 1095; the shipped form - distinct bins, the two bins
 // of a row as one two-byte store - 1064 / 1071 / 1067 (-6 %).  All three were bit-exact
-constexpr int kRThreads = 512;            // raster workgroup: kRHalves groups of 256 threads, each group takes its own source tile
+constexpr int kRThreads = 512;            // raster workgroup: kRWaves waves, each wave takes its own source blocks
 constexpr int kRMinWaves = 8;             // __launch_bounds__' second argument on HIP: waves per SIMD -> 64 registers
-constexpr int kRHalves = kRThreads / 256;
+constexpr int kRWaves = kRThreads / 64;
 constexpr int kSrcTH = 16, kSrcTW = 64;   // source tile (pixels); 256 threads x 4 consecutive pixels
+constexpr int kBlkH = 8, kBlkW = 32;      // source block: one wave's 64 lanes x 4 consecutive pixels; the unit of boxes and lists
+constexpr int kTileBlocks = (kSrcTH / kBlkH) * (kSrcTW / kBlkW);   // block id = tile * kTileBlocks + wave, wave = (row half) * 2 + column half
+static_assert(kTileBlocks == kThreads / 64 && kSrcTW / kBlkW == 2, "one wave per block, two blocks per tile row");
 constexpr int kDstTH = 32, kDstTW = 128;  // destination tile owned by one raster workgroup (32 KB LDS)
 constexpr int kScan = 256;                // bounding boxes tested per thread-pass (overflow path only)
-constexpr int kScanBatches = 8;           // (the list holds kScan * kScanBatches = 2048 tile ids)
-constexpr int kListCap = 64;              // source-tile ids per destination-tile list written by bin_kernel (typical fill 6-12)
-constexpr int kFlight = 2;                // source tiles whose projections a group of 256 raster threads keeps in flight
-constexpr int kIdFrameShift = 20;         // list entry = (frame inside the z-buffer group) << 20 | source tile  (in the raster workgroup's LDS
-                                          // copy: | source tile row << 10 | column; both < 1024 as bins have 13 bits)
+constexpr int kScanBatches = 8;           // (the list holds kScan * kScanBatches = 2048 block ids)
+constexpr int kListCap = 64;              // source-block ids per destination-tile list written by bin_kernel (fill at 1024x2048: mean 13-21,
+                                          // maximum 34: tools/splat_list_counts.py)
+constexpr int kFlight = 2;                // source blocks whose projections a raster wave keeps in flight
+constexpr int kIdFrameShift = 20;         // list entry = (frame inside the z-buffer group) << 20 | source block  (in the raster workgroup's LDS
+                                          // copy: | block row << 10 | block column; rows <= 8192 / 8, columns <= 8192 / 32 as bins have 13 bits)
 constexpr int kZSlots = 64;               // atomicMax slots per z-buffer group (spreads the memory-side atomics)
 
 struct SplatArgs {
@@ -74,12 +81,12 @@ struct SplatArgs {
     const uint8_t *mask;
     const uint8_t *seg;
     const float *Kinv, *E, *Tt, *Einv, *K;
-    int4 *bbox;           // [B][T][src tiles]  (x0min, y0min, x1max, y1max) of valid points' bins
+    int4 *bbox;           // [B][T][src tiles][kTileBlocks]  (x0min, y0min, x1max, y1max) of the block's valid points' bins
     unsigned *zmax_part;  // [G][kZSlots]       order-preserving u32 of max(z) per z-buffer group (atomicMax, zeroed per call)
     uint8_t *inv_mark;    // [B*G][N]           1 where an invalid point lands
     uint2 *proj;          // [B][T][N]          {bits(z), x0 | y0<<13 | (x1!=x0)<<26 | (y1!=y0)<<27 | valid<<28}
     unsigned *count;      // [B][G][dst tiles]  fill of the destination tile's list (zeroed per call; > kListCap = overflowed)
-    unsigned *lists;      // [B][G][dst tiles][kListCap]  source tiles whose valid points can reach the destination tile
+    unsigned *lists;      // [B][G][dst tiles][kListCap]  source blocks whose valid points can reach the destination tile
     uint8_t *out_seg;
     float *out_depth;
     long long *out_r2d;
@@ -347,7 +354,9 @@ __global__ __launch_bounds__(kThreads) void bin_kernel(SplatArgs a) {
     const int ty0 = (tile / a.stx) * kSrcTH, tx0 = (tile % a.stx) * kSrcTW;
     const long long N = (long long)a.H * a.W;
     const long long in_base = ((long long)b * a.T_total + t) * N;
-    const int y = ty0 + (threadIdx.x >> 4), x = tx0 + (threadIdx.x & 15) * 4;
+    // a wave owns one 8x32 block of the tile: eight lanes per row segment (128 B of depth, 256 B of records)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int y = ty0 + (wave >> 1) * kBlkH + (lane >> 3), x = tx0 + (wave & 1) * kBlkW + (lane & 7) * 4;
     // the pixel loads go out BEFORE the 66 camera scalars are fetched: two independent round trips in flight together (a
     // one-tile workgroup lives ~9 us, most of it dependent latency: profiles/r02_experiments.md)
     float d[4] = {1.0f, 1.0f, 1.0f, 1.0f};
@@ -438,48 +447,49 @@ __global__ __launch_bounds__(kThreads) void bin_kernel(SplatArgs a) {
     PF_DPP_STEP(0x142, 0xA)   // row_bcast:15 into rows 1 and 3
     PF_DPP_STEP(0x143, 0xC)   // row_bcast:31 into rows 2 and 3
 #undef PF_DPP_STEP
+    // lane 63 holds the wave's reductions.  The box stays per block: stored for the raster pass' overflow path, and passed through LDS
+    // to wave 0, which registers all four blocks; max z is combined over the tile's four waves for the one zmax_part slot of the tile
     __shared__ float zred[kThreads / 64];
     __shared__ int bred[kThreads / 64][2];
-    if ((threadIdx.x & 63) == 63) {
-        const int w = threadIdx.x >> 6;
-        zred[w] = zmax;
-        bred[w][0] = __builtin_bit_cast(int, bmin);
-        bred[w][1] = __builtin_bit_cast(int, bmax);
+    if (lane == 63) {
+        const long long ntile = (long long)a.stx * a.sty;
+        zred[wave] = zmax;
+        bred[wave][0] = __builtin_bit_cast(int, bmin);
+        bred[wave][1] = __builtin_bit_cast(int, bmax);
+        a.bbox[(((long long)b * a.T + tl) * ntile + tile) * kTileBlocks + wave] =
+            make_int4(bmin[0] == 0xFFFF ? 0x7fffffff : (int)bmin[0], bmin[1] == 0xFFFF ? 0x7fffffff : (int)bmin[1], bmax[0], bmax[1]);
     }
     __syncthreads();
-    zmax = zred[0];
-    bmin = __builtin_bit_cast(u16x2, bred[0][0]);
-    bmax = __builtin_bit_cast(i16x2, bred[0][1]);
-#pragma unroll
-    for (int w = 1; w < kThreads / 64; ++w) {
-        zmax = fmaxf(zmax, zred[w]);
-        bmin = __builtin_elementwise_min(bmin, __builtin_bit_cast(u16x2, bred[w][0]));
-        bmax = __builtin_elementwise_max(bmax, __builtin_bit_cast(i16x2, bred[w][1]));
-    }
-    bx0 = bmin[0] == 0xFFFF ? 0x7fffffff : (int)bmin[0];
-    by0 = bmin[1] == 0xFFFF ? 0x7fffffff : (int)bmin[1];
-    bx1 = bmax[0];
-    by1 = bmax[1];
-    if (threadIdx.x == 0) {
-        const long long ntile = (long long)a.stx * a.sty;
+    if (wave != 0) return;   // the other waves end here instead of waiting for an atomic's round trip each
+    if (lane == 0) {
         // :105 the sentinel is max(z)+1 over the whole predict call (one frame's points in per_frame mode): one
         // order-independent atomicMax per source tile instead of every raster workgroup re-reducing all partials
+        zmax = zred[0];
+#pragma unroll
+        for (int w = 1; w < kThreads / 64; ++w) zmax = fmaxf(zmax, zred[w]);
         atomicMax(&a.zmax_part[(b * a.zgroups_per_sample + (a.per_frame ? tl : 0)) * kZSlots + ((tile + b) & (kZSlots - 1))], float_to_ordered(zmax));
-        a.bbox[((long long)b * a.T + tl) * ntile + tile] = make_int4(bx0, by0, bx1, by1);
     }
-    // register this tile with every destination tile its box touches (one global atomicAdd per pair, ~1.5 per tile): the
-    // raster workgroups then read their list instead of testing every box of the frame
-    if (bx1 >= 0) {
+    // register every block with every destination tile its own box touches (one global atomicAdd per pair): the raster workgroups
+    // then read their list instead of testing every box of the frame.  A block without a valid point registers nothing.
+    // Sixteen lanes per block, as a 4x4 grid over the touched tiles (1-4 of them as a rule; a wider box takes more rounds)
+    {
+        const int blk = lane >> 4, jx = lane & 3, jy = (lane >> 2) & 3;
+        bmin = __builtin_bit_cast(u16x2, bred[blk][0]);
+        bmax = __builtin_bit_cast(i16x2, bred[blk][1]);
+        bx0 = bmin[0]; by0 = bmin[1];
+        bx1 = bmax[0]; by1 = bmax[1];
+        if (bx1 < 0) return;
         const int ndst = a.dtx * a.dty;
         const long long dbase = ((long long)b * G + g) * ndst;
-        const unsigned id = ((unsigned)(a.per_frame ? 0 : tl) << kIdFrameShift) | (unsigned)tile;
+        const unsigned id = ((unsigned)(a.per_frame ? 0 : tl) << kIdFrameShift) | (unsigned)(tile * kTileBlocks + blk);
         const int dtx0 = bx0 / kDstTW, dty0 = by0 / kDstTH;
-        const int ntx = bx1 / kDstTW - dtx0 + 1, nt = ntx * (by1 / kDstTH - dty0 + 1);
-        for (int j = threadIdx.x; j < nt; j += kThreads) {
-            const long long dst = dbase + (dty0 + j / ntx) * a.dtx + dtx0 + j % ntx;
-            const unsigned slot = atomicAdd(&a.count[dst], 1u);
-            if (slot < (unsigned)kListCap) a.lists[dst * kListCap + slot] = id;
-        }
+        const int ntx = bx1 / kDstTW - dtx0 + 1, nty = by1 / kDstTH - dty0 + 1;
+        for (int oy = jy; oy < nty; oy += 4)
+            for (int ox = jx; ox < ntx; ox += 4) {
+                const long long dst = dbase + (dty0 + oy) * a.dtx + dtx0 + ox;
+                const unsigned slot = atomicAdd(&a.count[dst], 1u);
+                if (slot < (unsigned)kListCap) a.lists[dst * kListCap + slot] = id;
+            }
     }
 }
 
@@ -497,12 +507,12 @@ __global__ __launch_bounds__(kRThreads, kRMinWaves) void raster_kernel(SplatArgs
     const int dy1 = min(dy0 + kDstTH, a.H) - 1, dx1 = min(dx0 + kDstTW, a.W) - 1;
     const long long N = (long long)a.H * a.W;
     const long long P = (long long)Tg * N;
-    const int ntile = a.stx * a.sty;
+    const int nblock = a.stx * a.sty * kTileBlocks;
 
     RPROBE(0);
     [[maybe_unused]] int n_hits_total = 0;   // PF_PROBE builds report it
     for (int i = threadIdx.x; i < kDstTH * kDstTW; i += kRThreads) zb[i] = kEmpty;
-    const int lt = threadIdx.x & 255, half = threadIdx.x >> 8;   // thread inside its group of 256, group
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;   // every wave takes source blocks of its own
 
     // sentinel = max(z over the whole predict call) + 1 (:105); one frame's points in per_frame mode
     if (threadIdx.x < 64) {
@@ -512,8 +522,8 @@ __global__ __launch_bounds__(kRThreads, kRMinWaves) void raster_kernel(SplatArgs
         if (threadIdx.x == 0) sentinel_s = __fadd_rn(ordered_to_float(m), 1.0f);
     }
 
-    // ---- rasterise: every source tile whose valid-point bounding box touches this destination tile.  Hits are
-    //      collected first (one barrier pair per 256 boxes) and then consumed four at a time: their 32-B projection
+    // ---- rasterise: every source block whose valid-point bounding box touches this destination tile.  Hits are
+    //      collected first (one barrier pair per 256 boxes) and then consumed four per wave at a time: their 32-B projection
     //      records are all in flight before the first goes through the LDS atomics - the loop was
     //      a chain of ~2 us load latencies, one per hit (tools/probe_splat.py).
     // (the kernel is bound by vector-instruction issue - 87 % busy at 8 waves per SIMD, profiles/r02_k_pmc.json - and this is
@@ -541,12 +551,12 @@ __global__ __launch_bounds__(kRThreads, kRMinWaves) void raster_kernel(SplatArgs
             if (in_x1 && in_y1) atomicMin(&zb[ry1 * kDstTW + rx1], khi | (e0 + 3u * Pu1));
         }
     };
-    auto load4 = [&](const uint2 *pbase, int stx, int sty, unsigned (&pk)[8], int &x, int &y) {   // source tile column, row (< 0: none)
-        y = sty * kSrcTH + (lt >> 4);
-        x = stx * kSrcTW + (lt & 15) * 4;
+    auto load4 = [&](const uint2 *pbase, int bcol, int brow, unsigned (&pk)[8], int &x, int &y) {   // source block column (< 0: none), row
+        y = brow * kBlkH + (lane >> 3);
+        x = bcol * kBlkW + (lane & 7) * 4;
 #pragma unroll
         for (int k = 0; k < 8; ++k) pk[k] = 0u;      // valid bit clear: nothing to splat
-        if (stx < 0 || y >= a.H || x >= a.W) return;
+        if (bcol < 0 || y >= a.H || x >= a.W) return;
         const uint2 *pj = pbase + (long long)y * a.W + x;
         if ((a.W & 3) == 0) {
             const uint4 q0 = reinterpret_cast<const uint4 *>(pj)[0], q1 = reinterpret_cast<const uint4 *>(pj)[1];
@@ -560,25 +570,26 @@ __global__ __launch_bounds__(kRThreads, kRMinWaves) void raster_kernel(SplatArgs
             }
         }
     };
-    // ---- the destination tile's list (written by bin_kernel): kFlight source tiles' records in flight at a time
+    // ---- the destination tile's list (written by bin_kernel): kFlight source blocks' records in flight per wave at a time
     const int ndst = a.dtx * a.dty;
     const long long dslot = ((long long)b * G + g) * ndst + dtile;
     const unsigned cnt = a.count[dslot];
     if (cnt <= (unsigned)kListCap) {
         if (threadIdx.x < cnt) {
-            // source tile -> (row, column) once per entry here: a division by the tiles per row inside the loop below costs
-            // every lane ~25 vector instructions per listed tile, in a kernel bound by vector issue
-            const unsigned e = a.lists[dslot * kListCap + threadIdx.x], st = e & ((1u << kIdFrameShift) - 1u), row = st / (unsigned)a.stx;
-            ent[threadIdx.x] = (e & ~((1u << kIdFrameShift) - 1u)) | (row << 10) | (st - row * (unsigned)a.stx);
+            // source block -> (block row, block column) once per entry here: a division by the tiles per row inside the loop below
+            // costs every lane ~25 vector instructions per listed block, in a kernel bound by vector issue
+            const unsigned e = a.lists[dslot * kListCap + threadIdx.x], sb = e & ((1u << kIdFrameShift) - 1u);
+            const unsigned st = sb / kTileBlocks, w = sb % kTileBlocks, row = st / (unsigned)a.stx;
+            ent[threadIdx.x] = (e & ~((1u << kIdFrameShift) - 1u)) | ((row * 2u + (w >> 1)) << 10) | ((st - row * (unsigned)a.stx) * 2u + (w & 1u));
         }
         __syncthreads();
-        for (int li = 0; li < (int)cnt; li += kFlight * kRHalves) {
+        for (int li = 0; li < (int)cnt; li += kFlight * kRWaves) {
             unsigned pk[kFlight][8];
             int xs[kFlight], ys[kFlight];
             unsigned eb[kFlight];
 #pragma unroll
             for (int j = 0; j < kFlight; ++j) {
-                const int le = li + j * kRHalves + half;
+                const int le = li + j * kRWaves + wave;
                 const unsigned e = le < (int)cnt ? ent[le] : 0u;
                 const int tt = (int)(e >> kIdFrameShift), sx = le < (int)cnt ? (int)(e & 1023u) : -1, sy = (int)((e >> 10) & 1023u);
                 const int tl = a.per_frame ? g : tt;
@@ -592,17 +603,17 @@ __global__ __launch_bounds__(kRThreads, kRMinWaves) void raster_kernel(SplatArgs
     // the list overflowed: test every box of the group's frames (the path every call took before the lists existed)
     for (int tt = 0; tt < Tg; ++tt) {
         const int tl = a.per_frame ? g : tt;     // local frame index
-        const int4 *boxes = a.bbox + ((long long)b * a.T + tl) * ntile;
+        const int4 *boxes = a.bbox + ((long long)b * a.T + tl) * nblock;
         const uint2 *pbase = a.proj + ((long long)b * a.T + tl) * N;
         const unsigned ebase = (unsigned)tt * (unsigned)N;
-        for (int s0 = 0; s0 < ntile; s0 += kScan * kScanBatches) {
+        for (int s0 = 0; s0 < nblock; s0 += kScan * kScanBatches) {
             __syncthreads();
             if (threadIdx.x == 0) list_n = 0;
             __syncthreads();
 #pragma unroll
             for (int j = 0; j < kScanBatches; ++j) {
-                const int s = s0 + j * kScan + lt;
-                if (s < ntile && half == 0) {
+                const int s = s0 + j * kScan + (int)threadIdx.x;
+                if (s < nblock && threadIdx.x < kScan) {
                     const int4 bb = boxes[s];
                     if (bb.x <= dx1 && bb.z >= dx0 && bb.y <= dy1 && bb.w >= dy0) list[atomicAdd(&list_n, 1)] = (unsigned short)(s - s0);
                 }
@@ -611,14 +622,14 @@ __global__ __launch_bounds__(kRThreads, kRMinWaves) void raster_kernel(SplatArgs
             const int n_hit = list_n;
             n_hits_total += n_hit;
             RPROBE(4);
-            for (int li = 0; li < n_hit; li += 4 * kRHalves) {
+            for (int li = 0; li < n_hit; li += 4 * kRWaves) {
                 unsigned pk[4][8];
                 int xs[4], ys[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int le = li + j * kRHalves + half;
-                    const int st = le < n_hit ? s0 + list[le] : -1;
-                    load4(pbase, st < 0 ? -1 : st % a.stx, st < 0 ? 0 : st / a.stx, pk[j], xs[j], ys[j]);
+                    const int le = li + j * kRWaves + wave;
+                    const int sb = le < n_hit ? s0 + list[le] : -1, st = sb / kTileBlocks, w = sb % kTileBlocks;
+                    load4(pbase, sb < 0 ? -1 : (st % a.stx) * 2 + (w & 1), sb < 0 ? 0 : (st / a.stx) * 2 + (w >> 1), pk[j], xs[j], ys[j]);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) splat4(pk[j], xs[j], ys[j], ebase);
@@ -711,7 +722,7 @@ static SplatLayout splat_layout(int B, int T, int H, int W, int per_frame) {
     L.dtx = (W + kDstTW - 1) / kDstTW; L.dty = (H + kDstTH - 1) / kDstTH;
     const size_t ntile = (size_t)L.stx * L.sty, N = (size_t)H * W;
     L.bbox_off = 0;
-    L.zmax_off = align_up(L.bbox_off + (size_t)B * T * ntile * sizeof(int4), 256);
+    L.zmax_off = align_up(L.bbox_off + (size_t)B * T * ntile * kTileBlocks * sizeof(int4), 256);
     // zmax slots, list counters and marks are contiguous: one memset per call
     const size_t ndst = (size_t)L.dtx * L.dty, G = per_frame ? T : 1;
     L.count_off = align_up(L.zmax_off + (size_t)B * T * kZSlots * sizeof(unsigned), 256);
@@ -732,6 +743,11 @@ extern "C" int pf_warp_splat_workspace(int B, int T, int H, int W, int per_frame
         return pf::fail(PF_EUNSUPPORTED, "pf_warp_splat: 4*T*H*W must be < 2^32 (element index packs in 32 bits)");
     if (H > 8192 || W > 8192 || T >= 4096)
         return pf::fail(PF_EUNSUPPORTED, "pf_warp_splat: H and W must be <= 8192 (13-bit bin coordinates) and T < 4096");
+    // list entries count source BLOCKS: id below the frame bits, block row and column in 10 bits each (raster_kernel's ent[])
+    const long long brows = (H + pf::kBlkH - 1) / pf::kBlkH, bcols = (W + pf::kBlkW - 1) / pf::kBlkW;
+    const long long tiles = ((H + pf::kSrcTH - 1) / pf::kSrcTH) * (long long)((W + pf::kSrcTW - 1) / pf::kSrcTW);
+    if (tiles * pf::kTileBlocks > (1ll << pf::kIdFrameShift) || brows > 1024 || bcols > 1024)
+        return pf::fail(PF_EUNSUPPORTED, "pf_warp_splat: %lld source blocks (%lld x %lld) do not fit the list entry", tiles * pf::kTileBlocks, brows, bcols);
     *bytes = pf::splat_layout(B, T, H, W, per_frame & PF_SPLAT_PER_FRAME).total;
     return PF_OK;
 }
@@ -794,5 +810,24 @@ extern "C" int pf_warp_splat(const float *depth, const uint8_t *depth_mask, cons
         hipLaunchKernelGGL(pf::raster_kernel, dim3(L.dtx * L.dty, G, B), dim3(pf::kRThreads), 0, s, a);
         PF_LAUNCH_CHECK("raster_kernel");
     }
+    return PF_OK;
+}
+
+extern "C" int pf_debug_splat_counts(const void *ws, size_t ws_bytes, int B, int T, int H, int W, int per_frame, unsigned *host_counts,
+                                     size_t cap, size_t *n_counts, void *stream) {
+    if (!ws || !n_counts) return pf::fail(PF_EINVAL, "pf_debug_splat_counts: null pointer argument");
+    size_t need = 0;
+    if (int rc = pf_warp_splat_workspace(B, T, H, W, per_frame, &need)) return rc;
+    if (ws_bytes < need)
+        return pf::fail(PF_EWORKSPACE, "pf_debug_splat_counts: workspace %zu B < required %zu B", ws_bytes, need);
+    const pf::SplatLayout L = pf::splat_layout(B, T, H, W, per_frame & PF_SPLAT_PER_FRAME);
+    const size_t n = (size_t)B * ((per_frame & PF_SPLAT_PER_FRAME) ? T : 1) * L.dtx * L.dty;
+    *n_counts = n;
+    if (!host_counts) return PF_OK;   // size query
+    if (cap < n) return pf::fail(PF_EINVAL, "pf_debug_splat_counts: room for %zu counts, %zu needed", cap, n);
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(host_counts, (const char *)ws + L.count_off, n * sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return pf::fail(PF_EHIP, "pf_debug_splat_counts: copying the counts failed");
     return PF_OK;
 }

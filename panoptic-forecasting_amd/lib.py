@@ -96,6 +96,7 @@ SIGNATURES = {
     'pf_debug_conv_decision': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _i]),
     'pf_debug_net_choice': (_i, [_i, _c.POINTER(_i), _i, _c.POINTER(_f), _i, _c.c_char_p, _sz, _c.POINTER(_c.c_longlong), _i]),
     'pf_debug_probe_read': (_i, [_c.POINTER(_c.c_longlong)]),
+    'pf_debug_splat_counts': (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _sz, _c.POINTER(_sz), _vp]),
     'pf_debug_conv_ranges': (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _sz]),
     'pf_debug_pack_conv': (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _c.POINTER(_sz)]),
     'pf_debug_plan_arena': (_i, [_vp, _sz, _i, _i, _vp, _sz, _c.POINTER(_sz), _vp, _i]),

@@ -135,6 +135,7 @@ class WarpSplat:
 
     def __init__(self):
         self._ws = None
+        self._last = None
 
     def _workspace(self, b, t, h, w, per_frame, device):
         L = _lib.load()
@@ -174,9 +175,23 @@ class WarpSplat:
                              r2d.data_ptr() if r2d is not None else None,
                              ws.data_ptr(), ws.numel(), _lib.stream_ptr())
         _lib.check(rc, 'pf_warp_splat')
+        self._last = (b, T, h, w, flags)
         if seg_dtype != torch.uint8:
             out_seg = out_seg.to(seg_dtype)
         return out_seg, out_depth, r2d
+
+    def list_counts(self):
+        """Debug tap (``pf_debug_splat_counts``): how many 8x32 source blocks the last call listed per 32x128 destination tile,
+        as an int64 tensor [B, G, tile rows, tile columns] (G = T with per_frame, else 1)."""
+        L = _lib.load()
+        b, T, h, w, flags = self._last
+        n = ctypes.c_size_t()
+        args = (self._ws.data_ptr(), self._ws.numel(), b, T, h, w, flags)
+        _lib.check(L.pf_debug_splat_counts(*args, None, 0, ctypes.byref(n), _lib.stream_ptr()), 'pf_debug_splat_counts')
+        host = (ctypes.c_uint * n.value)()
+        _lib.check(L.pf_debug_splat_counts(*args, host, n.value, ctypes.byref(n), _lib.stream_ptr()), 'pf_debug_splat_counts')
+        g = T if flags & PF_SPLAT_PER_FRAME else 1
+        return torch.tensor(list(host), dtype=torch.int64).view(b, g, (h + 31) // 32, (w + 127) // 128)
 
 
 class PCTransformModel(BaseModel):

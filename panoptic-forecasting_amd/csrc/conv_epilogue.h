@@ -162,34 +162,59 @@ __device__ __forceinline__ epi_f32x4 quad_transpose(epi_f32x4 v) {
 typedef split_x2 epi_h2;   // fp16 terms of the operand split (conv_mfma.h)
 typedef split_x4 epi_h4;
 
-// c = 4 consecutive channels (buffer channels chb .. chb+3, chb even) of the pixel at element offset `pix` of an h x w plane
-__device__ __forceinline__ void s4_store_unit(const ConvArgs &a, int b, int chb, size_t plane_px, size_t pix, epi_f32x4 c) {
+// ---- the one store rule of the packed-pair layout --------------------------------------------------------------------
+// A layer's 4 output channels of one pixel are one 8-B unit per term.  A slice may start in the middle of a channel group
+// (choff & 2: it then owns the upper half of one group and the lower half of the next) and owns its last group in half or in
+// full (limit).  Every kernel that writes the layout stores through s4_store_px; conv_front.hip alone keeps a buffer-store form of
+// the group-aligned branch (its store_pending says why).
+struct S4Dst {
+    char *base;      // frame base of the destination tensor (hi term)
+    size_t term, hw; // bytes between the terms, pixels per plane
+    int choff, limit;
+};
+// frame b of the launch's own destination, as planes of plane_px pixels (pooled stores: a quarter of the conv's).  epi_store /
+// epi_store_pooled pass co & ~3, so the buffer channel dst_choff + (co & ~3) has the low two bits of the even dst_choff: the
+// "(chb & 3) == 0" these two once tested is s4_store_px's "(choff & 2) == 0"
+__device__ __forceinline__ S4Dst s4_dst(const ConvArgs &a, int b, size_t plane_px) {
+    S4Dst d;
+    d.term = (size_t)a.dst_c4 * plane_px * 8;
+    d.hw = plane_px;
+    d.base = reinterpret_cast<char *>(a.dst) + (size_t)b * 2 * d.term;
+    d.choff = a.dst_choff;
+    d.limit = a.dst_limit;
+    return d;
+}
+// v = the layer's couts co .. co + 3 (co % 4 == 0) of the pixel at element offset pix
+__device__ __forceinline__ void s4_store_px(const S4Dst &d, int co, size_t pix, const epi_f32x4 &v) {
     epi_h4 hi, mid;
-    split_terms4(c, hi, mid);
-    const size_t term = (size_t)a.dst_c4 * plane_px * 8;                      // bytes between the hi and the mid block
-    char *base = reinterpret_cast<char *>(a.dst) + (size_t)b * 2 * term + pix * 8;
-    const bool ok0 = chb < a.dst_limit, ok1 = chb + 2 < a.dst_limit;
-    if ((chb & 3) == 0) {
-        char *p = base + (size_t)(chb >> 2) * plane_px * 8;
+    split_terms4(v, hi, mid);
+    const int chb = d.choff + co;
+    const bool ok0 = chb < d.limit, ok1 = chb + 2 < d.limit;
+    char *p = d.base + pix * 8 + (size_t)(chb >> 2) * d.hw * 8;
+    if ((d.choff & 2) == 0) {
         if (ok1) {
             *reinterpret_cast<epi_h4 *>(p) = hi;
-            *reinterpret_cast<epi_h4 *>(p + term) = mid;
+            *reinterpret_cast<epi_h4 *>(p + d.term) = mid;
         } else if (ok0) {
             *reinterpret_cast<epi_h2 *>(p) = epi_h2{hi[0], hi[1]};
-            *reinterpret_cast<epi_h2 *>(p + term) = epi_h2{mid[0], mid[1]};
+            *reinterpret_cast<epi_h2 *>(p + d.term) = epi_h2{mid[0], mid[1]};
         }
-    } else {   // the range starts in the middle of a group: upper half of one group, lower half of the next
-        char *p = base + (size_t)(chb >> 2) * plane_px * 8 + 4;
+    } else {   // upper half of one group, lower half of the next
         if (ok0) {
-            *reinterpret_cast<epi_h2 *>(p) = epi_h2{hi[0], hi[1]};
-            *reinterpret_cast<epi_h2 *>(p + term) = epi_h2{mid[0], mid[1]};
+            *reinterpret_cast<epi_h2 *>(p + 4) = epi_h2{hi[0], hi[1]};
+            *reinterpret_cast<epi_h2 *>(p + 4 + d.term) = epi_h2{mid[0], mid[1]};
         }
-        p += plane_px * 8 - 4;
         if (ok1) {
-            *reinterpret_cast<epi_h2 *>(p) = epi_h2{hi[2], hi[3]};
-            *reinterpret_cast<epi_h2 *>(p + term) = epi_h2{mid[2], mid[3]};
+            *reinterpret_cast<epi_h2 *>(p + d.hw * 8) = epi_h2{hi[2], hi[3]};
+            *reinterpret_cast<epi_h2 *>(p + d.hw * 8 + d.term) = epi_h2{mid[2], mid[3]};
         }
     }
+}
+// the finishing step in front of the store: 2^-k of the weight scaling (exact), bias, ReLU as one max (relu_lo = 0 or -inf)
+__device__ __forceinline__ epi_f32x4 s4_finish(epi_f32x4 acc, float scale, const epi_f32x4 &bias4, float relu_lo) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = fmaxf(acc[r] * scale + bias4[r], relu_lo);
+    return acc;
 }
 
 // vmax: the caller's running max |v| of what it stores (range guard of the operand split, conv_mfma.h: the caller commits it
@@ -201,7 +226,7 @@ __device__ __forceinline__ void epi_store(const ConvArgs &a, int b, int co, int 
         const epi_f32x4 c = quad_transpose(v);
         const int k = threadIdx.x & 3;
         if (ox + k < a.Wout)
-            s4_store_unit(a, b, a.dst_choff + (co & ~3), (size_t)a.Hout * a.Wout, (size_t)oy * a.Wout + ox + k, c);
+            s4_store_px(s4_dst(a, b, (size_t)a.Hout * a.Wout), co & ~3, (size_t)oy * a.Wout + ox + k, c);
         return;
     }
     float *p = a.dst + ((size_t)b * a.dst_ctotal + a.dst_choff + co) * ((size_t)a.Hout * a.Wout) + (size_t)oy * a.Wout + ox;
@@ -226,7 +251,7 @@ __device__ __forceinline__ void epi_store_pooled(const ConvArgs &a, int b, int c
         const epi_f32x4 c = quad_transpose(epi_f32x4{live ? p0 : 0.f, live ? p1 : 0.f, 0.f, 0.f});
         const int k = threadIdx.x & 3;
         if (py < Hp && k < 2 && px + k < Wp)
-            s4_store_unit(a, b, a.dst_choff + (co & ~3), (size_t)Hp * Wp, (size_t)py * Wp + px + k, c);
+            s4_store_px(s4_dst(a, b, (size_t)Hp * Wp), co & ~3, (size_t)py * Wp + px + k, c);
         return;
     }
     if (py >= Hp) return;

@@ -199,7 +199,8 @@ __global__ __launch_bounds__(256, 2) void conv_front_kernel(FrontArgs a) {
             if (!(rc[j] >> 6) || oy >= a.H2 || ox >= a.W2 || co >= a.C2 + 2) continue;
             const unsigned pix = (unsigned)(oy * a.W2 + ox);
             const fm_f32x4 v = pend[j];
-            if (a.dst_fmt) {
+            if (a.dst_fmt) {   // the store rule of s4_store_px (conv_epilogue.h), group-aligned branch, as buffer stores (through a buffer twin
+                               // of that routine: 230 instead of 229 VGPRs, 100 instead of 96 SGPRs, 98 instructions more)
                 fm_h4 hi, mid;
                 split_terms4(v, hi, mid);
                 const fm_u2 hu = __builtin_bit_cast(fm_u2, hi), mu = __builtin_bit_cast(fm_u2, mid);

@@ -277,7 +277,7 @@ bool conv_split_supported(const ConvArgs &a);   // launch_conv_split has a kerne
 int launch_conv_split1(const ConvArgs &a, int nt, int B, hipStream_t stream);
 bool conv_split1_supported(const ConvArgs &a, int nt);   // ... and launch_conv_split1 (a residual window must fit LDS)
 
-// S4 path (conv_s4.hip; stride 1, W % 4 == 0): every source in the packed-pair layout, tiles arrive by LDS-DMA, no split
+// S4 path (conv_s4.hip, 1x1: conv_s4_1x1.hip; stride 1, W % 4 == 0): every source in the packed-pair layout, tiles arrive by LDS-DMA, no split
 // phase; a.wpk = pack_conv_weights_s4() output (conv_pack.h: its K order).
 struct S4Range { int choff, ch; };   // a source range in the channel numbering of its tensor
 struct KOrder;   // the ranges of a launch in K order with their starts in the conv's input-channel numbering (conv_ranges.h, which counts
@@ -348,7 +348,7 @@ bool conv_pair_merged_supports(int c_cout, int p_cout);     // PairArgs::merged 
 // 3: wherever possible and never merged, 4: the merged pairs only)
 bool pair_wanted(int p_cin, int p_cout, int c_cin, int c_cout, int h, int w, int B, int mode);
 int launch_conv_pair(const PairArgs &pa, int B, hipStream_t stream);
-// layout conversion (tests, tensor taps): fp32 NCHW <-> S4
+// s4_layout.hip: layout conversion (tests, tensor taps), fp32 NCHW <-> S4, and the range guard's own kernels
 // status (nullable, device): PF_STATUS_RANGE is raised when an element exceeds what the pair represents (|x| > 65504)
 int launch_s4_pack(const float *src, void *dst, int B, int C, int H, int W, unsigned *status, hipStream_t stream);
 // raises PF_STATUS_RANGE in *status if any of the n floats at x is not |x| <= 65504 (NaN included); max |x| -> *slot (nullable)

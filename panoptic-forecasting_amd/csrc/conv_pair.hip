@@ -85,41 +85,6 @@ __device__ __forceinline__ void pair_products(s4_f32x4 (*acc)[NTn], const s4_h8 
 #endif
 }
 
-// one pixel's 4 output channels into the packed-pair layout (group tails, ranges that start in the middle of a group): conv_s4.hip
-struct PairDst {
-    char *base;      // frame base of the destination tensor (hi term)
-    size_t term, hw; // bytes between the terms, pixels per plane
-    int choff, limit;
-};
-__device__ __forceinline__ void pair_store_px(const PairDst &d, int co, size_t pix, const s4_f32x4 &v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef split_x2 h2;
-    s4_h4 hi, mid;
-    split_terms4(v, hi, mid);
-    const int chb = d.choff + co;
-    const bool ok0 = chb < d.limit, ok1 = chb + 2 < d.limit;
-    char *p = d.base + pix * 8 + (size_t)(chb >> 2) * d.hw * 8;
-    if ((d.choff & 2) == 0) {
-        if (ok1) {
-            *reinterpret_cast<s4_h4 *>(p) = hi;
-            *reinterpret_cast<s4_h4 *>(p + d.term) = mid;
-        } else if (ok0) {
-            *reinterpret_cast<h2 *>(p) = h2{hi[0], hi[1]};
-            *reinterpret_cast<h2 *>(p + d.term) = h2{mid[0], mid[1]};
-        }
-    } else {   // upper half of one group, lower half of the next
-        if (ok0) {
-            *reinterpret_cast<h2 *>(p + 4) = h2{hi[0], hi[1]};
-            *reinterpret_cast<h2 *>(p + 4 + d.term) = h2{mid[0], mid[1]};
-        }
-        if (ok1) {
-            *reinterpret_cast<h2 *>(p + d.hw * 8) = h2{hi[2], hi[3]};
-            *reinterpret_cast<h2 *>(p + d.hw * 8 + d.term) = h2{mid[2], mid[3]};
-        }
-    }
-#endif
-}
-
 template <int NT, int NTP, int MERGED>
 __global__ __launch_bounds__(512, 4) void conv_pair_kernel(PairArgs pa) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -426,7 +391,7 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(PairArgs pa) {
         // ---- P's epilogue: bias, ReLU, zero outside the image, split -> LDS planes (+ the tile's own pixels -> memory)
         const int px = lane & 15;
         const size_t hw = (size_t)a.Hout * a.Wout;
-        PairDst pd;
+        S4Dst pd;                               // P's slice of the block output (conv_epilogue.h)
         pd.term = (size_t)pa.p_dst_c4 * hw * 8;
         pd.hw = hw;
         pd.base = reinterpret_cast<char *>(pa.p_dst) + (size_t)b * 2 * pd.term;
@@ -449,6 +414,8 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(PairArgs pa) {
             for (int n = 0; n < NTP; ++n) {
                 s4_f32x4 v = pacc[m][n] + pacc9[m][n];
                 const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(bias_lds + (NT + n) * 16 + 4 * g);
+                // (s4_finish written out: through the helper and one select per vector the scratch of <2, 2, 0> and <3, 1, 0> moved,
+                //  108 -> 112 and 52 -> 44 B, and six kernels changed; profiles/s4_store_unify.md)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = inimg ? fmaxf(v[r] * pa.p_acc_scale + b4[r], relu_lo) : 0.f;
                 vmax = range_acc(vmax, v[0], v[1], v[2], v[3]);
@@ -460,7 +427,7 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(PairArgs pa) {
                     *reinterpret_cast<s4_h4 *>(dp + C::NDENT * C::DPLANE) = mid;
                 }
                 const int co = n * 16 + 4 * g;
-                if (own && co < pa.p_cout + 2) pair_store_px(pd, co, (size_t)y * a.Wout + x, v);
+                if (own && co < pa.p_cout + 2) s4_store_px(pd, co, (size_t)y * a.Wout + x, v);
             }
         }
         }
@@ -477,15 +444,14 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(PairArgs pa) {
                 s4_f32x4 v = acc[m][NT - 1];
                 const int pg = g > 0 ? g - 1 : 3;             // plane entry this lane writes
                 const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(bias_lds + NT * 16 + 4 * pg);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = (inimg && g > 0) ? fmaxf(v[r] * pa.p_acc_scale + b4[r], relu_lo) : 0.f;
+                v = (inimg && g > 0) ? s4_finish(v, pa.p_acc_scale, b4, relu_lo) : s4_f32x4{0.f, 0.f, 0.f, 0.f};
                 vmax = range_acc(vmax, v[0], v[1], v[2], v[3]);
                 s4_h4 hi, mid;
                 split_terms4(v, hi, mid);
                 unsigned char *dp = dbuf + pg * C::DPLANE + q * 8;
                 *reinterpret_cast<s4_h4 *>(dp) = hi;
                 *reinterpret_cast<s4_h4 *>(dp + C::NDENT * C::DPLANE) = mid;
-                if (inimg && g > 0 && 4 * pg < pa.p_cout + 2) pair_store_px(pd, 4 * pg, (size_t)oy * a.Wout + ox, v);
+                if (inimg && g > 0 && 4 * pg < pa.p_cout + 2) s4_store_px(pd, 4 * pg, (size_t)oy * a.Wout + ox, v);
             }
         }
         range_commit(a.status, pa.p_range_slot, vmax);
@@ -498,12 +464,7 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(PairArgs pa) {
         __builtin_amdgcn_s_waitcnt(0x0F70);
         const int px = lane & 15;
         const size_t hw = (size_t)a.Hout * a.Wout;
-        PairDst cd;
-        cd.term = (size_t)a.dst_c4 * hw * 8;
-        cd.hw = hw;
-        cd.base = reinterpret_cast<char *>(a.dst) + (size_t)b * 2 * cd.term;
-        cd.choff = a.dst_choff;
-        cd.limit = a.dst_limit;
+        const S4Dst cd = s4_dst(a, b, hw);
         const float relu_lo = a.relu ? 0.f : -__builtin_inff();
         float vmax = 0.f;
 #pragma unroll
@@ -515,12 +476,10 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(PairArgs pa) {
             for (int n = 0; n < NT; ++n) {
                 const int co = n * 16 + 4 * g;
                 if (co >= a.Cout + 2) continue;
-                s4_f32x4 v = acc[m][n];
                 const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(bias_lds + n * 16 + 4 * g);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r] * a.acc_scale + b4[r], relu_lo);
+                const s4_f32x4 v = s4_finish(acc[m][n], a.acc_scale, b4, relu_lo);
                 vmax = range_acc(vmax, v[0], v[1], v[2], v[3]);
-                pair_store_px(cd, co, pix, v);
+                s4_store_px(cd, co, pix, v);
             }
         }
         range_commit(a.status, a.range_slot, vmax);

@@ -395,37 +395,9 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
         if constexpr (RING) __syncthreads();       // every wave's pieces of R's fragments have landed
         const int g = lane >> 4, px = lane & 15;
         const size_t hw = (size_t)a.Hout * a.Wout;
-        const size_t term = (size_t)a.dst_c4 * hw * 8;
-        const bool mis = (a.dst_choff & 2) != 0;   // the range starts in the middle of a group (uniform)
+        const S4Dst sd = s4_dst(a, b, hw);         // this conv's slice (conv_epilogue.h: s4_store_px)
         const float relu_lo = a.relu ? 0.f : -__builtin_inff();
         float vmax = 0.f;                          // range guard of the operand split (conv_mfma.h)
-        typedef split_x2 h2;
-        // one pixel's 4 channels (group tails, ranges that start in the middle of a group)
-        auto store_px = [&](int co, size_t pix, s4_f32x4 v) {
-            s4_h4 hi, mid;
-            split_terms4(v, hi, mid);
-            const int chb = a.dst_choff + co;
-            const bool ok0 = chb < a.dst_limit, ok1 = chb + 2 < a.dst_limit;
-            char *p = reinterpret_cast<char *>(a.dst) + (size_t)b * 2 * term + pix * 8 + (size_t)(chb >> 2) * hw * 8;
-            if (!mis) {
-                if (ok1) {
-                    *reinterpret_cast<s4_h4 *>(p) = hi;
-                    *reinterpret_cast<s4_h4 *>(p + term) = mid;
-                } else if (ok0) {
-                    *reinterpret_cast<h2 *>(p) = h2{hi[0], hi[1]};
-                    *reinterpret_cast<h2 *>(p + term) = h2{mid[0], mid[1]};
-                }
-            } else {   // upper half of one group, lower half of the next
-                if (ok0) {
-                    *reinterpret_cast<h2 *>(p + 4) = h2{hi[0], hi[1]};
-                    *reinterpret_cast<h2 *>(p + 4 + term) = h2{mid[0], mid[1]};
-                }
-                if (ok1) {
-                    *reinterpret_cast<h2 *>(p + hw * 8) = h2{hi[2], hi[3]};
-                    *reinterpret_cast<h2 *>(p + hw * 8 + term) = h2{mid[2], mid[3]};
-                }
-            }
-        };
         // folds: R's chunk 0 operand of M-tile m, the centre pixels of its other channels (K slice g: group entries 2g, 2g + 1)
         [[maybe_unused]] auto fold_chunk0 = [&](int m, s4_h8 &x0h, s4_h8 &x0m) {
             x0h = s4_join(to_h[m][0], to_h[m][1]); x0m = s4_join(to_m[m][0], to_m[m][1]);
@@ -469,10 +441,8 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 s4_h4 xh[2], xm[2];
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
-                    s4_f32x4 v = acc[m][n];
                     const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(bias_lds + n * 16 + 4 * g);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r] * a.acc_scale + b4[r], relu_lo);
+                    const s4_f32x4 v = s4_finish(acc[m][n], a.acc_scale, b4, relu_lo);
                     const float vm = range_acc(vmax, v[0], v[1], v[2], v[3]);
                     vmax = in ? vm : vmax;
                     split_terms4(v, xh[n], xm[n]);
@@ -493,22 +463,18 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
             if constexpr (RING) {
                 // the plain epilogue for every lane (rows past this launch's couts: zero weights, zero bias -> 0), the slice stored as the
                 // plain form stores it; the same values split into the two terms R would read back are K slice g of R's chunk 1, as in
-                // the tail form, and are kept for all four M-tiles next to chunk 0's.  (The finishing loop is the tail form's, written out
-                // twice: as a shared lambda, capturing or not, it changes the register allocation of both kernels, which sit at 114 and
-                // 117 of 128 registers.  Likewise the pooled store below is store_px written out for R's destination)
+                // the tail form, and are kept for all four M-tiles next to chunk 0's
                 const bool in = oy < a.Hout && ox < a.Wout;
                 s4_h4 xh[NT], xm[NT];
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
                     const int co = (tile0 + n) * 16 + 4 * g;
-                    s4_f32x4 v = acc[m][n];
                     const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(bias_lds + n * 16 + 4 * g);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r] * a.acc_scale + b4[r], relu_lo);
+                    const s4_f32x4 v = s4_finish(acc[m][n], a.acc_scale, b4, relu_lo);
                     const float vm = range_acc(vmax, v[0], v[1], v[2], v[3]);
                     vmax = in ? vm : vmax;
                     split_terms4(v, xh[n], xm[n]);
-                    if (in && co < a.Cout + 2 && slice_stored) store_px(co, (size_t)oy * a.Wout + ox, v);
+                    if (in && co < a.Cout + 2 && slice_stored) s4_store_px(sd, co, (size_t)oy * a.Wout + ox, v);
                 }
                 dx1h[m] = s4_join(xh[0], xh[1]); dx1m[m] = s4_join(xm[0], xm[1]);
                 if constexpr (NT == 3) { dx2h[m] = xh[2]; dx2m[m] = xm[2]; }
@@ -537,14 +503,15 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 if (co >= a.Cout + 2) continue;
                 s4_f32x4 v = acc[m][n];
                 const s4_f32x4 b4 = *reinterpret_cast<const s4_f32x4 *>(bias_lds + n * 16 + 4 * g);
+                if constexpr (EPI == 2) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if constexpr (EPI == 2) v[r] = fmaxf(__builtin_fmaf(v[r], a.acc_scale, part[m][n][r]) + b4[r], relu_lo);
-                    else v[r] = fmaxf(v[r] * a.acc_scale + b4[r], relu_lo);   // relu_lo = 0 or -inf: one max, no select
+                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(__builtin_fmaf(v[r], a.acc_scale, part[m][n][r]) + b4[r], relu_lo);
+                } else {
+                    v = s4_finish(v, a.acc_scale, b4, relu_lo);
                 }
                 vmax = range_acc(vmax, v[0], v[1], v[2], v[3]);
                 if (a.dst_fmt) {
-                    store_px(co, pix, v);
+                    s4_store_px(sd, co, pix, v);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -561,7 +528,8 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
             const int rt = (a.fold_cout + 15) >> 4;
             const int Ho = a.Hout >> 1, Wo = a.Wout >> 1;       // a last row or column the pool drops is not stored
             const size_t hw2 = (size_t)Ho * Wo, term2 = (size_t)a.down_c4 * hw2 * 8;
-            const bool mis2 = (a.down_choff & 2) != 0, odd = (px & 1) != 0;
+            const S4Dst dd = {reinterpret_cast<char *>(a.down_dst) + (size_t)b * 2 * term2, term2, hw2, a.down_choff, a.down_limit};   // R's (down_fmt)
+            const bool odd = (px & 1) != 0;
             const int poy = tileY * (C::TH / 2) + wave, pox = tileX * (C::TW / 2) + (odd ? 8 : 0) + (px >> 1);
             const bool pin = poy < Ho && pox < Wo;
             const size_t ppix = (size_t)poy * Wo + pox;
@@ -597,34 +565,13 @@ __global__ __launch_bounds__(32 * TH_ * KS_, S4_KERNEL_WAVES) void S4_KERNEL_NAM
                 }
                 const float vm = range_acc(vmax2, pv[0], pv[1], pv[2], pv[3]);
                 vmax2 = pin ? vm : vmax2;
-                const int co = ct * 16 + 4 * g, chb = a.down_choff + co;   // store_px into R's destination, or fp32 NCHW
+                const int co = ct * 16 + 4 * g;
                 if (pin && !a.down_fmt) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (co + r < a.fold_cout) reinterpret_cast<float *>(a.down_dst)[((size_t)b * a.down_ctotal + chb + r) * hw2 + ppix] = pv[r];
+                        if (co + r < a.fold_cout) reinterpret_cast<float *>(a.down_dst)[((size_t)b * a.down_ctotal + a.down_choff + co + r) * hw2 + ppix] = pv[r];
                 } else if (pin && co < a.fold_cout + 2) {
-                    s4_h4 hi, mid;
-                    split_terms4(pv, hi, mid);
-                    const bool ok0 = chb < a.down_limit, ok1 = chb + 2 < a.down_limit;
-                    char *p = reinterpret_cast<char *>(a.down_dst) + (size_t)b * 2 * term2 + ppix * 8 + (size_t)(chb >> 2) * hw2 * 8;
-                    if (!mis2) {
-                        if (ok1) {
-                            *reinterpret_cast<s4_h4 *>(p) = hi;
-                            *reinterpret_cast<s4_h4 *>(p + term2) = mid;
-                        } else if (ok0) {
-                            *reinterpret_cast<h2 *>(p) = h2{hi[0], hi[1]};
-                            *reinterpret_cast<h2 *>(p + term2) = h2{mid[0], mid[1]};
-                        }
-                    } else {
-                        if (ok0) {
-                            *reinterpret_cast<h2 *>(p + 4) = h2{hi[0], hi[1]};
-                            *reinterpret_cast<h2 *>(p + 4 + term2) = h2{mid[0], mid[1]};
-                        }
-                        if (ok1) {
-                            *reinterpret_cast<h2 *>(p + hw2 * 8) = h2{hi[2], hi[3]};
-                            *reinterpret_cast<h2 *>(p + hw2 * 8 + term2) = h2{mid[2], mid[3]};
-                        }
-                    }
+                    s4_store_px(dd, co, ppix, pv);
                 }
             }
             range_commit(a.down_status, a.down_slot, vmax2);

@@ -182,6 +182,40 @@ def view_tensor(plan, ws, name, b, h, w):
     return out
 
 
+SLICES = [('A', 0, 10), ('B', 10, 10), ('C', 20, 18)]
+
+
+def slices_net(g, k, stride, src='t0'):
+    """t0 = conv3x3(input) (src = 't0' only); A, B, C = three k x k convs (stride `stride`) over t0 - or, src = 'input', over the fp32 network input - into
+    the slices 0 / 10 / 20 of `out` (38 channels: block growth (10, 18)); fin = a 3x3 conv over out, the packed-pair reader that makes
+    the plan keep `out` in that layout.  Returns the spec and its parameters"""
+    S = arch.Src
+    spec = MiniSpec(12)
+    from_t, cin, shapes = 0, 12, []
+    if src == 't0':
+        from_t, cin, shapes = spec.conv('t0', [S(0, 0, 12)], 24, 3), 24, [('t0', 12, 24, 3)]
+    out = spec.tensor('out', 38)
+    for name, off, ch in SLICES:
+        spec.conv(name, [S(from_t, 0, cin)], ch, k, stride=stride, dst=out, dst_choff=off)
+        shapes.append((name, cin, ch, k))
+    spec.conv('fin', [S(out, 0, 38)], 9, 3, relu=False)
+    shapes.append(('fin', 38, 9, 3))
+    P = {n: (torch.randn(co, ci, kk, kk, generator=g) / (ci * kk * kk) ** 0.5, torch.randn(co, generator=g) * 0.5) for n, ci, co, kk in shapes}
+    return spec, P
+
+
+def pooled_net(g, cout=18):
+    """dn = a 1x1 conv with ReLU over the fp32 network input, pl = its 2x2 average pool, fin = a 3x3 conv over pl: the packed-pair reader
+    that makes an fp32-source kernel store the pooled tensor (cout = 18: half of its last group) as packed pairs"""
+    S = arch.Src
+    spec = MiniSpec(12)
+    pl = spec.pool('pl', spec.conv('dn', [S(0, 0, 12)], cout, 1))
+    spec.conv('fin', [S(pl, 0, cout)], 9, 3, relu=False)
+    shapes = [('dn', 12, cout, 1), ('fin', cout, 9, 3)]
+    P = {n: (torch.randn(co, ci, kk, kk, generator=g) / (ci * kk * kk) ** 0.5, torch.randn(co, generator=g) * 0.5) for n, ci, co, kk in shapes}
+    return spec, P
+
+
 class MiniTrain:
     """A hand-built op table through the training entry points (pf_train_*), dense input.  ``params``: {op name: dict(w=,
     gamma=, beta=, mean=, var=) for conv+BN ops, dict(w=, b=) for plain convs} (CPU tensors)."""

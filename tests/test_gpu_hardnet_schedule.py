@@ -18,7 +18,7 @@ FAMILY = {'S_CONV_GENERIC': 'conv_mfma_kernel', 'S_CONV_SPLIT': 'conv_split_kern
 
 
 def kernel_of(spec, r):
-    """the profile label of a convolution step's launch (csrc/conv_s4.hip: launch_s4_form, launch_s41_cfg), or its kernel family"""
+    """the profile label of a convolution step's launch (csrc/conv_s4.hip: launch_s4_form; conv_s4_1x1.hip: launch_s41_cfg), or its kernel family"""
     kind = KIND_NAME[r[KIND]]
     if kind in FAMILY:
         return FAMILY[kind]

@@ -359,6 +359,44 @@ int pf_iiou_status(const void *ws, void *stream, int *host_status);
 int pf_iiou_status_reset(void *ws, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cityscapes ground-truth preparation — what createPanopticImgs and createTrainIdLabelImgs of cityscapesscripts.preparation (absent
+ * here, written down as remembered: parity unpinned) and the reference's scripts/preprocessing/remove_fg_from_gt.py compute, from
+ * the one file per image they all derive from.
+ *
+ *   inst            [B,H,W] instance maps (*_gtFine_instanceIds.png): 0 = u16, 1 = i32, 2 = i64.  A value v below 1000 is a labelId L,
+ *                   any other is L * 1000 + instance index.  The base pointer need only be aligned to its element; where the map is
+ *                   not 16-byte aligned relative to the outputs it is read per element.
+ *   out_rgb         (nullable) [B,H,W,3] u8, the panoptic PNG's pixels: (0,0,0) where L is ignoreInEval, else
+ *                   (v % 256, v / 256 % 256, v / 65536).
+ *   out_train       (nullable) [B,H,W] u8, the trainId of L; 255 for a label without one.
+ *   out_train_nofg  (nullable) [B,H,W] u8, the same with the thing classes (trainIds 11..18: hasInstances and not ignoreInEval)
+ *                   replaced by 255.
+ *   seg_count       (nullable, with segs) [B] i32;  segs [B][pf_gt_prepare_max_segments() = 1024][6] i32: an image's segments in
+ *                   ascending v, each {v, area, x, y, width, height} with the tight pixel box (first and last non-empty column and
+ *                   row).  Segments of ignoreInEval labels are not listed; a stuff label with an instance part (7001) is.  Rows from
+ *                   seg_count[b] on are not written.
+ * A null output is not computed.  The pixel outputs and ws must be 16-byte aligned.  H * W < 2^31.
+ * Legal values: [0, 34) and [1000, 34000).  Integers only - two runs of a call give the same bits.  Never silent: the first word
+ * of the workspace is a sticky status word, ORed with
+ *   PF_GTPREP_STATUS_FULL   an image has more listed segments than the list holds
+ *   PF_GTPREP_STATUS_VALUE  a value in [34, 1000), a label of 34 or more, or a negative or wide i32 / i64 value (compared in the
+ *                           map's own width: 2^33 + 7 is illegal)
+ * and an image flagged with either lists zero segments (its illegal pixels are written as void: black, 255); the other images of
+ * the batch are untouched.  The caller zeroes the first 256 bytes of a fresh workspace once (pf_gt_prepare_status_reset enqueues
+ * that); everything else is zeroed by every call with the library's own fill kernel, so a captured call holds kernel nodes only.
+ * pf_gt_prepare enqueues only (3 launches: fill, stream, finish); B == 0 launches nothing.  pf_gt_prepare_status copies the status
+ * word to the host and waits for the stream.
+ */
+#define PF_GTPREP_STATUS_FULL 1u
+#define PF_GTPREP_STATUS_VALUE 2u
+int pf_gt_prepare_workspace(int B, size_t *bytes);
+int pf_gt_prepare_max_segments(void);
+int pf_gt_prepare(const void *inst, int inst_kind, int B, int H, int W, uint8_t *out_rgb, uint8_t *out_train, uint8_t *out_train_nofg,
+                  int *seg_count, int *segs, void *ws, size_t ws_bytes, void *stream);
+int pf_gt_prepare_status(const void *ws, void *stream, int *host_status);
+int pf_gt_prepare_status_reset(void *ws, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * pf_bg_dense_input - the network input of BGModel.forward (models/bg/bg_model.py:61-69) for the configurations the fused stem
  * of pf_bg_forward does not cover (convert2onehot = False, or no depth channels): writes x [B, T*C (+T), H, W] f32 for
  * pf_hardnet_forward_dense.
@@ -809,6 +847,10 @@ int pf_debug_fg_schedule(int N, int T_in, int T_out, int flags, long long *regio
  * from head on by unit loads.  head is the fewest pixels below 16 that align both maps, failing that map a alone, clamped to n. */
 int pf_debug_label_scan_span(unsigned long long addr_a, unsigned long long addr_b, int esz_a, int esz_b, int align_a, int align_b,
                              unsigned long long n, int P, unsigned long long *out5);
+/* Host only, no device involved (tests): row `index` (0 .. 34) of the Cityscapes label table behind pf_gt_prepare (csrc/gt_labels.h).
+ * out8 = {id, trainId, category id, hasInstances, ignoreInEval, r, g, b}; name and category are NUL-terminated, cut to their
+ * capacities.  PF_EINVAL past the table's end. */
+int pf_debug_gt_labels(int index, int *out8, char *name, size_t name_cap, char *category, size_t category_cap);
 /* Instrumented builds only (make libpfhip_probe.so, env PF_PROBE=1): the 64 in-kernel timestamps (shader clock)
  * written by workgroup 0 / wave 0 of the last conv_wave launch; PF_EINVAL when nothing was recorded. */
 int pf_debug_probe_read(long long *host64);

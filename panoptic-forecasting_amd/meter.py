@@ -1,4 +1,5 @@
-"""What the device meters (pq.PanopticQuality, semantic_iou.SemanticIoU) share: workspaces that begin with a sticky status word.
+"""What the device meters (pq.PanopticQuality, semantic_iou.SemanticIoU) and gt_prep.GTPreparer share: workspaces that begin with a
+sticky status word.
 
 A workspace ``which`` belongs to the entry points pf_<which>_workspace / _accumulate / _status / _status_reset of include/pfhip.h:
 bytes [0, 256) hold the status word and are cleared by the host only, everything behind them is zeroed by every call.
@@ -11,6 +12,7 @@ import torch
 class DeviceMeter:
     WORKSPACES = {}      # which -> (attribute that holds its tensor, how the growth error names it: '' or 'name ')
     HOST_PATH = ''       # the function that does the same on the host, for the refusal of a CPU device
+    ENQUEUE = 'update'   # the method that enqueues a call, for the growth error
 
     def __init__(self, device):
         from . import lib as _lib
@@ -28,7 +30,7 @@ class DeviceMeter:
 
     def _workspace(self, b, which):
         """The workspace grows with the largest B seen.  A captured graph keeps the pointer it was captured with, so a
-        workspace may not grow during a capture or after one: call update once with the largest batch before capturing."""
+        workspace may not grow during a capture or after one: call the enqueuing method once with the largest batch before capturing."""
         attr, label = self.WORKSPACES[which]
         old = getattr(self, attr)
         need = ctypes.c_size_t()
@@ -37,8 +39,8 @@ class DeviceMeter:
         if old is None or old.numel() < need.value:
             if capturing or self._captured:
                 raise self._lib.PfError('%s: the %sworkspace would have to grow to B = %d %s a graph capture, whose replays '
-                                        'keep the old pointer: call update() with the largest batch before capturing'
-                                        % (type(self).__name__, label, b, 'during' if capturing else 'after'))
+                                        'keep the old pointer: call %s() with the largest batch before capturing'
+                                        % (type(self).__name__, label, b, 'during' if capturing else 'after', self.ENQUEUE))
             ws = torch.zeros(need.value, dtype=torch.uint8, device=self.device)    # status word starts at 0
             if old is not None:
                 ws[:256].copy_(old[:256])                                            # a sticky bit survives the growth

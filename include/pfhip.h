@@ -359,6 +359,77 @@ int pf_iiou_status(const void *ws, void *stream, int *host_status);
 int pf_iiou_status_reset(void *ws, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Instance AP — the integer records behind AP / AP50 of the Cityscapes instance-level evaluation
+ * (cityscapesscripts.evaluation.evalInstanceLevelSemanticLabeling: absent here; the definition below is written down from that
+ * evaluator as remembered: parity unpinned).  pf_ap_accumulate intersects every predicted mask with every ground-truth region of
+ * its label; everything after the records is float64 on the host (instance_ap.ap_from_records).
+ *
+ * Constants.  Instance classes are labelIds 24, 25, 26, 27, 28, 31, 32, 33 (person .. bicycle; trainIds 11..18), in that order
+ *   class index 0..7.  The overlap thresholds are the float64 values of np.arange(0.5, 1.0, 0.05), taken verbatim and not as
+ *   rounded decimals: the third is 0.6000000000000001.  min_region is an integer parameter, default 100.  The distance criteria
+ *   of the original (AP50m / AP100m) are not built.
+ * Ground truth.  In an image's instance map a value v < 1000 is the labelId v with no instance; for an instance class this is a
+ *   *group*.  A value v >= 1000 is instance v % 1000 of label v / 1000.  Void pixels are those whose value is the id of an
+ *   ignore_in_eval label (csrc/gt_labels.h).  A ground-truth region of class c is *regular* when v >= 1000 and its pixel count
+ *   is >= min_region.
+ * Prediction p.  A binary mask (inside = non-zero), a labelId and a confidence.  It is *skipped* if its label is not an instance
+ *   class or its mask is empty; otherwise it is *counted*.
+ * Per counted prediction, integers only.  `pixels` is the mask's pixel count.  For every ground-truth value g of the same label
+ *   (regular, small or group) inter(p, g) is the intersection pixel count.
+ *   ignore = |mask & void| + sum of inter(p, g) over groups + sum of inter(p, g) over g with fewer than min_region pixels; a
+ *   small group is added twice, as in the original.  `best` is the g with the largest non-zero intersection, ties to the smaller
+ *   value; its value, inter and g's own pixel count are recorded.  Only `best` matters at every threshold: an overlap
+ *   inter / (|g| + pixels - inter) > 0.5 forces inter > pixels / 2, so the full pairwise matching of the original reduces to it.
+ * Per class c and threshold t, over all images.  A counted prediction *hits* when its best exists and
+ *   float(inter) / (|g| + pixels - inter) > t.  A hit on a regular g: among the predictions of that image hitting that g the one
+ *   of highest confidence is a true positive (1, conf), the others are false positives (0, conf); equal confidences are
+ *   indistinguishable in the lists.  A hit on a group or a small region: the prediction is dropped.  No hit: it is a false
+ *   positive (0, conf) when float(ignore) / pixels <= t, else it is dropped.  hard_fn is the number of regular g that no
+ *   prediction hits.
+ * AP.  have_gt: any image has a regular g of c.  have_pred: any image has a counted prediction of c.  AP is nan without have_gt
+ *   and 0.0 with have_gt but without have_pred.  AP is 0.0 when every prediction was dropped (the original would raise there).
+ *   Otherwise the original's curve: sort the scores ascending; take the unique scores with their first indices; for each
+ *   tp = n_true - cum[idx - 1], fp = n - idx - tp, fn = cum[idx - 1] + hard_fn (0 appended to the cumulative sum, so index -1
+ *   reads 0); append precision 1 and recall 0; the step widths are np.convolve([r0, r..., 0], [-0.5, 0, 0.5], 'valid'); AP is
+ *   precision . widths.  The result does not depend on the order of the records.  Reported: per class `ap` (mean over the ten
+ *   thresholds) and `ap50%`; allAp, the nan-mean over classes x thresholds; allAp50%, the nan-mean over classes at t = 0.5.
+ *
+ *   masks       [P][H][W] u8, inside = non-zero; any base alignment.
+ *   mask_image  [P] i32, the index of the mask's image in gt; may be unsorted, an image's masks need not be contiguous.
+ *   mask_label  [P] i32, a labelId.
+ *   gt          [B][H][W] instance map (*_gtFine_instanceIds.png): gt_kind 0 = u16, 1 = i32, 2 = i64, aligned to its element.
+ *   rec         [P][8] i32, written: {state, pixels, ignore, best_value (-1: none), best_inter, best_pixels, image, class index}.
+ *               state 0 counted, 1 empty, 2 not an instance class, 3 flagged.  Only a counted record carries counts (the others
+ *               hold pixels = ignore = best_inter = best_pixels = 0 and best_value = -1); image is mask_image as given; class
+ *               index is -1 where the label is no instance class or out of range.
+ *   gt_regular  [B][8] i32, written: the number of regular regions per class; zero for a flagged image.
+ * Passes (5 launches: fill, size, overlap, record, regular; all kernel nodes): the size pass scans gt alone into a dense per-image
+ * table u32 [8][1008] of region sizes (1000 instances + the group per class); the overlap pass (grid: chunks of
+ * pf_ap_chunk_pixels() = 16384 pixels x P) folds runs of equal (inside, value) in registers, classifies a run inside the mask once
+ * and counts it in a dense 4 KB table in LDS (1000 instances + group + void + pixels of the prediction's own label), added to the
+ * prediction's u32 [1024] table in the workspace with integer atomics; one wave per prediction then writes rec, one workgroup per
+ * image gt_regular.  No floating point on the device.  P == 0 runs the fill, size and regular passes only, B == 0 the record pass
+ * only (every prediction is flagged; nothing of the workspace but the status word is touched).  H * W must be below 2^30, P and B at most 65535.
+ * The first word of the workspace is a sticky status word of its own, ORed with
+ *   PF_AP_STATUS_VALUE  a gt value outside [0, 65536), compared in the map's own width.  The image and its predictions are
+ *                       flagged and add nothing.
+ *   PF_AP_STATUS_INDEX  a mask_image outside [0, B) or a mask_label outside [0, 34).  The prediction is flagged.
+ * The caller zeroes the first 256 bytes of a fresh workspace once (pf_ap_status_reset enqueues that); everything else is zeroed by
+ * every call with the library's own fill kernel.  pf_ap_status copies the status word to the host and waits for the stream.
+ */
+#define PF_AP_STATUS_VALUE 1u
+#define PF_AP_STATUS_INDEX 2u
+int pf_ap_workspace(int P, int B, size_t *bytes);
+int pf_ap_chunk_pixels(void);
+int pf_ap_accumulate(const void *masks, const int *mask_image, const int *mask_label, int P, const void *gt, int gt_kind, int B, int H,
+                     int W, int min_region, int *rec, int *gt_regular, void *ws, size_t ws_bytes, void *stream);
+int pf_ap_status(const void *ws, void *stream, int *host_status);
+int pf_ap_status_reset(void *ws, void *stream);
+/* Host only, nothing enqueued (tests): the slot of the overlap pass's table that a pixel inside a mask of `label` adds to when the
+ * ground truth holds `value`: 0..999 instance k, 1000 the group, 1001 void, -1 neither (or label is no instance class). */
+int pf_debug_ap_slot(int value, int label, int *slot);
+
+/* ------------------------------------------------------------------------------------------
  * Cityscapes ground-truth preparation — what createPanopticImgs and createTrainIdLabelImgs of cityscapesscripts.preparation (absent
  * here, written down as remembered: parity unpinned) and the reference's scripts/preprocessing/remove_fg_from_gt.py compute, from
  * the one file per image they all derive from.

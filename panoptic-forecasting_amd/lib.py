@@ -59,6 +59,11 @@ SIGNATURES = {
     'pf_iiou_accumulate': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'pf_iiou_status': (_i, [_vp, _vp, _c.POINTER(_i)]),
     'pf_iiou_status_reset': (_i, [_vp, _vp]),
+    'pf_ap_workspace': (_i, [_i, _i, _c.POINTER(_sz)]),
+    'pf_ap_chunk_pixels': (_i, []),
+    'pf_ap_accumulate': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'pf_ap_status': (_i, [_vp, _vp, _c.POINTER(_i)]),
+    'pf_ap_status_reset': (_i, [_vp, _vp]),
     'pf_gt_prepare_workspace': (_i, [_i, _c.POINTER(_sz)]),
     'pf_gt_prepare_max_segments': (_i, []),
     'pf_gt_prepare': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -113,6 +118,7 @@ SIGNATURES = {
     'pf_debug_fg_schedule': (_i, [_i, _i, _i, _i, _vp, _i, _c.POINTER(_i), _vp, _vp, _i, _c.POINTER(_i)]),
     'pf_debug_label_scan_span': (_i, [_c.c_ulonglong, _c.c_ulonglong, _i, _i, _i, _i, _c.c_ulonglong, _i, _c.POINTER(_c.c_ulonglong)]),
     'pf_debug_gt_labels': (_i, [_i, _c.POINTER(_i), _c.c_char_p, _sz, _c.c_char_p, _sz]),
+    'pf_debug_ap_slot': (_i, [_i, _i, _c.POINTER(_i)]),
     'pf_profile_enable': (_i, [_i]),
     'pf_profile_collect': (_i, []),
     'pf_profile_get': (_i, [_i, _c.c_char_p, _sz, _c.POINTER(_i), _c.POINTER(_c.c_double),
